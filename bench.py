@@ -2,6 +2,7 @@
 """bench.py -- env steps/s of the tensor-game step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--samples n] [--scaling weak|strong] [--global-batch G]
+                    [--dump-outputs DIR]
 
 A "step" is ONE launch of the hot-path kernel (tg_step_i8, in place) over the whole batch of games resident in
 HBM.  Workloads:
@@ -241,9 +242,16 @@ class StepTimer:
         while self.pos % self.L != p0 % self.L:
             self.eager(1)
 
-    def measure(self, K, W, samples, sync=None):
+    def outputs(self, games=None):
+        """What a caller of the step holds after it: state, done and overflow, on the device (copies; every game, or
+        the game ids in `games`)."""
+        take = (lambda t: t.clone()) if games is None else (lambda t: t.index_select(0, games))
+        return {"state": take(self.state), "done": take(self.done), "overflow": take(self.ovf)}
+
+    def measure(self, K, W, samples, sync=None, keep=False, keep_games=None):
         """Returns dict(wall_s=[...], event_ms=[...], ok).  Wall samples are sync-bracketed; event samples come
-        from a second pass with the replays enqueued back to back."""
+        from a second pass with the replays enqueued back to back.  keep=True adds `outputs`: self.outputs(keep_games)
+        as the last step of the last wall sample left them (copied after that sample's clock stopped)."""
         self.eager(W)
         torch.cuda.synchronize(self.dev)
         p0 = self.pos
@@ -262,6 +270,7 @@ class StepTimer:
             self.run_k(K)
             torch.cuda.synchronize(self.dev)
             walls.append(time.perf_counter() - t0)
+        last = self.outputs(keep_games) if keep else None
         if sync:
             sync()
         self._rewind(p0)
@@ -294,7 +303,7 @@ class StepTimer:
         t = [evs[i].elapsed_time(evs[i + 1]) for i in range(len(seq))]
         event_ms = [t[2 * i] - t[2 * i + 1] for i in range(samples)]          # exactly K launches each
         replay_ms = [t[2 * i] for i in range(samples)]                         # one run of m + K launches, as it is
-        return {"wall_s": walls, "event_ms": event_ms, "ok": self.check(), "lead_in": m,
+        return {"wall_s": walls, "event_ms": event_ms, "ok": self.check(), "lead_in": m, "outputs": last,
                 "run_ms_with_lead_in": replay_ms, "run_ms_lead_in_only": [t[2 * i + 1] for i in range(samples)]}
 
 
@@ -540,21 +549,55 @@ def write_side_file(full, also):
     return written
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: every .npy file of the run together
+
+
+def dump_games(B, S, world, dev):
+    """The games whose outputs --dump-outputs writes: all B while this rank's share of DUMP_BYTES holds their state,
+    done and overflow in float32, else a fixed seeded sample of them (sorted; their ids go to game_index)."""
+    n = (DUMP_BYTES // world - 4096) // (4 * (S ** 3 + 2) + 8)
+    if n >= B:
+        return None
+    g = torch.Generator(device="cpu").manual_seed(0)
+    return torch.randperm(B, generator=g)[:n].sort().values.to(dev)
+
+
+def write_outputs(dirpath, res, lo, rank, world):
+    """--dump-outputs: the arrays the timed step hands its caller after the last timed step (StepTimer.outputs) as
+    DIR/<name>.npy in float32 -- state (B,S,S,S), done (B,), overflow (B,) -- plus game_index (float64, global game
+    ids) when they are a sample.  A rank's files carry a _rank<r> suffix when there is more than one."""
+    import numpy as np
+
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v.float().cpu().numpy() for k, v in res["outputs"].items()}
+    if res["outputs_games"] is not None:
+        arrays["game_index"] = (res["outputs_games"].cpu() + lo).double().numpy()
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(d / f"{name}{suffix}.npy", a)
+    return sorted(arrays)
+
+
 def demo_rank(S):
     return 7 if S == 4 else 8
 
 
-def sharded_step(group, G, S, dev, mode, K, W, samples, seed=0):
+def sharded_step(group, G, S, dev, mode, K, W, samples, seed=0, keep=False):
     """One sharded measurement, every rank taking part: G games in total, this rank's contiguous range of global ids,
     W warm-up + `samples` samples of exactly K in-place steps, each bracketed by barrier + synchronize; the wall time
-    per sample and the event-timed launch time are MAX-reduced over the ranks."""
+    per sample and the event-timed launch time are MAX-reduced over the ranks.  keep=True: res["outputs"] holds this
+    rank's outputs of the last timed step (dump_games chooses the games)."""
     from mat_mul_amd import shard_range
 
     lo, hi = shard_range(G, group.rank, group.world)
     B = hi - lo
     start, sched, _ = make_demo_schedule(B, S, demo_rank(S), dev, seed, lo)
     tm = StepTimer(start, sched, dev, mode)
-    res = tm.measure(K, W, samples, sync=group.barrier)
+    games = dump_games(B, S, group.world, dev) if keep else None
+    res = tm.measure(K, W, samples, sync=group.barrier, keep=keep, keep_games=games)
+    if keep:
+        res["outputs_games"] = games
     my_launch_us = statistics.median(res["event_ms"]) * 1e3 / K
     my_fixed_us = statistics.median(res["run_ms_lead_in_only"]) * 1e3 - res["lead_in"] * my_launch_us
     reduced = group.max_over_ranks(*res["wall_s"], 0.0 if res["ok"] else 1.0, my_launch_us, my_fixed_us)
@@ -680,7 +723,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2016)
+    ap.add_argument("--steps", type=int, default=2016, help="timed steps per sample; ms_per_step = the median sample / K")
     ap.add_argument("--warmup", type=int, default=224)
     ap.add_argument("--samples", type=int, default=9, help="timed samples of exactly --steps steps each (median reported)")
     ap.add_argument("--mode", choices=["graph", "eager"], default="graph",
@@ -696,6 +739,9 @@ def main(argv=None):
     ap.add_argument("--print-also", action="store_true", help="print the `also` entries as separate lines BEFORE the contract line")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous, shard arithmetic and the JSON line only -- no GPU work (CPU test of the N>1 path)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (state, done, overflow) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed seeded sample of the games beyond that)")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -767,9 +813,11 @@ def main(argv=None):
     group.barrier()
     from mat_mul_amd import _lib  # noqa: F401  (raises if libtensorgame.so or a symbol is missing: no CPU path)
 
-    m = sharded_step(group, G, S, dev, args.mode, args.steps, args.warmup, args.samples)
+    m = sharded_step(group, G, S, dev, args.mode, args.steps, args.warmup, args.samples, keep=bool(args.dump_outputs))
     res, sched, walls, wall = m["res"], m["sched"], m["walls"], m["wall"]
     extras = sharded_extras(group, world, dev, args.mode, args.steps, m) if world > 1 and not args.no_also else {}
+    if args.dump_outputs and rank != 0:
+        write_outputs(args.dump_outputs, res, lo, rank, world)
 
     if rank == 0:
         need = needed_bytes_per_launch(B, S, sched)
@@ -816,6 +864,8 @@ def main(argv=None):
             if "streamed_share_of_8_us_per_step" in c4 and "streamed_whole_us_per_step" in c4:
                 c4["predicted_speedup_8gpu_streamed"] = round(c4["streamed_whole_us_per_step"] / c4["streamed_share_of_8_us_per_step"], 3)
             out["also_ok"] = {"entries": len(also), "failed": [a["workload"][:60] for a in also if not a.get("ok", True)]}
+        if args.dump_outputs:
+            out["dumped_outputs"] = write_outputs(args.dump_outputs, res, lo, rank, world)
         if also or world > 1:
             out["also_file"] = write_side_file(out, also)
         if args.print_also:

@@ -1,6 +1,6 @@
 """bench.py pieces that do not need a GPU: the algorithmic byte counts of SURVEY.md section 8(d), the
 roofline object's arithmetic (no fraction above 1 from skipped stores), the committed traffic file it reads,
-and the N>1 self-launch path (two gloo ranks, --dry-run)."""
+the N>1 self-launch path (two gloo ranks, --dry-run) and the size bound of --dump-outputs."""
 import importlib.util
 import json
 import os
@@ -194,6 +194,36 @@ def test_side_file_holds_what_left_the_line(bench, tmp_path, monkeypatch):
     doc = json.loads((tmp_path / name).read_text())
     assert doc["headline"]["roofline"]["method"].startswith("HIP events") and doc["also"][0]["workload"] == "x"
     assert "launch_us_samples" in doc["headline"]["roofline"] and "timing" in doc["headline"]["config"]
+
+
+@pytest.mark.parametrize("B,S,world", [(65536, 4, 1), (8192, 16, 1), (1 << 19, 4, 2), (32768, 25, 1)])
+def test_dumped_outputs_fit_64_mb(bench, tmp_path, B, S, world):
+    """--dump-outputs writes every game while state + done + overflow fit in float32, else the same seeded sample of
+    games in every run, with their global ids; all ranks' files together stay within 64 MB."""
+    import numpy as np
+
+    games = bench.dump_games(B, S, world, "cpu")
+    n = B if games is None else len(games)
+    if games is not None:
+        assert torch.equal(games, bench.dump_games(B, S, world, "cpu")) and bool((games[1:] > games[:-1]).all())
+        assert 0 <= int(games[0]) and int(games[-1]) < B and n * (4 * (S ** 3 + 2) + 8) * world > 60_000_000
+    else:
+        assert B * S ** 3 * 4 < 60_000_000
+    res = {"outputs": {"state": torch.ones((n, S, S, S), dtype=torch.int8), "done": torch.zeros(n, dtype=torch.uint8),
+                       "overflow": torch.zeros(n, dtype=torch.uint8)}, "outputs_games": games}
+    lo = 123
+    for rank in range(world):
+        names = bench.write_outputs(tmp_path, res, lo, rank, world)
+    assert names == sorted(["done", "overflow", "state"] + (["game_index"] if games is not None else []))
+    files = sorted(tmp_path.iterdir())
+    assert len(files) == world * (3 + (games is not None))
+    assert sum(f.stat().st_size for f in files) <= 64_000_000
+    sfx = "_rank0" if world > 1 else ""
+    st = np.load(tmp_path / f"state{sfx}.npy")
+    assert st.dtype == np.float32 and st.shape == (n, S, S, S) and np.load(tmp_path / f"done{sfx}.npy").dtype == np.float32
+    if games is not None:
+        gi = np.load(tmp_path / f"game_index{sfx}.npy")
+        assert gi.dtype == np.float64 and np.array_equal(gi, games.numpy() + lo)
 
 
 def test_wrong_world_size_is_refused():

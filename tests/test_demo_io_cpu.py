@@ -1,16 +1,10 @@
 """N4: packed demo files and the reference's on-disk layout.  CPU only."""
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
 from mat_mul_amd import demo_io
 from oracle import tensor_game as O
-
-REF = Path("/root/reference")
 
 
 def _demos(B=5, S=4, R=6, seed=3):
@@ -44,30 +38,24 @@ def test_reference_layout_roundtrip(tmp_path):
     assert torch.equal(tok2, tok) and torch.equal(tgt2, tgt)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="the reference only exists in the build container")
-def test_reference_dataset_reads_our_files(tmp_path):
-    """The reference's own SyntheticDemoDataset(overwrite=False) consumes the exported files, and its
-    __getitem__ (datasets.py:78-122) returns what the oracle predicts for our tokens."""
+def test_reference_dataset_reads_our_files(tmp_path, golden):
+    """The reference's own SyntheticDemoDataset(overwrite=False) consumed the exported files of these demos, and what
+    its __getitem__ (datasets.py:78-122) returned is recorded (tests/golden/reference_dataset_getitem.npz,
+    make_golden_reference_runs.py).  The files written today carry the same demos in the reference's layout, read the
+    way the dataset reads them (datasets.py:55, 86-89), and the oracle predicts the recorded items from them."""
+    g = golden("reference_dataset_getitem")
     tok, tgt = _demos(B=3, S=4, R=7, seed=11)
+    assert np.array_equal(tok.numpy(), g["tokens"]) and np.array_equal(tgt.numpy(), g["target"])
     demo_io.export_reference_layout(tmp_path / "d", tok, tgt)
-    np.save(tmp_path / "tok.npy", tok.numpy())
-    np.save(tmp_path / "tgt.npy", tgt.numpy())
-    script = f"""
-import sys, numpy as np, torch
-sys.dont_write_bytecode = True
-sys.path.insert(0, {str(REF)!r})
-import datasets
-ds = datasets.SyntheticDemoDataset(7, 3, 2, 4, "cpu", overwrite=False, save_dir={str(tmp_path / 'd')!r})
-assert ds.n_demos == 3 and len(ds) == 21
-out = [ds[i] for i in range(21)]
-np.save({str(tmp_path / 'frames.npy')!r}, np.stack([o[0].numpy() for o in out]))
-np.save({str(tmp_path / 'meta.npy')!r}, np.array([[o[1].item(), o[3].item()] for o in out]))
-np.save({str(tmp_path / 'act.npy')!r}, np.stack([o[2].numpy() for o in out]))
-"""
-    subprocess.run([sys.executable, "-c", script], check=True, cwd=tmp_path, timeout=300)
-    frames, meta, act = (np.load(tmp_path / n) for n in ("frames.npy", "meta.npy", "act.npy"))
+    assert len(list((tmp_path / "d").glob("target_tensor_*.pt"))) == 3
     for i in range(21):
         d, ia = divmod(i, 7)
-        f, sc, a, rw = O.demo_getitem(list(tok[d].numpy()), tgt[d].numpy(), ia, 2)
-        assert np.array_equal(frames[i], f.astype(np.float32)) and meta[i].tolist() == [sc, rw]
-        assert np.array_equal(act[i], a)
+        seq = torch.load(tmp_path / "d" / f"action_seq_{d}.pt")
+        target = torch.load(tmp_path / "d" / f"target_tensor_{d}.pt")
+        assert isinstance(seq, list) and all(a.dtype == torch.int64 for a in seq) and target.dtype == torch.float32
+        f, sc, a, rw = O.demo_getitem([s.numpy() for s in seq], target.numpy(), ia, 2)
+        assert np.array_equal(g["frames"][i], f) and g["meta"][i].tolist() == [sc, rw]
+        assert np.array_equal(g["action"][i], a)
+        # and from the tokens as generated, without the files
+        f2, sc2, a2, rw2 = O.demo_getitem(list(tok[d].numpy()), tgt[d].numpy(), ia, 2)
+        assert np.array_equal(f2, f) and [sc2, rw2] == [sc, rw] and np.array_equal(a2, a)

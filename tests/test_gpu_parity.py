@@ -1308,6 +1308,47 @@ def test_integration_md_stub_runs_against_strassen_golden(golden, tmp_path):
     assert np.array_equal(host(kids), wk[0]) and np.array_equal(host(dn), wdn[0]) and np.array_equal(host(ch), wch[0])
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed step handed its caller after the last timed step -- state,
+    done and overflow in float32 -- the same files again for the same arguments, equal to the oracle's replay of the
+    bench schedule to that step (W + samples * K steps into it); beyond 64 MB (S=16, 8 192 games) a seeded sample."""
+    import json, subprocess, sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    W, K, n = 5, 16, 2
+
+    def run(out, *extra):
+        res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                              "--samples", str(n), "--no-also", "--no-cpu-baseline", "--dump-outputs", str(out), *extra],
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == K and line["samples"] == n and line["ms_per_step"] > 0
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+        return {p.stem: np.load(p) for p in out.iterdir()}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert sorted(a) == sorted(b) == ["done", "overflow", "state"]
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    c = run(tmp_path / "c", "--dim", "16", "--batch", "8192")
+    assert sorted(c) == ["done", "game_index", "overflow", "state"] and 0 < len(c["game_index"]) < 8192
+    for S, B, got in ((4, 65536, a), (16, 8192, c)):
+        R = 7 if S == 4 else 8                                   # bench.demo_rank: the schedule has period 2R
+        tok, st = (host(t) for t in ops.gen_demos(B, S, R, DEV, seed=0))
+        if "game_index" in got:
+            games = got["game_index"].astype(np.int64)
+            tok, st = tok[games], st[games]
+        assert (W + n * K) % (2 * R)
+        for k in range((W + n * K) % (2 * R)):
+            act = tok[:, k % R].copy()
+            if k >= R:
+                act[:, :S] = 2 - act[:, :S]                     # the second half adds the terms back
+            st, done, ovf = O.step_i8(st, act)
+        assert got["state"].shape == st.shape and np.array_equal(got["state"], st), S
+        assert np.array_equal(got["done"], done) and np.array_equal(got["overflow"], ovf), S
+
+
 def test_bench_two_ranks_self_launched_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2` with no launcher: bench.py starts its own ranks (torch.distributed.run children).
     On the one-GPU box both ranks share the GPU and the control plane is gloo (TG_BENCH_BACKEND).  The contract line is
