@@ -2970,10 +2970,11 @@ int tg_step_stream_i8(int8_t* state, const int8_t* actions, uint8_t* done, uint8
     if (variant < 0) {
       // beyond what the device keeps resident: without ready words no producer can be waiting for the whole batch, so the
       // units (64 games each, the one-game-per-lane kernel) simply run in rounds, every wavefront taking its games
-      // through all K steps
+      // through all K steps.  Always the lane kernel, whatever the A/B switches say: they choose among RESIDENT layouts only,
+      // and a caller sizes progress for the rounds by this fixed layout (ops.step_stream: one word per 64 games)
       if (ready) return tg_step_stream_layout(B, S, nullptr, nullptr);  // (fails with the message that names the capacity)
-      variant = TG_SWITCH("TG_STREAM_NO_LANES") ? 1 : kStreamLanes;
-      gpu_ = variant == kStreamLanes ? 64 : 16;
+      variant = kStreamLanes;
+      gpu_ = 64;
       units = (B + gpu_ - 1) / gpu_;
     }
   }

@@ -453,6 +453,16 @@ def seen_u64(keys, table: set, mask=None, insert=False) -> np.ndarray:
     return fresh
 
 
+def seen_u64_np(keys, table_keys, mask=None) -> np.ndarray:
+    """``seen_u64`` vectorised for large calls (no insert): fresh[i] = mask[i] and keys[i] not among ``table_keys`` (the
+    table's contents BEFORE the call, any array of uint64 keys).  Equal keys within one call are all fresh alike: the
+    decision is against the table as it was, never against earlier keys of the same call."""
+    k = np.asarray(keys, np.uint64)
+    m = np.ones(k.shape, bool) if mask is None else np.asarray(mask).astype(bool)
+    known = np.isin(k, np.unique(np.asarray(table_keys, np.uint64)))
+    return (m & ~known).astype(np.uint8)
+
+
 def tree_filter(parent, actions, table: set, shift=1):
     """The candidate filter of extend_tree (act.py:183-195) for ONE expanded state: children = parent - tensor(action)
     (get_child_states, act.py:266-275), drop the children equal to the parent (remove_null_actions, utils.py:191-194),

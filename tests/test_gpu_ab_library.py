@@ -286,6 +286,54 @@ def test_stream_lane_kernel_forced_at_small_batches(env_name, tmp_path):
     _run(LANES_SCRIPT, tmp_path, "LANES_OK", {env_name: "1"})
 
 
+ROUNDS_SCRIPT = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+from mat_mul_amd import ops, _lib
+from oracle import tensor_game as O
+from oracle.c_oracle import COracle
+assert _lib.AB_VARIANT
+DEV = "cuda:0"
+CO = COracle()
+S, K, CANARY = 4, 5, 0x5A5A5A5A
+B = ops.step_stream_capacity(S, DEV) + 37          # beyond every resident layout: units run in rounds, no ready words
+rng = np.random.default_rng(41)
+st = rng.integers(-2, 3, size=(B, S, S, S)).astype(np.int8)
+ac = rng.integers(0, 3, size=(K, B, 3 * S)).astype(np.int8)
+for b in (0, 15, 16, 63, 64, B - 17, B - 16, B - 1):  # terminal games at unit boundaries of both layouts (16 and 64 games)
+    st[b] = O.action_to_tensor(ac[0, b]).astype(np.int8)
+st[1::997] = 127                                  # overflow where the factor product is -1
+ac[2, 3::1013] = rng.integers(-128, 128, size=ac[2, 3::1013].shape)   # full-range tokens: the general form
+want_done, want_ovf, cur = np.zeros((K, B), np.uint8), np.zeros(B, np.uint8), st.copy()
+for k in range(K):
+    cur, want_done[k], o = CO.step_i8(cur, ac[k])
+    want_ovf |= o
+n_words = -(-B // 64)                             # what ops.step_stream accepts for this batch
+# guard words behind it: enough to hold a word per 16 games as well, so a kernel on the wrong unit size stays inside
+pbuf = torch.full((-(-B // 16) + 64,), CANARY, dtype=torch.int32, device=DEV)
+prog = pbuf[:n_words]
+t = ops.alloc_states(B, S, DEV); t.copy_(torch.from_numpy(st))
+ovf = torch.zeros(B, dtype=torch.uint8, device=DEV)
+status = torch.zeros(1, dtype=torch.int32, device=DEV)
+out, done = ops.step_stream(t, torch.from_numpy(ac).to(DEV), overflow=ovf, progress=prog, status=status)
+torch.cuda.synchronize()
+tail = pbuf[n_words:].cpu().numpy()
+assert (tail == CANARY).all(), f"progress written past its {n_words} words: {int((tail != CANARY).sum())} guard words changed"
+assert bool((prog == K).all()) and int(status[0]) == 0
+assert np.array_equal(t.cpu().numpy(), cur) and np.array_equal(done.cpu().numpy(), want_done)
+assert np.array_equal(ovf.cpu().numpy(), want_ovf)
+print("ROUNDS_OK")
+'''
+
+
+def test_stream_rounds_beyond_the_resident_batch_without_lanes(tmp_path):
+    """TG_STREAM_NO_LANES, S=4, a batch beyond ops.step_stream_capacity and no ready words: the rounds fallback.  progress
+    is sized as ops.step_stream accepts (one word per 64 games) with guard words behind it; state, the (K, B) done and
+    overflow against the C oracle.  (The fallback once took the 16-game kernel under this switch and wrote progress
+    for four times as many units.)"""
+    _run(ROUNDS_SCRIPT, tmp_path, "ROUNDS_OK", {"TG_STREAM_NO_LANES": "1"})
+
+
 def test_product_library_has_no_switches():
     """The product library reads no environment variable and does not export the A/B-only entry."""
     import ctypes as C

@@ -7,6 +7,7 @@ import torch
 
 import mat_mul_amd
 from mat_mul_amd import TensorGameEnv, SyntheticDemos, functional as F, ops
+from guarded_buffers import check_flat, check_states, guarded, guarded_states
 from oracle import tensor_game as O
 
 pytestmark = pytest.mark.gpu
@@ -176,7 +177,8 @@ def test_env_track_nnz_matches_the_plain_env():
 def test_env_picks_the_tracked_step_by_batch_size(S, below, above):
     """TensorGameEnv(track_nnz=None) takes tg_step_tracked_i8 from the measured crossovers on (S=16:
     12 000 games, S=25: 2 048) when dim_t == 1 -- both sides of each crossover roll a demonstration out to zero with the
-    same states, done flags and counts as an env forced the other way; dim_t > 1 and S=4 never track."""
+    same states, done flags and counts as an env forced the other way; dim_t > 1 and S=4 never track.
+    test_gpu_full_size_oracle.py::test_step_tracked_at_full_size_matches_oracle checks the tracked step at the crossover against the oracle."""
     R = 6
     for B in (below, above):
         auto = TensorGameEnv(B, S, DEV)
@@ -725,7 +727,8 @@ def test_basis(S):
                                    (4, 1 << 21, 4)])                   # S=4 beyond 96 MiB: non-temporal state loads
 def test_full_size_generate_replay_terminate(S, B, R):
     """cfg2/cfg3/cfg4/cfg5-per-GPU: generator -> replay the demo's own actions -> every game reaches
-    zero exactly at the last step (generator, step, step_many and done agree)."""
+    zero exactly at the last step (generator, step, step_many and done agree).
+    test_gpu_full_size_oracle.py checks these launch sizes against the oracle on adversarial states."""
     demos = SyntheticDemos(R, B, 1, S, DEV, seed=S)
     assert not bool(demos.overflow.any())
     rev = demos.action_seq.flip(1).contiguous()
@@ -761,7 +764,8 @@ def test_launch_shapes_beyond_the_caches_replay_to_zero(S, B, R):
     on, the S=4 token wait from 384 MiB) had their arithmetic variants forced against the oracle at small batches, but the
     launches themselves ran at full size only under bench.py's self-check.  Here: generate, replay the demonstration's own
     actions in reverse with the plain step (and with the tracked one the env takes by itself) -- every game must be all
-    zero exactly at the last step, twice (both sweep directions), and step_many must agree."""
+    zero exactly at the last step, twice (both sweep directions), and step_many must agree.
+    test_gpu_full_size_oracle.py (step_* entries) checks these footprints against the oracle."""
     demos = SyntheticDemos(R, B, 1, S, DEV, seed=S + 1)
     rev = demos.action_seq.flip(1).contiguous()
     for track in (False, None):
@@ -1079,31 +1083,8 @@ def test_take_action_batched_greedy_step():
 def test_no_out_of_bounds_writes():
     """Guard bytes before/after every output buffer and in the padding between games must survive every
     entry point, for aligned, padded and packed layouts."""
-    GUARD, CANARY = 256, 0x5A
     rng = np.random.default_rng(99)
-
-    def guarded_states(B, S, stride):
-        n = S ** 3
-        buf = torch.full((GUARD + B * stride + GUARD,), CANARY, dtype=torch.uint8, device=DEV).view(torch.int8)
-        view = buf[GUARD:GUARD + B * stride].view(B, stride)[:, :n].unflatten(1, (S, S, S))
-        return buf, view
-
-    def check(buf, B, S, stride, what):
-        raw = host(buf.view(torch.uint8))
-        n = S ** 3
-        assert (raw[:GUARD] == CANARY).all() and (raw[GUARD + B * stride:] == CANARY).all(), what
-        body = raw[GUARD:GUARD + B * stride].reshape(B, stride)
-        assert (body[:, n:] == CANARY).all(), what + " (padding between games)"
-
-    def guarded(shape, dtype):
-        numel = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        buf = torch.full((GUARD + numel + GUARD,), CANARY, dtype=torch.uint8, device=DEV)
-        return buf, buf[GUARD:GUARD + numel].view(dtype).view(shape)
-
-    def check_flat(buf, what):
-        raw = host(buf)
-        assert (raw[:GUARD] == CANARY).all() and (raw[-GUARD:] == CANARY).all(), what
-
+    check = check_states
     for S in (4, 9, 16, 25, 6):
         n = S ** 3
         for stride in {n, -(-n // 16) * 16, -(-n // 16) * 16 + 32}:
@@ -1488,7 +1469,8 @@ def test_step_stream_waits_for_ready_words_and_times_out():
 
 def test_step_stream_beyond_the_resident_batch_runs_in_rounds_without_ready_words():
     """S=4 with more games than the device keeps resident: refused with ready words (a producer waiting for the whole batch
-    would stall), accepted without -- units of 64 games run in rounds; BASELINE config 4 whole on one GPU."""
+    would stall), accepted without -- units of 64 games run in rounds; BASELINE config 4 whole on one GPU.
+    test_gpu_full_size_oracle.py::test_step_stream_in_rounds_matches_oracle checks the rounds against the oracle."""
     B, K = 1 << 20, 3
     with pytest.raises(mat_mul_amd.TensorGameError, match="resident"):
         ops.step_stream_layout(B, 4, DEV)
@@ -1513,7 +1495,8 @@ def test_step_stream_capacity_and_ready_words_beyond_it(S):
     """at S=16 / 25 tg_step_stream_layout accepts any B and the units run in rounds beyond the resident batch --
     with ready words a producer that waits for the whole batch would never see the later rounds start.  The capacity is
     now exported (from the occupancy of the stepper's kernel on this device); ready words beyond it are refused, the same
-    batch without them runs in rounds and equals K single steps."""
+    batch without them runs in rounds and equals K single steps.
+    test_gpu_full_size_oracle.py::test_step_stream_in_rounds_matches_oracle checks launches beyond the capacity against the oracle."""
     cap = ops.step_stream_capacity(S, DEV)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     assert cap == cus * {16: 32, 25: 16}[S]
@@ -1808,7 +1791,8 @@ def test_change_basis_matrix_core_kernel_and_its_fallbacks(S, B):
 def test_streamed_outputs_match_the_cached_form(S, B, k):
     """Outputs of >= 128 MiB (expand's children -- S = 4 writes them with non-temporal stores from that size on --,
     copies, resets, model-input frames): the same bytes as a small slice of the batch gives, and (size-independent
-    property) child c of a parent == one step of the parent with action c."""
+    property) child c of a parent == one step of the parent with action c.
+    test_gpu_full_size_oracle.py::test_expand_streamed_children_match_oracle checks the streamed launch in full against the oracle."""
     tok, tgt = ops.gen_demos(B, S, k, DEV, seed=S + 1)
     tok[1, k - 1, :S] = 1                                      # a null action
     kids, done, chg = ops.expand(tgt, tok)
