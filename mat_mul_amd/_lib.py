@@ -57,6 +57,11 @@ SIGNATURES = {
     "tg_rank_i32": [_p, _p, _i64, _i, _i64, _p],
 }
 
+# name -> argtypes; every symbol include/tensor_game_demos.h declares
+DEMO_SIGNATURES = {
+    "tg_demo_items": [_p, _p, _i64, _i, _i, _i64, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p],
+}
+
 
 def _preload_torch_hip_runtime() -> None:
     """PyTorch-ROCm ships its own libamdhip64 (SONAME libamdhip64.so.7).  Two HIP runtimes in
@@ -84,7 +89,7 @@ def _load() -> C.CDLL:
             "mat_mul_amd has no CPU fallback."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

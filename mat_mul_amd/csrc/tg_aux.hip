@@ -7,42 +7,11 @@
 
 #include "../../include/tensor_game.h"
 #include "tg_device.h"
+#include "tg_emit.h"
 
 int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
 
 namespace tg {
-
-// 16 output bytes from PER = 16 / sizeof(OutT) int8 values (small integers: exact in float32, float16 and bfloat16
-// alike).  Built in registers, word by word: an `OutT v[PER]` array + memcpy made hipcc stage the values through LDS,
-// and the f16 / bf16 kernels took 33 us where the f32 kernel took 13.5 (S=4, B=65 536, T=4).
-template <typename OutT>
-__device__ __forceinline__ uint4 emit_pack(const int (&x)[16 / sizeof(OutT)]) {
-  if constexpr (sizeof(OutT) == 4) {
-    return uint4{__float_as_uint(static_cast<float>(x[0])), __float_as_uint(static_cast<float>(x[1])),
-                 __float_as_uint(static_cast<float>(x[2])), __float_as_uint(static_cast<float>(x[3]))};
-  } else {
-    uint32_t w[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const float lo = static_cast<float>(x[2 * d]), hi = static_cast<float>(x[2 * d + 1]);
-      if constexpr (std::is_same<OutT, __half>::value) {
-        typedef __fp16 h2_t __attribute__((ext_vector_type(2)));
-        const h2_t h = __builtin_amdgcn_cvt_pkrtz(lo, hi);  // |x| <= 128: exact whatever the rounding
-        __builtin_memcpy(&w[d], &h, 4);
-      } else {  // bfloat16 = the upper half of the float32 (|x| <= 128 has at most 8 significant bits: exact)
-        w[d] = __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
-      }
-    }
-    return uint4{w[0], w[1], w[2], w[3]};
-  }
-}
-// element t of a packed group (the last, partial group of the output)
-template <typename OutT>
-__device__ __forceinline__ void emit_store_one(OutT* out, const uint4& o, int t) {
-  const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-  if constexpr (sizeof(OutT) == 4) *reinterpret_cast<uint32_t*>(out) = w[t];
-  else *reinterpret_cast<uint16_t*>(out) = static_cast<uint16_t>(w[t >> 1] >> (16 * (t & 1)));
-}
 
 // ---------------------------------------------------------------------------------------------
 // N1: int8 history ring -> float model input.  One thread per 16 input bytes (64 or 32 output

@@ -7,7 +7,7 @@ packed int8 arrays in HBM instead of two pickles per demo on disk.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Iterator, Optional, Tuple
 
 import torch
 
@@ -96,3 +96,48 @@ class SyntheticDemos:
         scalar = torch.full((self.n_demos, 1), float(R - idx_action), device=self.device)
         reward = torch.full((self.n_demos, 1), float(-(idx_action + 1)), device=self.device)
         return state, scalar, self.action_seq[:, idx_action], reward
+
+    def items(self, idx: Optional[torch.Tensor] = None, *, demo_idx: Optional[torch.Tensor] = None,
+              action_idx: Optional[torch.Tensor] = None, dtype=torch.float32, dim_t: Optional[int] = None):
+        """The ``__getitem__`` tuples (datasets.py:78-122) of a batch of items, each with its own demo and action index,
+        in one launch (``ops.demo_items``): ``idx`` holds flat reference indices (demo * max_actions + action index),
+        or ``demo_idx`` and ``action_idx`` the two halves.  Returns (state (N,dim_t,S,S,S) of ``dtype``, scalar fp32
+        (N,1), action int8 (N,3S), reward fp32 (N,1)).  An index outside the set gives an all-zero item."""
+        if idx is None:
+            if demo_idx is None or action_idx is None:
+                raise TensorGameError("items", -1, "pass idx, or both demo_idx and action_idx")
+            idx = torch.as_tensor(demo_idx, device=self.device).to(torch.int64) * self.max_actions + \
+                torch.as_tensor(action_idx, device=self.device).to(torch.int64)
+        elif demo_idx is not None or action_idx is not None:
+            raise TensorGameError("items", -1, "pass idx or demo_idx / action_idx, not both")
+        idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1)
+        return ops.demo_items(self.action_seq, self.target_tensor, idx, self.dim_t if dim_t is None else dim_t,
+                              dtype=dtype, shift=self.shift)
+
+    def __getitem__(self, i: int):
+        """One item, shaped as the reference returns it: (state (dim_t,S,S,S) fp32, scalar (1,), action (3S,),
+        reward (1,)).  For batches use ``items`` or ``batches``."""
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(f"item {i} outside [0, {len(self)})")
+        state, scalar, action, reward = self.items(torch.tensor([i], device=self.device))
+        return state[0], scalar[0], action[0], reward[0]
+
+    def batches(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None,
+                indices: Optional[torch.Tensor] = None, drop_last: bool = False,
+                dtype=torch.float32) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """One epoch of ``items`` batches: what ``DataLoader(random_split(dataset)[i], batch_size, shuffle=True)``
+        yields (training.py:234-246), gathered on the GPU.  ``indices`` (flat item indices) selects the subset, as
+        ``random_split`` does; the permutation is drawn on the device (``generator``: a generator of that device), and
+        each batch is one ``ops.demo_items`` call.  No host sync."""
+        if batch_size < 1:
+            raise TensorGameError("batches", -1, "batch_size must be >= 1")
+        if indices is None:
+            indices = torch.arange(len(self), device=self.device)
+        indices = torch.as_tensor(indices, device=self.device).to(torch.int64).reshape(-1)
+        n = indices.shape[0]
+        if shuffle:
+            indices = indices[torch.randperm(n, generator=generator, device=self.device)]
+        stop = n - n % batch_size if drop_last else n
+        for lo in range(0, stop, batch_size):
+            yield self.items(indices[lo:lo + batch_size], dtype=dtype)

@@ -19,7 +19,7 @@ from ._lib import TG_MAX_ACTIONS, TG_MAX_S, TG_MAX_VALUES, TensorGameError, call
 __all__ = [
     "step", "step_tracked", "copy_states", "prepare_step", "step_many", "step_stream", "step_stream_layout", "step_stream_capacity", "expand", "done", "reset_matmul", "reset_broadcast", "gen_from_factors",
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
-    "alloc_states", "alloc_ring", "emit_frames", "step_emit", "state_hash", "slice_rank", "alloc_seen_table", "seen",
+    "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
 ]
 
 
@@ -518,6 +518,53 @@ def step_emit(ring, head_slot: int, actions, t_step: float = 0.0, dtype=torch.fl
         call("tg_step_emit", _ptr(ring), _ptr(actions), _ptr(out), _ptr(scalars), _ptr(done), _ptr(overflow), codes[dtype],
              B, S, T, head, C.c_float(float(t_step)), fs, gs, int(shift), _stream(dev))
     return out, scalars, done, (head + 1) % T
+
+
+_ITEM_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.int8: 3}
+
+
+def demo_items(tokens, targets, idx, T: int, dtype=torch.float32, out=None, scalars=None, actions=None, rewards=None,
+               overflow=None, status=None, shift: int = 1):
+    """Items of a demo set at flat indices ``idx`` (int64 (N,), item n = demo idx // R at action index idx % R), the
+    ``__getitem__`` of SyntheticDemoDataset (datasets.py:78-122) for a whole shuffled batch in one launch (no host sync).
+    tokens int8 (n_demos,R,3S); targets int8 (n_demos,S,S,S), game stride >= S^3 (``alloc_states`` padding accepted).
+    Returns (frames (N,T,S,S,S) of ``dtype`` (float32, float16, bfloat16 or int8), scalars float32 (N,1) = R - k,
+    actions int8 (N,3S), rewards float32 (N,1) = -(k+1)).  ``overflow`` uint8 (N,) is set where an exact frame value
+    left int8; ``status`` uint32 (1,) gets bit 0 for an index outside [0, n_demos*R) (that item is all zero)."""
+    B, S, stride = _state_layout(targets, "targets")
+    dev = targets.device
+    _need_gpu(tokens, "tokens")
+    if tokens.dim() != 3 or tokens.shape[0] != B:
+        raise TensorGameError("demo_items", -1, f"tokens must be int8 (n_demos,R,3S) with n_demos={B}, got {tuple(tokens.shape)}")
+    R = tokens.shape[1]
+    tokens = _tokens(tokens, (B, R), S, dev, "tokens")
+    _need_gpu(idx, "idx")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
+        raise TensorGameError("demo_items", -1, f"idx must be int64 (N,) on {dev}, got {idx.dtype} {tuple(idx.shape)} on {idx.device}")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    N = idx.shape[0]
+    if dtype not in _ITEM_DTYPES:
+        raise TensorGameError("demo_items", -1, "dtype must be float32, float16, bfloat16 or int8")
+    if out is None:
+        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
+    if out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
+        raise TensorGameError("demo_items", -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
+    if scalars is None:
+        scalars = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    if actions is None:
+        actions = torch.empty((N, 3 * S), dtype=torch.int8, device=dev)
+    if rewards is None:
+        rewards = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    scalars = _flag(scalars, (N, 1), torch.float32, dev, "scalars")
+    actions = _flag(actions, (N, 3 * S), torch.int8, dev, "actions")
+    rewards = _flag(rewards, (N, 1), torch.float32, dev, "rewards")
+    overflow = _flag(overflow, (N,), torch.uint8, dev, "overflow")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    with torch.cuda.device(dev):
+        call("tg_demo_items", _ptr(tokens), _ptr(targets), B, R, S, stride, _ptr(idx), N, int(T), _ITEM_DTYPES[dtype],
+             _ptr(out), _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), int(shift),
+             _stream(dev))
+    return out, scalars, actions, rewards
 
 
 def state_hash(state) -> torch.Tensor:
