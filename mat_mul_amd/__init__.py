@@ -14,15 +14,16 @@ import importlib
 
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
-           "shard_range"]
+           "shard_range", "SearchForest", "search"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
     "TranspositionTable": "tree",
     "TensorGameError": "_lib",
     "shard_range": "sharding",
+    "SearchForest": "search",
 }
 
 

@@ -63,6 +63,32 @@ DEMO_SIGNATURES = {
 }
 
 
+# name -> argtypes; every symbol include/tensor_game_search.h declares (the forest descriptor goes by pointer)
+SEARCH_SIGNATURES = {
+    "tg_search_reset": [_p, _p, _i, _p],
+    "tg_search_select": [_p, _p, _i, _p, _p],
+    "tg_search_commit": [_p, _p, _p, _p, _p, _p],
+    "tg_search_advance": [_p, _i, _p],
+    "tg_search_policy": [_p, _p, _i, _i, _p],
+}
+
+# flags of tg_search_select / tg_search_commit (include/tensor_game_search.h)
+TG_SEARCH_EXPAND, TG_SEARCH_TERMINAL, TG_SEARCH_HORIZON, TG_SEARCH_RETRY, TG_SEARCH_PENDING = 1, 2, 4, 8, 128
+TG_SEARCH_MAX_K, TG_SEARCH_MAX_T, TG_SEARCH_MAX_DEPTH, TG_SEARCH_MAX_ACTIONS = 64, 16, 4096, 4096
+
+
+class SearchForestDesc(C.Structure):
+    """``tg_search_forest`` of include/tensor_game_search.h (sizes, then device pointers)."""
+
+    _fields_ = [("B", C.c_int64), ("S", C.c_int32), ("T", C.c_int32), ("k", C.c_int32), ("M", C.c_int32),
+                ("index_capacity", C.c_int64), ("max_actions", C.c_int32), ("horizon", C.c_int32),
+                ("max_depth", C.c_int32), ("shift", C.c_int32)] + [(name, C.c_void_p) for name in (
+                    "node_key", "node_frames", "node_nchild", "child_tokens", "child_key", "child_n", "child_q",
+                    "child_prior", "index_key", "index_node", "node_count", "root_frames", "root_key", "move", "done",
+                    "sims_left", "status", "overflow", "leaf_frames", "leaf_key", "path_node", "path_slot", "depth",
+                    "flags", "attempt", "traj_frames", "traj_node", "traj_choice")]
+
+
 def _preload_torch_hip_runtime() -> None:
     """PyTorch-ROCm ships its own libamdhip64 (SONAME libamdhip64.so.7).  Two HIP runtimes in
     one process do not share devices or streams (the second one reports "no ROCm-capable
@@ -89,7 +115,7 @@ def _load() -> C.CDLL:
             "mat_mul_amd has no CPU fallback."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -20,6 +20,7 @@ __all__ = [
     "step", "step_tracked", "copy_states", "prepare_step", "step_many", "step_stream", "step_stream_layout", "step_stream_capacity", "expand", "done", "reset_matmul", "reset_broadcast", "gen_from_factors",
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
+    "search_reset", "search_select", "search_commit", "search_advance", "search_policy",
 ]
 
 
@@ -637,3 +638,64 @@ def debug_handovers(device="cuda:0") -> int:
     with torch.cuda.device(torch.device(device)):
         call("tg_debug_handovers", C.byref(out))
     return int(out.value)
+
+
+# ---- batched MCTS (include/tensor_game_search.h) ---------------------------------------------------------------
+
+_SEARCH_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _search_call(name: str, forest, *args) -> None:
+    with torch.cuda.device(forest.device):
+        call(name, C.byref(forest.desc), *args, _stream(forest.device))
+
+
+def search_reset(forest, states, n_sim: int) -> None:
+    """Load the roots of a ``search.SearchForest`` (int8 (B,T,S,S,S), frame 0 = head) and empty its trees."""
+    _need_gpu(states, "states")
+    want = (forest.B, forest.T, forest.S, forest.S, forest.S)
+    if states.dtype != torch.int8 or tuple(states.shape) != want or states.device != forest.device:
+        raise TensorGameError("search_reset", -1, f"states must be int8 {want} on {forest.device}, got {states.dtype} "
+                              f"{tuple(states.shape)} on {states.device}")
+    states = states.contiguous()
+    _search_call("tg_search_reset", forest, _ptr(states), int(n_sim))
+
+
+def search_select(forest, model_in=None, scalars=None) -> None:
+    """One descent per active game (tg_search_select); ``model_in`` (B,T,S,S,S) float32/float16/bfloat16 and ``scalars``
+    float32 (B,1) receive the leaf's model input when given."""
+    code = 0
+    if model_in is not None:
+        want = (forest.B, forest.T, forest.S, forest.S, forest.S)
+        if model_in.dtype not in _SEARCH_DTYPES or tuple(model_in.shape) != want or not model_in.is_contiguous() \
+                or model_in.device != forest.device:
+            raise TensorGameError("search_select", -1, f"model_in must be contiguous float32/float16/bfloat16 {want}")
+        code = _SEARCH_DTYPES[model_in.dtype]
+    scalars = _flag(scalars, (forest.B, 1), torch.float32, forest.device, "scalars")
+    _search_call("tg_search_select", forest, _ptr(model_in), code, _ptr(scalars))
+
+
+def search_commit(forest, tokens, leaf_q, prior=None, mask=None) -> None:
+    """Expand and back up every selected game (tg_search_commit): tokens int8 (B,k,3S), leaf_q float32 (B,), prior
+    float32 (B,k) or None, mask uint8 (B,) or None."""
+    dev = forest.device
+    tokens = _tokens(tokens, (forest.B, forest.k), forest.S, dev, "tokens")
+    leaf_q = _flag(leaf_q, (forest.B,), torch.float32, dev, "leaf_q")
+    prior = _flag(prior, (forest.B, forest.k), torch.float32, dev, "prior")
+    mask = _flag(mask, (forest.B,), torch.uint8, dev, "mask")
+    _search_call("tg_search_commit", forest, _ptr(tokens), _ptr(leaf_q), _ptr(prior), _ptr(mask))
+
+
+def search_advance(forest, n_sim: int) -> None:
+    """End the move of every game that is not done (tg_search_advance)."""
+    _search_call("tg_search_advance", forest, int(n_sim))
+
+
+def search_policy(forest, n_logits: int, n_bar: int, out=None) -> torch.Tensor:
+    """Improved policy float32 (B, max_actions, 3S, n_logits) of every move played (tg_search_policy)."""
+    shape = (forest.B, forest.max_actions, 3 * forest.S, n_logits)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=forest.device)
+    out = _flag(out, shape, torch.float32, forest.device, "out")
+    _search_call("tg_search_policy", forest, _ptr(out), int(n_logits), int(n_bar))
+    return out
