@@ -14,9 +14,9 @@ import importlib
 
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
-           "shard_range", "SearchForest", "search"]
+           "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -24,6 +24,8 @@ _ATTRS = {
     "TensorGameError": "_lib",
     "shard_range": "sharding",
     "SearchForest": "search",
+    "GameBuffer": "replay",
+    "TensorGameData": "replay",
 }
 
 

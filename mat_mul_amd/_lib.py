@@ -89,6 +89,25 @@ class SearchForestDesc(C.Structure):
                     "flags", "attempt", "traj_frames", "traj_node", "traj_choice")]
 
 
+# name -> argtypes; every symbol include/tensor_game_replay.h declares (buffer descriptors go by pointer)
+REPLAY_SIGNATURES = {
+    "tg_replay_add": [_p, _p, _p, _i, _p, _p, _i64, _i, _p, _p],
+    "tg_replay_items": [_p, _p, _i64, _i, _i, _i64, _i, _p, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _p, _p, _p, _p, _p,
+                        _p, _p],
+}
+
+# limits and row kinds of include/tensor_game_replay.h
+TG_REPLAY_MAX_CAPACITY, TG_REPLAY_MAX_ACTIONS, TG_REPLAY_MAX_T, TG_REPLAY_MAX_LOGITS = 65536, 4096, 16, 128
+TG_REPLAY_SYNTH, TG_REPLAY_PLAYED, TG_REPLAY_BEST = 0, 1, 2
+
+
+class ReplayBufferDesc(C.Structure):
+    """``tg_replay_buffer`` of include/tensor_game_replay.h (sizes, then device pointers)."""
+
+    _fields_ = [("C", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("S", C.c_int32)] + [
+        (name, C.c_void_p) for name in ("frames", "tokens", "rewards", "length", "offset", "ring")]
+
+
 def _preload_torch_hip_runtime() -> None:
     """PyTorch-ROCm ships its own libamdhip64 (SONAME libamdhip64.so.7).  Two HIP runtimes in
     one process do not share devices or streams (the second one reports "no ROCm-capable
@@ -115,7 +134,7 @@ def _load() -> C.CDLL:
             "mat_mul_amd has no CPU fallback."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -1,0 +1,384 @@
+// Replay buffers of played games and mixed training batches (include/tensor_game_replay.h).  gfx950 only; part of
+// libtensorgame.so.
+//
+// tg_replay_add: three launches, no host sync.
+//   - replay_plan_kernel (one workgroup of 1024): counts the storable games (select 0) or finds the best one (select 1),
+//     gives every surviving game its slot -- the survivor of rank r goes to (next + r) mod C, so no two games share a
+//     slot -- writes its length, parks the game index in offset[slot] and the survivor count in offset[C] (offset is
+//     rebuilt by the scan anyway), and advances the ring words;
+//   - replay_copy_kernel (one workgroup per possible survivor): copies the game's frames (16-byte loads and stores when
+//     both sides allow), takes the argmax token of every (move, step) of its policy and copies its rewards;
+//   - replay_scan_kernel (one workgroup of 1024): offset = exclusive prefix sums of length over the C slots.
+// tg_replay_items: the three item kernels of tg_items.h with the MixedRows policy -- a row resolves through the epoch
+// table (or directly) to a synthetic item, which takes the tg_demo_items path unchanged, or to a stored move, found by a
+// binary search over offset and written as a plain frame copy.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/tensor_game_demos.h"
+#include "../../include/tensor_game_replay.h"
+#include "tg_items.h"
+
+namespace tg {
+
+// ---- rows of a mixed batch ------------------------------------------------------------------------------------------
+struct BufView {        // what a gather reads of one buffer; C == 0: the buffer is absent (holds nothing)
+  const int8_t* frames;
+  const int8_t* tokens;
+  const float* rewards;
+  const int64_t* offset;
+  int32_t C, L;
+};
+
+struct MixArgs {
+  BufView buf[2];       // played, best
+  const uint8_t* kind;  // epoch table [len_data], or NULL: every row is of direct_kind at source index idx[n]
+  const int64_t* src;
+  int64_t len_data;
+  int direct_kind;
+};
+
+struct MixedRows {
+  static constexpr bool kMixed = true;
+  MixArgs x;
+
+  // the kind (3: a bad dataset index) and the source index of row n
+  __device__ __forceinline__ int lookup(const ItemArgs& a, int64_t n, int64_t& s) const {
+    const int64_t i = a.idx[n];
+    if (!x.kind) {
+      s = i;
+      return x.direct_kind;
+    }
+    const bool ok = i >= 0 && i < x.len_data;
+    s = ok ? x.src[i] : -1;
+    return ok ? x.kind[i] : 3;
+  }
+
+  // a synthetic row (valid or not); a stored move or a bad row is an invalid synthetic item here
+  __device__ __forceinline__ Item item(const ItemArgs& a, int64_t n) const {
+    int64_t s;
+    const int k = lookup(a, n, s);
+    Item it;
+    it.valid = k == TG_REPLAY_SYNTH && s >= 0 && s < a.n_demos * a.R;
+    it.d = it.valid ? s / a.R : 0;
+    it.k = it.valid ? static_cast<int>(s - it.d * a.R) : 0;
+    return it;
+  }
+
+  // row n is move m of slot `slot` of buffer b: the slot with offset[slot] <= s < offset[slot+1] (empty slots have
+  // offset[slot] == offset[slot+1] and are never found); false for anything else
+  __device__ __forceinline__ bool stored(const ItemArgs& a, int64_t n, BufView& b, int& slot, int& m) const {
+    int64_t s;
+    const int k = lookup(a, n, s);
+    if (k != TG_REPLAY_PLAYED && k != TG_REPLAY_BEST) return false;
+    b = k == TG_REPLAY_PLAYED ? x.buf[0] : x.buf[1];
+    if (b.C <= 0 || s < 0 || s >= b.offset[b.C]) return false;
+    int lo = 0, hi = b.C - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (b.offset[mid + 1] > s) hi = mid;
+      else lo = mid + 1;
+    }
+    const int64_t mm = s - b.offset[lo];
+    slot = lo;
+    m = static_cast<int>(mm);
+    return mm >= 0 && mm < b.L;  // (holds for a consistent buffer; the guard keeps every read inside it)
+  }
+
+  // PlayedGamesDataset.__getitem__: the stored frames, scalar = m, the stored tokens and reward
+  template <typename OutT>
+  __device__ __forceinline__ bool write_stored(const ItemArgs& a, int64_t n, OutT* out, int t, int nthr) const {
+    BufView b;
+    int slot, m;
+    if (!stored(a, n, b, slot, m)) return false;
+    const int N3 = a.S * a.S * a.S, A3 = 3 * a.S;
+    const int64_t row = static_cast<int64_t>(slot) * b.L + m;
+    if (t == 0) {
+      if (a.scalars) a.scalars[n] = static_cast<float>(m);
+      if (a.rewards) a.rewards[n] = b.rewards[row];
+    }
+    if (a.actions)
+      for (int q = t; q < A3; q += nthr) a.actions[n * A3 + q] = b.tokens[row * A3 + q];
+    const int8_t* f = b.frames + row * a.T * N3;
+    write_frame(out, a.T * N3, t, nthr, [&](int e) { return static_cast<int>(f[e]); });
+    return true;
+  }
+};
+
+// ---- tg_replay_add --------------------------------------------------------------------------------------------------
+constexpr int kScanBlock = 1024;
+
+struct AddArgs {
+  tg_replay_buffer b;
+  const int8_t* states;  // (B,L,T,S^3)
+  const float* policy;   // (B,L,3S,n_logits)
+  const float* rewards;  // (B,L)
+  const int64_t* lengths;
+  int64_t B;
+  int n_logits, select;
+  uint32_t* status;
+};
+
+// exclusive prefix sum of v over the workgroup (kScanBlock threads); *total = the sum of all.  sh: kScanBlock int64.
+__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t* sh, int64_t* total) {
+  const int t = threadIdx.x;
+  __syncthreads();  // sh's previous readers are done
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < kScanBlock; d <<= 1) {
+    const int64_t add = t >= d ? sh[t - d] : 0;
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  *total = sh[kScanBlock - 1];
+  return sh[t] - v;
+}
+
+__device__ __forceinline__ bool storable(int64_t len, int L) { return len >= 1 && len <= L; }
+
+__global__ __launch_bounds__(kScanBlock) void replay_plan_kernel(AddArgs p) {
+  __shared__ int64_t sh[kScanBlock];
+  __shared__ float best_r[kScanBlock];
+  __shared__ int64_t best_g[kScanBlock];
+  const int t = threadIdx.x, L = p.b.L;
+  const int64_t C = p.b.C, next = p.b.ring[0];
+  int64_t cnt = 0;
+  int bad = 0;
+  float br = -1e6f;  // act_step: best_reward = -1e6, strict >
+  int64_t bg = -1;
+  for (int64_t g = t; g < p.B; g += kScanBlock) {
+    const int64_t len = p.lengths[g];
+    const bool ok = storable(len, L);
+    cnt += ok;
+    bad |= !ok;
+    if (ok) {
+      const float r = p.rewards[g * L + len - 1];
+      if (r > br) br = r, bg = g;  // within a thread g rises: the first maximum stays
+    }
+  }
+  if (__syncthreads_or(bad) && t == 0 && p.status) atomicOr(p.status, 1u);
+  int64_t V, n_surv;
+  if (p.select == 0) {
+    block_exclusive_scan(cnt, sh, &V);
+    n_surv = V < C ? V : C;
+    const int64_t r0 = V - n_surv;  // ranks below r0 would be overwritten within this call: never written
+    int64_t base = 0;
+    for (int64_t g0 = 0; g0 < p.B; g0 += kScanBlock) {
+      const int64_t g = g0 + t;
+      const int64_t len = g < p.B ? p.lengths[g] : 0;
+      const bool ok = storable(len, L);
+      int64_t chunk;
+      const int64_t r = base + block_exclusive_scan(ok, sh, &chunk);
+      if (ok && r >= r0) {
+        const int64_t slot = (next + r) % C;
+        p.b.offset[slot] = g;
+        p.b.length[slot] = static_cast<int32_t>(len);
+      }
+      base += chunk;
+    }
+  } else {
+    // (reward greater, or equal at a smaller game index) wins: the sequential first-strict-maximum
+    best_r[t] = br;
+    best_g[t] = bg;
+    __syncthreads();
+    for (int d = kScanBlock / 2; d > 0; d >>= 1) {
+      if (t < d) {
+        const float r2 = best_r[t + d];
+        const int64_t g2 = best_g[t + d];
+        if (g2 >= 0 && (best_g[t] < 0 || r2 > best_r[t] || (r2 == best_r[t] && g2 < best_g[t]))) {
+          best_r[t] = r2;
+          best_g[t] = g2;
+        }
+      }
+      __syncthreads();
+    }
+    const int64_t g = best_g[0];
+    V = n_surv = g >= 0 ? 1 : 0;
+    if (t == 0 && g >= 0) {
+      p.b.offset[next] = g;
+      p.b.length[next] = static_cast<int32_t>(p.lengths[g]);
+    }
+  }
+  __syncthreads();  // every thread has read ring[0]
+  if (t == 0) {
+    p.b.ring[0] = (next + V) % C;
+    p.b.ring[1] += V;
+    p.b.offset[C] = n_surv;
+  }
+}
+
+// torch.argmax over n floats: the first maximal index, a NaN counts as the maximum (the first NaN wins)
+__device__ __forceinline__ int argmax_first(const float* v, int n) {
+  float best = v[0];
+  int at = 0;
+  if (std::isnan(best)) return 0;
+  for (int q = 1; q < n; ++q) {
+    const float x = v[q];
+    if (std::isnan(x)) return q;
+    if (x > best) best = x, at = q;
+  }
+  return at;
+}
+
+__global__ __launch_bounds__(kBlock) void replay_copy_kernel(AddArgs p) {
+  const int64_t C = p.b.C, n_surv = p.b.offset[C], j = blockIdx.x;
+  if (j >= n_surv) return;
+  const int t = threadIdx.x, L = p.b.L, A3 = 3 * p.b.S;
+  const int64_t slot = ((p.b.ring[0] - n_surv + j) % C + C) % C;
+  const int64_t g = p.b.offset[slot];
+  const int len = p.b.length[slot];
+  const int64_t fb = static_cast<int64_t>(p.b.T) * p.b.S * p.b.S * p.b.S;  // bytes per state
+  const int8_t* sf = p.states + g * L * fb;
+  int8_t* df = p.b.frames + slot * L * fb;
+  const int64_t nbytes = len * fb;
+  int64_t done = 0;
+  if (((reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(df)) & 15) == 0) {
+    done = nbytes & ~static_cast<int64_t>(15);
+    for (int64_t c = t; c < done / 16; c += kBlock)
+      reinterpret_cast<uint4*>(df)[c] = reinterpret_cast<const uint4*>(sf)[c];
+  }
+  for (int64_t e = done + t; e < nbytes; e += kBlock) df[e] = sf[e];
+  const float* pol = p.policy + g * L * A3 * static_cast<int64_t>(p.n_logits);
+  int8_t* tk = p.b.tokens + slot * L * A3;
+  for (int q = t; q < len * A3; q += kBlock)
+    tk[q] = static_cast<int8_t>(argmax_first(pol + static_cast<int64_t>(q) * p.n_logits, p.n_logits));
+  for (int m = t; m < len; m += kBlock) p.b.rewards[slot * L + m] = p.rewards[g * L + m];
+}
+
+__global__ __launch_bounds__(kScanBlock) void replay_scan_kernel(tg_replay_buffer b) {
+  __shared__ int64_t sh[kScanBlock];
+  const int t = threadIdx.x, per = (b.C + kScanBlock - 1) / kScanBlock;
+  const int lo = min(t * per, b.C), hi = min(lo + per, b.C);
+  int64_t sum = 0;
+  for (int s = lo; s < hi; ++s) sum += b.length[s];
+  int64_t total;
+  int64_t run = block_exclusive_scan(sum, sh, &total);
+  for (int s = lo; s < hi; ++s) {
+    b.offset[s] = run;
+    run += b.length[s];
+  }
+  if (t == 0) b.offset[b.C] = total;
+}
+
+}  // namespace tg
+
+namespace {
+
+struct MixKernels {
+  static constexpr const char* kName = "tg_replay_items";
+  template <typename OutT, typename Acc>
+  static auto s4() { return tg::items_s4_kernel<tg::MixedRows, OutT, Acc, tg::MixArgs>; }
+  template <int S, typename OutT>
+  static auto mfma() { return tg::items_mfma_kernel<tg::MixedRows, S, OutT, tg::MixArgs>; }
+  template <typename OutT>
+  static auto exact() { return tg::items_exact_kernel<tg::MixedRows, OutT, tg::MixArgs>; }
+};
+
+int check_buffer(const char* fn, const char* what, const tg_replay_buffer* b) {
+  if (b->C < 1 || b->C > TG_REPLAY_MAX_CAPACITY)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: %s C=%d outside [1,%d]", fn, what, b->C, TG_REPLAY_MAX_CAPACITY);
+  if (b->L < 1 || b->L > TG_REPLAY_MAX_ACTIONS)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: %s L=%d outside [1,%d]", fn, what, b->L, TG_REPLAY_MAX_ACTIONS);
+  if (b->T < 1 || b->T > TG_REPLAY_MAX_T)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: %s T=%d outside [1,%d]", fn, what, b->T, TG_REPLAY_MAX_T);
+  if (b->S < 1 || b->S > TG_MAX_S)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: %s S=%d outside [1,%d]", fn, what, b->S, TG_MAX_S);
+  if (!b->frames || !b->tokens || !b->rewards || !b->length || !b->offset || !b->ring)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: null %s buffer array", fn, what);
+  if ((reinterpret_cast<uintptr_t>(b->rewards) | reinterpret_cast<uintptr_t>(b->length)) % 4 ||
+      (reinterpret_cast<uintptr_t>(b->offset) | reinterpret_cast<uintptr_t>(b->ring)) % 8)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: %s buffer arrays not aligned to their elements", fn, what);
+  return TG_OK;
+}
+
+}  // namespace
+
+extern "C" int tg_replay_add(const tg_replay_buffer* buf, const int8_t* states, const float* policy, int n_logits,
+                             const float* rewards, const int64_t* lengths, int64_t B, int select, uint32_t* status,
+                             tg_stream_t stream) {
+  const char* fn = "tg_replay_add";
+  if (!buf) return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer", fn);
+  if (int rc = check_buffer(fn, "the", buf)) return rc;
+  if (n_logits < 1 || n_logits > TG_REPLAY_MAX_LOGITS)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: n_logits=%d outside [1,%d]", fn, n_logits, TG_REPLAY_MAX_LOGITS);
+  if (select != 0 && select != 1) return tg_internal_fail(TG_ERR_INVALID, "%s: select=%d (0 all, 1 best)", fn, select);
+  if (B < 0 || B > INT32_MAX) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld out of range", fn, (long long)B);
+  if (B == 0) return TG_OK;
+  if (!states || !policy || !rewards || !lengths)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: null states, policy, rewards or lengths", fn);
+  if (reinterpret_cast<uintptr_t>(policy) % 4 || reinterpret_cast<uintptr_t>(rewards) % 4 ||
+      reinterpret_cast<uintptr_t>(lengths) % 8)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: policy, rewards or lengths not aligned to their elements", fn);
+  const tg::AddArgs p{*buf, states, policy, rewards, lengths, B, n_logits, select, status};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t copies = select ? 1 : (B < buf->C ? B : buf->C);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(tg::replay_plan_kernel, dim3(1), dim3(tg::kScanBlock), 0, st, p);
+  hipLaunchKernelGGL(tg::replay_copy_kernel, dim3(static_cast<unsigned>(copies)), dim3(tg::kBlock), 0, st, p);
+  hipLaunchKernelGGL(tg::replay_scan_kernel, dim3(1), dim3(tg::kScanBlock), 0, st, *buf);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return TG_OK;
+}
+
+extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int64_t n_demos, int R, int S,
+                               int64_t target_stride_bytes, int shift, const tg_replay_buffer* played,
+                               const tg_replay_buffer* best, const uint8_t* kind, const int64_t* src, int64_t len_data,
+                               int direct_kind, const int64_t* item_idx, int64_t N, int T, int out_dtype,
+                               void* frames_out, float* scalars_out, int8_t* actions_out, float* rewards_out,
+                               uint8_t* overflow, uint32_t* status, tg_stream_t stream) {
+  const char* fn = "tg_replay_items";
+  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
+  if (R < 1 || R > TG_DEMO_MAX_ACTIONS)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: R=%d outside [1,%d]", fn, R, TG_DEMO_MAX_ACTIONS);
+  if (T < 1 || T > TG_DEMO_MAX_T) return tg_internal_fail(TG_ERR_INVALID, "%s: T=%d outside [1,%d]", fn, T, TG_DEMO_MAX_T);
+  if (n_demos < 0 || n_demos > INT64_MAX / R)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: n_demos=%lld out of range", fn, (long long)n_demos);
+  const int64_t N3 = static_cast<int64_t>(S) * S * S;
+  if (target_stride_bytes < N3)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: target_stride_bytes=%lld < S^3=%lld", fn, (long long)target_stride_bytes,
+                            (long long)N3);
+  if (out_dtype < 0 || out_dtype > 3)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: out_dtype=%d (0 f32, 1 f16, 2 bf16, 3 int8)", fn, out_dtype);
+  const tg_replay_buffer* bufs[2] = {played, best};
+  const char* names[2] = {"played", "best"};
+  for (int q = 0; q < 2; ++q) {
+    if (!bufs[q]) continue;
+    if (int rc = check_buffer(fn, names[q], bufs[q])) return rc;
+    if (bufs[q]->S != S || bufs[q]->T != T)
+      return tg_internal_fail(TG_ERR_INVALID, "%s: %s buffer has S=%d T=%d, the items S=%d T=%d", fn, names[q],
+                              bufs[q]->S, bufs[q]->T, S, T);
+  }
+  if (kind) {
+    if (!src) return tg_internal_fail(TG_ERR_INVALID, "%s: null src with an epoch table", fn);
+    if (len_data < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: len_data=%lld", fn, (long long)len_data);
+  } else if (direct_kind < TG_REPLAY_SYNTH || direct_kind > TG_REPLAY_BEST) {
+    return tg_internal_fail(TG_ERR_INVALID, "%s: direct_kind=%d outside [0,2]", fn, direct_kind);
+  }
+  if (N < 0 || N > INT64_MAX / (T * N3)) return tg_internal_fail(TG_ERR_INVALID, "%s: N=%lld out of range", fn, (long long)N);
+  if (N == 0) return TG_OK;
+  if (!item_idx || !frames_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null item_idx or frames_out", fn);
+  if (n_demos > 0 && (!tokens || !targets)) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens or targets", fn);
+  const int esize = out_dtype == 3 ? 1 : out_dtype == 0 ? 4 : 2;
+  if (reinterpret_cast<uintptr_t>(frames_out) % esize)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_out not aligned to its %d-byte elements", fn, esize);
+  tg::MixArgs x{};
+  for (int q = 0; q < 2; ++q)
+    if (bufs[q]) x.buf[q] = tg::BufView{bufs[q]->frames, bufs[q]->tokens, bufs[q]->rewards, bufs[q]->offset,
+                                        bufs[q]->C, bufs[q]->L};
+  x.kind = kind;
+  x.src = src;
+  x.len_data = len_data;
+  x.direct_kind = direct_kind;
+  tg::ItemArgs a{tokens, targets, n_demos, target_stride_bytes, item_idx, N, frames_out, scalars_out, actions_out,
+                 rewards_out, overflow, status, R, S, T, shift, 0, 0};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (out_dtype) {
+    case 0: return dispatch_items<float, MixKernels>(a, st, x);
+    case 1: return dispatch_items<__half, MixKernels>(a, st, x);
+    case 2: return dispatch_items<__hip_bfloat16, MixKernels>(a, st, x);
+    default: return dispatch_items<int8_t, MixKernels>(a, st, x);
+  }
+}

@@ -20,7 +20,7 @@ __all__ = [
     "step", "step_tracked", "copy_states", "prepare_step", "step_many", "step_stream", "step_stream_layout", "step_stream_capacity", "expand", "done", "reset_matmul", "reset_broadcast", "gen_from_factors",
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
-    "search_reset", "search_select", "search_commit", "search_advance", "search_policy",
+    "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
 ]
 
 
@@ -699,3 +699,109 @@ def search_policy(forest, n_logits: int, n_bar: int, out=None) -> torch.Tensor:
     out = _flag(out, shape, torch.float32, forest.device, "out")
     _search_call("tg_search_policy", forest, _ptr(out), int(n_logits), int(n_bar))
     return out
+
+
+# ---- replay buffers and mixed batches (include/tensor_game_replay.h) ------------------------------------------------
+
+
+def replay_add(buf, states, policy, rewards, lengths, select: bool = False, status=None) -> None:
+    """Store finished games in a ``replay.GameBuffer`` (tg_replay_add): states int8 (B,L,T,S,S,S), policy float32
+    (B,L,3S,n_logits), rewards float32 (B,L), lengths int64 (B,) -- what ``search.actor_prediction`` returns (its int64
+    rewards converted).  ``select``: store only the first game with the greatest final reward (act_step's best game).
+    ``status`` uint32 (1,) gets bit 0 for a game with length 0 or > L (not stored)."""
+    dev = buf.device
+    for t, name in ((states, "states"), (policy, "policy"), (rewards, "rewards"), (lengths, "lengths")):
+        _need_gpu(t, name)
+    B = states.shape[0] if states.dim() == 6 else -1
+    want = (B, buf.L, buf.T, buf.S, buf.S, buf.S)
+    if states.dtype != torch.int8 or tuple(states.shape) != want or states.device != dev:
+        raise TensorGameError("replay_add", -1, f"states must be int8 (B,L,T,S,S,S) = {want[1:]} per game on {dev}, "
+                              f"got {states.dtype} {tuple(states.shape)} on {states.device}")
+    if policy.dtype != torch.float32 or policy.dim() != 4 or tuple(policy.shape[:3]) != (B, buf.L, 3 * buf.S) \
+            or policy.device != dev:
+        raise TensorGameError("replay_add", -1, f"policy must be float32 (B,L,3S,n_logits) with (B,L,3S) = "
+                              f"{(B, buf.L, 3 * buf.S)} on {dev}, got {policy.dtype} {tuple(policy.shape)}")
+    n_logits = policy.shape[3]
+    if not 1 <= n_logits <= _lib.TG_REPLAY_MAX_LOGITS:
+        raise TensorGameError("replay_add", -1, f"n_logits={n_logits} outside [1, {_lib.TG_REPLAY_MAX_LOGITS}]")
+    rewards = _flag(rewards, (B, buf.L), torch.float32, dev, "rewards")
+    lengths = _flag(lengths, (B,), torch.int64, dev, "lengths")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    states, policy = states.contiguous(), policy.contiguous()
+    with torch.cuda.device(dev):
+        call("tg_replay_add", C.byref(buf.desc), _ptr(states), _ptr(policy), int(n_logits), _ptr(rewards),
+             _ptr(lengths), B, 1 if select else 0, _ptr(status), _stream(dev))
+
+
+def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=None, best=None, kind=None, src=None,
+                 direct_kind: Optional[int] = None, dtype=torch.float32, out=None, scalars=None, actions=None,
+                 rewards=None, overflow=None, status=None, shift: int = 1):
+    """Items of a mixed dataset at dataset indices ``idx`` (int64 (N,)) in one launch (tg_replay_items), in the layout
+    of ``demo_items``: (frames (N,T,S,S,S) of ``dtype``, scalars float32 (N,1), actions int8 (N,3S), rewards float32
+    (N,1)).  Sources: the synthetic set ``tokens`` int8 (n_demos,R,3S) / ``targets`` int8 (n_demos,S,S,S) (both None:
+    no synthetic set), the ``played`` and ``best`` ``replay.GameBuffer`` (or None).  With the epoch table ``kind``
+    uint8 / ``src`` int64 (len_data,) row n is of kind[idx[n]] at source index src[idx[n]]; without it every row is of
+    ``direct_kind`` (0 synthetic, 1 played, 2 best) at source index idx[n].  Synthetic rows equal ``demo_items``;
+    played / best rows are PlayedGamesDataset.__getitem__ (scalar = the move index).  A bad row is all zero and sets
+    bit 0 of ``status`` uint32 (1,); ``overflow`` uint8 (N,) as ``demo_items``.  No host sync."""
+    dev = torch.device(device)
+    _need_gpu(idx, "idx")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
+        raise TensorGameError("replay_items", -1, f"idx must be int64 (N,) on {dev}, got {idx.dtype} "
+                              f"{tuple(idx.shape)} on {idx.device}")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    N = idx.shape[0]
+    if (tokens is None) != (targets is None):
+        raise TensorGameError("replay_items", -1, "pass both tokens and targets, or neither")
+    if tokens is not None:
+        n_demos, S_t, stride = _state_layout(targets, "targets")
+        if S_t != S or targets.device != dev:
+            raise TensorGameError("replay_items", -1, f"targets must be (n_demos,{S},{S},{S}) on {dev}")
+        _need_gpu(tokens, "tokens")
+        if tokens.dim() != 3 or tokens.shape[0] != n_demos:
+            raise TensorGameError("replay_items", -1, f"tokens must be int8 (n_demos,R,3S) with n_demos={n_demos}")
+        R = tokens.shape[1]
+        tokens = _tokens(tokens, (n_demos, R), S, dev, "tokens")
+    else:
+        n_demos, R, stride = 0, 1, S ** 3
+    for b, name in ((played, "played"), (best, "best")):
+        if b is not None and (b.S != S or b.T != T or b.device != dev):
+            raise TensorGameError("replay_items", -1, f"the {name} buffer holds S={b.S} T={b.T} on {b.device}, the "
+                                  f"items S={S} T={T} on {dev}")
+    if kind is not None:
+        if direct_kind is not None:
+            raise TensorGameError("replay_items", -1, "pass the epoch table (kind, src) or direct_kind, not both")
+        len_data = kind.shape[0] if kind.dim() == 1 else -1
+        kind = _flag(kind, (len_data,), torch.uint8, dev, "kind")
+        src = _flag(src, (len_data,), torch.int64, dev, "src")
+        if src is None:
+            raise TensorGameError("replay_items", -1, "an epoch table needs src")
+        code = 0
+    else:
+        if direct_kind not in (0, 1, 2):
+            raise TensorGameError("replay_items", -1, "without an epoch table direct_kind must be 0, 1 or 2")
+        len_data, code = 0, int(direct_kind)
+    if dtype not in _ITEM_DTYPES:
+        raise TensorGameError("replay_items", -1, "dtype must be float32, float16, bfloat16 or int8")
+    if out is None:
+        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
+    if out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
+        raise TensorGameError("replay_items", -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
+    if scalars is None:
+        scalars = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    if actions is None:
+        actions = torch.empty((N, 3 * S), dtype=torch.int8, device=dev)
+    if rewards is None:
+        rewards = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    scalars = _flag(scalars, (N, 1), torch.float32, dev, "scalars")
+    actions = _flag(actions, (N, 3 * S), torch.int8, dev, "actions")
+    rewards = _flag(rewards, (N, 1), torch.float32, dev, "rewards")
+    overflow = _flag(overflow, (N,), torch.uint8, dev, "overflow")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    pdesc = None if played is None else C.byref(played.desc)
+    bdesc = None if best is None else C.byref(best.desc)
+    with torch.cuda.device(dev):
+        call("tg_replay_items", _ptr(tokens), _ptr(targets), n_demos, R, S, stride, int(shift), pdesc, bdesc,
+             _ptr(kind), _ptr(src), len_data, code, _ptr(idx), N, int(T), _ITEM_DTYPES[dtype], _ptr(out),
+             _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), _stream(dev))
+    return out, scalars, actions, rewards
