@@ -14,9 +14,10 @@ import importlib
 
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
-           "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay"]
+           "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
+           "FusedAlphaTensor", "net"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -26,6 +27,7 @@ _ATTRS = {
     "SearchForest": "search",
     "GameBuffer": "replay",
     "TensorGameData": "replay",
+    "FusedAlphaTensor": "net",
 }
 
 

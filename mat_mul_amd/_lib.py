@@ -108,6 +108,30 @@ class ReplayBufferDesc(C.Structure):
         (name, C.c_void_p) for name in ("frames", "tokens", "rewards", "length", "offset", "ring")]
 
 
+# name -> argtypes; every symbol include/tensor_game_net.h declares (the configuration goes by pointer)
+NET_SIGNATURES = {
+    "tg_net_check": [_p],
+    "tg_net_weights_size": [_p, _p],
+    "tg_net_torso": [_p, _p, _p, _i, _p, _p, _i64, _p],
+    "tg_net_sample": [_p, _p, _p, _p, _i64, _i, _u64, _u64, _p, _p, _p, _p, _p],
+    "tg_net_logits": [_p, _p, _p, _p, _i64, _p, _p, _p, _p],
+}
+
+# the supported family of include/tensor_game_net.h
+NET_LIMITS = {"S": 5, "T": 8, "dim_s": 4, "c": 32, "torso_layers": 16, "torso_heads": 8, "torso_d": 64, "torso_ff": 128,
+              "W": 64, "heads": 8, "d": 64, "ff": 256, "blocks": 4, "n_steps": 16, "n_logits": 8, "n_hidden": 512,
+              "n_quantile": 16}
+TG_NET_MAX_SAMPLES = 64
+
+
+class NetConfig(C.Structure):
+    """``tg_net_config`` of include/tensor_game_net.h."""
+
+    _fields_ = [(name, C.c_int32) for name in ("S", "T", "dim_s", "c", "torso_layers", "torso_heads", "torso_d",
+                                                "torso_ff", "W", "heads", "d", "ff", "blocks", "n_steps", "n_logits",
+                                                "n_hidden", "n_quantile")]
+
+
 def _preload_torch_hip_runtime() -> None:
     """PyTorch-ROCm ships its own libamdhip64 (SONAME libamdhip64.so.7).  Two HIP runtimes in
     one process do not share devices or streams (the second one reports "no ROCm-capable
@@ -134,7 +158,8 @@ def _load() -> C.CDLL:
             "mat_mul_amd has no CPU fallback."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
+                           **NET_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -1,0 +1,760 @@
+// Fused eval-mode inference of the AlphaTensor network (include/tensor_game_net.h).  gfx950 only; part of
+// libtensorgame.so.
+//
+// Two kernels, both plain fp32 with every activation in LDS and the weights read from global memory (they are shared by
+// every workgroup and stay in L2):
+//   - net_torso_kernel: one workgroup per game.  The three S x S x c grids stay in LDS for all layers; each attention
+//     pair (m1, m2) is S independent sequences of 2S tokens, processed head by head (q, k, v of one head, scores,
+//     softmax, a @ v, then its slice of li1 added into the residual), then the MLP.
+//   - net_decode_kernel: one workgroup per (game, group of R samples of that game); with teacher forcing one row per
+//     game.  Decodes position by position with a per-(row, block) cache of the self-attention's normalised key/value
+//     input (W floats per position): with it, a head's scores are (Wk_h^T q_h) . y_j and its output is
+//     Wv_h (sum_j a_j y_j), so neither keys nor values are stored.  The cross-attention does the same over ln2(ee) of
+//     the game, normalised once per block at the start.  Under the causal mask this equals the reference's rerun of
+//     the whole prefix.  The sampling rule runs per row at the end of each step; the value head runs in the workgroup
+//     that holds sample 0, on the position-0 output.
+// Every matrix product goes through mm(): thread = (output column, group of RB rows), the weight element read once per
+// RB rows, the rows read from LDS as broadcasts.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cmath>
+
+#include "../../include/tensor_game.h"
+#include "../../include/tensor_game_net.h"
+#include "tg_device.h"
+
+int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
+
+namespace tg {
+namespace net {
+
+constexpr int NT = 256;  // threads per workgroup (both kernels)
+
+// ---- blob layout (the header's) ---------------------------------------------------------------------------------------
+struct Mha {
+  const float *ln1w, *ln1b, *ln2w, *ln2b, *q, *k, *v, *li1w, *li1b, *ln3w, *ln3b, *li2w, *li2b, *li3w, *li3b;
+};
+
+__host__ __device__ inline int64_t mha_size(int c1, int c2, int H, int d, int ff) {
+  const int64_t hd = static_cast<int64_t>(H) * d;
+  return 2LL * c1 + 2LL * c2 + c1 * hd + hd * c2 + c2 * hd + hd * c1 + c1 + 2LL * c1 + static_cast<int64_t>(c1) * ff +
+         ff + static_cast<int64_t>(ff) * c1 + c1;
+}
+
+__device__ inline Mha mha_at(const float* p, int c1, int c2, int H, int d, int ff) {
+  const int hd = H * d;
+  Mha m;
+  m.ln1w = p; p += c1;
+  m.ln1b = p; p += c1;
+  m.ln2w = p; p += c2;
+  m.ln2b = p; p += c2;
+  m.q = p; p += c1 * hd;
+  m.k = p; p += hd * c2;
+  m.v = p; p += c2 * hd;
+  m.li1w = p; p += hd * c1;
+  m.li1b = p; p += c1;
+  m.ln3w = p; p += c1;
+  m.ln3b = p; p += c1;
+  m.li2w = p; p += c1 * ff;
+  m.li2b = p; p += ff;
+  m.li3w = p; p += ff * c1;
+  m.li3b = p;
+  return m;
+}
+
+struct Off {                   // float offsets into the blob
+  int64_t t_li1[3], t_li2[3];  // torso input projections
+  int64_t t_layer0, t_layer;   // first torso layer, stride
+  int64_t emb, pos, blk0, blk; // policy
+  int64_t out, v[4];           // policy logits, value MLP
+  int64_t total;
+};
+
+inline Off offsets(const tg_net_config& c) {
+  Off o{};
+  int64_t p = 0;
+  const int64_t S2 = static_cast<int64_t>(c.S) * c.S, cin = static_cast<int64_t>(c.S) * c.T + 1;
+  for (int g = 0; g < 3; ++g) { o.t_li1[g] = p; p += c.dim_s * S2 + S2; }
+  for (int g = 0; g < 3; ++g) { o.t_li2[g] = p; p += cin * c.c + c.c; }
+  o.t_layer0 = p;
+  o.t_layer = mha_size(c.c, c.c, c.torso_heads, c.torso_d, c.torso_ff);
+  p += o.t_layer * c.torso_layers;
+  o.emb = p; p += static_cast<int64_t>(c.n_logits + 1) * c.W;
+  o.pos = p; p += static_cast<int64_t>(c.n_steps) * c.W;
+  o.blk0 = p;
+  o.blk = 2LL * c.W + mha_size(c.W, c.W, c.heads, c.d, c.ff) + 2LL * c.W + mha_size(c.W, c.c, c.heads, c.d, c.ff);
+  p += o.blk * c.blocks;
+  o.out = p; p += static_cast<int64_t>(c.W) * c.n_logits + c.n_logits;
+  const int64_t nh = c.n_hidden;
+  o.v[0] = p; p += c.W * nh + nh;
+  o.v[1] = p; p += nh * nh + nh;
+  o.v[2] = p; p += nh * nh + nh;
+  o.v[3] = p; p += nh * c.n_quantile + c.n_quantile;
+  o.total = p;
+  return o;
+}
+
+// ---- LDS plans (floats) -----------------------------------------------------------------------------------------------
+struct TorsoPlan {
+  int G, X, XN, YN, Y, QKV, SC, total;
+};
+
+__host__ __device__ inline TorsoPlan torso_plan(const tg_net_config& c) {
+  const int S2 = c.S * c.S, T2 = 2 * S2, cin = c.S * c.T + 1;
+  int qkv = 3 * T2 * c.torso_d;
+  if (T2 * c.torso_ff > qkv) qkv = T2 * c.torso_ff;
+  if (3 * S2 * cin > qkv) qkv = 3 * S2 * cin;
+  TorsoPlan p;
+  p.G = 0;
+  p.X = p.G + 3 * S2 * c.c;
+  p.XN = p.X + T2 * c.c;
+  p.YN = p.XN + T2 * c.c;
+  p.Y = p.YN + T2 * c.c;
+  p.QKV = p.Y + T2 * c.c;
+  p.SC = p.QKV + qkv;
+  p.total = p.SC + c.S * 4 * S2;
+  return p;
+}
+
+struct DecPlan {
+  int EEN, CACHE, X, XB, XN, Q, QK, SC, YB, O, H1, M, F, LG, Z0, V1, V2, MISC, total;
+  int wq, nsc;  // per-head strides of QK / YB and SC
+};
+
+__host__ __device__ inline DecPlan dec_plan(const tg_net_config& c, int R) {
+  const int J = 3 * c.S * c.S, hd = c.heads * c.d;
+  DecPlan p;
+  p.wq = c.W > c.c ? c.W : c.c;
+  p.nsc = J > c.n_steps ? J : c.n_steps;
+  p.EEN = 0;
+  p.CACHE = p.EEN + c.blocks * J * c.c;
+  p.X = p.CACHE + R * c.blocks * c.n_steps * c.W;
+  p.XB = p.X + R * c.W;
+  p.XN = p.XB + R * c.W;
+  p.Q = p.XN + R * c.W;
+  p.QK = p.Q + R * hd;
+  p.SC = p.QK + R * c.heads * p.wq;
+  p.YB = p.SC + R * c.heads * p.nsc;
+  p.O = p.YB + R * c.heads * p.wq;
+  p.H1 = p.O + R * hd;
+  p.M = p.H1 + R * c.W;
+  p.F = p.M + R * c.W;
+  p.LG = p.F + R * c.ff;
+  p.Z0 = p.LG + R * TG_NET_MAX_LOGITS;
+  p.V1 = p.Z0 + R * c.W;
+  p.V2 = p.V1 + c.n_hidden;
+  p.MISC = p.V2 + (c.n_hidden > c.n_quantile ? c.n_hidden : c.n_quantile);
+  p.total = p.MISC + 2 * R;  // pp[R], token[R]
+  return p;
+}
+
+// ---- building blocks (all threads of the workgroup call them; each ends without a barrier) -------------------------
+enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
+
+// Y[r][o] = res2[r][o] + (res[r][o] + act(sum_i X[r][i] * Wt[i][o] + bias[o])) for r < R, o < O.
+template <int RB>
+__device__ inline void mm_rb(const float* X, int ldx, int R, int I, const float* __restrict__ Wt, int ldw, int O,
+                             const float* __restrict__ bias, int act, const float* res, const float* res2, int ldr,
+                             float* Y, int ldy) {
+  const int groups = (R + RB - 1) / RB;
+  for (int it = threadIdx.x; it < O * groups; it += NT) {
+    const int o = it % O, r0 = (it / O) * RB;
+    const float* xr[RB];
+#pragma unroll
+    for (int u = 0; u < RB; ++u) xr[u] = X + (r0 + u < R ? r0 + u : R - 1) * ldx;
+    float acc[RB];
+#pragma unroll
+    for (int u = 0; u < RB; ++u) acc[u] = 0.f;
+    const float* wp = Wt + o;
+#pragma unroll 8
+    for (int i = 0; i < I; ++i) {
+      const float wv = wp[static_cast<int64_t>(i) * ldw];
+#pragma unroll
+      for (int u = 0; u < RB; ++u) acc[u] = fmaf(xr[u][i], wv, acc[u]);
+    }
+    const float b = bias ? bias[o] : 0.f;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+      const int r = r0 + u;
+      if (r >= R) break;
+      float v = acc[u] + b;
+      if (act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+      else if (act == ACT_RELU) v = v > 0.f ? v : 0.f;
+      if (res) v = res[r * ldr + o] + v;
+      if (res2) v = res2[r * ldr + o] + v;
+      Y[r * ldy + o] = v;
+    }
+  }
+}
+
+__device__ inline void mm(const float* X, int ldx, int R, int I, const float* Wt, int ldw, int O, const float* bias,
+                          float* Y, int ldy, int act = ACT_NONE, const float* res = nullptr,
+                          const float* res2 = nullptr, int ldr = 0) {
+  const int work = R * O;
+  if (work >= 8 * NT) mm_rb<8>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
+  else if (work >= 4 * NT) mm_rb<4>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
+  else if (work >= 2 * NT) mm_rb<2>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
+  else mm_rb<1>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
+}
+
+// LayerNorm (eps 1e-5, biased variance) of R rows of n <= 64 floats: 32 lanes per row, two passes.
+__device__ inline void layernorm(const float* X, int ldx, int R, int n, const float* __restrict__ w,
+                                 const float* __restrict__ b, float* Y, int ldy) {
+  const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
+  for (int r = team; r < R; r += NT / 32) {
+    const float* x = X + r * ldx;
+    const float x0 = lane < n ? x[lane] : 0.f, x1 = lane + 32 < n ? x[lane + 32] : 0.f;
+    float s = x0 + x1;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) s += __shfl_xor(s, m, 32);
+    const float mean = s / static_cast<float>(n);
+    const float d0 = lane < n ? x0 - mean : 0.f, d1 = lane + 32 < n ? x1 - mean : 0.f;
+    float v = d0 * d0 + d1 * d1;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
+    const float rstd = 1.f / sqrtf(v / static_cast<float>(n) + 1e-5f);
+    if (lane < n) Y[r * ldy + lane] = d0 * rstd * w[lane] + b[lane];
+    if (lane + 32 < n) Y[r * ldy + lane + 32] = d1 * rstd * w[lane + 32] + b[lane + 32];
+  }
+}
+
+// softmax in place over rows of n entries (one thread per row)
+__device__ inline void softmax_rows(float* A, int rows, int n, int ld) {
+  for (int r = threadIdx.x; r < rows; r += NT) {
+    float* a = A + r * ld;
+    float m = a[0];
+    for (int j = 1; j < n; ++j) m = fmaxf(m, a[j]);
+    float s = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const float e = expf(a[j] - m);
+      a[j] = e;
+      s += e;
+    }
+    const float inv = 1.f / s;
+    for (int j = 0; j < n; ++j) a[j] *= inv;
+  }
+}
+
+// ---- torso --------------------------------------------------------------------------------------------------------
+struct TorsoArgs {
+  tg_net_config c;
+  Off off;
+  const float* w;
+  const void* frames;
+  int frames_i8;
+  const float* scalars;
+  float* ee;
+  int64_t B;
+};
+
+__global__ void __launch_bounds__(NT) net_torso_kernel(TorsoArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const tg_net_config& c = a.c;
+  const int S = c.S, S2 = S * S, T2 = 2 * S2, C = c.c, cin = S * c.T + 1;
+  const int64_t g = blockIdx.x;
+  if (g >= a.B) return;
+  const TorsoPlan P = torso_plan(c);
+  float *G = lds + P.G, *X = lds + P.X, *XN = lds + P.XN, *YN = lds + P.YN, *Y = lds + P.Y, *QKV = lds + P.QKV,
+        *SC = lds + P.SC;
+  // input grids: IN[m][i*S+j][ch], ch = c3*T + t < S*T from the frames, ch = S*T the scalar projection
+  float* IN = QKV;
+  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
+  for (int it = threadIdx.x; it < 3 * S2 * cin; it += NT) {
+    const int ch = it % cin, tok = (it / cin) % S2, m = it / (cin * S2);
+    float v;
+    if (ch == cin - 1) {
+      const float* Wt = a.w + a.off.t_li1[m];
+      float s = 0.f;
+      for (int q = 0; q < c.dim_s; ++q) s = fmaf(a.scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
+      v = s + Wt[c.dim_s * S2 + tok];
+    } else {
+      const int p = tok / S, q = tok % S, c3 = ch / c.T, t = ch % c.T;
+      int a0, a1, a2;
+      if (m == 0) { a0 = p; a1 = q; a2 = c3; }
+      else if (m == 1) { a0 = q; a1 = c3; a2 = p; }
+      else { a0 = c3; a1 = p; a2 = q; }
+      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
+      v = a.frames_i8 ? static_cast<float>(static_cast<const int8_t*>(a.frames)[idx])
+                      : static_cast<const float*>(a.frames)[idx];
+    }
+    IN[it] = v;
+  }
+  __syncthreads();
+  for (int m = 0; m < 3; ++m) {
+    const float* Wt = a.w + a.off.t_li2[m];
+    mm(IN + m * S2 * cin, cin, S2, cin, Wt, C, C, Wt + cin * C, G + m * S2 * C, C);
+  }
+  __syncthreads();
+  const int H = c.torso_heads, d = c.torso_d, hd = H * d, ff = c.torso_ff;
+  const float sd = sqrtf(static_cast<float>(d));
+  float *Q = QKV, *K = QKV + T2 * d, *V = QKV + 2 * T2 * d;
+  for (int l = 0; l < c.torso_layers; ++l) {
+    const Mha mh = mha_at(a.w + a.off.t_layer0 + l * a.off.t_layer, C, C, H, d, ff);
+    for (int pr = 0; pr < 3; ++pr) {
+      const int m1 = pr, m2 = pr == 2 ? 0 : pr + 1;
+      // token r = i*2S + u: grid m1 row (i, u) for u < S, grid m2 row (i, u - S) otherwise
+      for (int it = threadIdx.x; it < T2 * C; it += NT) {
+        const int ch = it % C, r = it / C, i = r / (2 * S), u = r % (2 * S);
+        const float v = u < S ? G[(m1 * S2 + i * S + u) * C + ch] : G[(m2 * S2 + i * S + u - S) * C + ch];
+        X[it] = v;
+        Y[it] = v;
+      }
+      __syncthreads();
+      layernorm(X, C, T2, C, mh.ln1w, mh.ln1b, XN, C);
+      layernorm(X, C, T2, C, mh.ln2w, mh.ln2b, YN, C);
+      __syncthreads();
+      for (int h = 0; h < H; ++h) {
+        mm(XN, C, T2, C, mh.q + h * d, hd, d, nullptr, Q, d);
+        // keys: K[r][e] = sum_i YN[r][i] * k[h*d+e][i]  (k stored [hd][c])
+        for (int it = threadIdx.x; it < T2 * d; it += NT) {
+          const int e = it % d, r = it / d;
+          const float* kr = mh.k + (h * d + e) * C;
+          float s = 0.f;
+#pragma unroll 8
+          for (int i = 0; i < C; ++i) s = fmaf(YN[r * C + i], kr[i], s);
+          K[it] = s;
+        }
+        mm(YN, C, T2, C, mh.v + h * d, hd, d, nullptr, V, d);
+        __syncthreads();
+        // scores of sequence i: SC[i][a][b] = Q[i,a] . K[i,b] / sqrt(d)
+        const int L2 = 2 * S;
+        for (int it = threadIdx.x; it < S * L2 * L2; it += NT) {
+          const int bb = it % L2, aa = (it / L2) % L2, i = it / (L2 * L2);
+          const float* q = Q + (i * L2 + aa) * d;
+          const float* k = K + (i * L2 + bb) * d;
+          float s = 0.f;
+#pragma unroll 8
+          for (int e = 0; e < d; ++e) s = fmaf(q[e], k[e], s);
+          SC[it] = s / sd;
+        }
+        __syncthreads();
+        softmax_rows(SC, S * L2, L2, L2);
+        __syncthreads();
+        // O (into Q) = A @ V per sequence
+        for (int it = threadIdx.x; it < T2 * d; it += NT) {
+          const int e = it % d, r = it / d, i = r / L2, aa = r % L2;
+          const float* ar = SC + (i * L2 + aa) * L2;
+          float s = 0.f;
+          for (int bb = 0; bb < L2; ++bb) s = fmaf(ar[bb], V[(i * L2 + bb) * d + e], s);
+          Q[it] = s;
+        }
+        __syncthreads();
+        // Y += O_h @ li1[h*d .. h*d+d-1][:] (+ the bias with head 0)
+        mm(Q, d, T2, d, mh.li1w + h * d * C, C, C, h == 0 ? mh.li1b : nullptr, Y, C, ACT_NONE, Y, nullptr, C);
+        __syncthreads();
+      }
+      layernorm(Y, C, T2, C, mh.ln3w, mh.ln3b, XN, C);
+      __syncthreads();
+      mm(XN, C, T2, C, mh.li2w, ff, ff, mh.li2b, QKV, ff, ACT_GELU);
+      __syncthreads();
+      mm(QKV, ff, T2, ff, mh.li3w, C, C, mh.li3b, X, C, ACT_NONE, Y, nullptr, C);
+      __syncthreads();
+      for (int it = threadIdx.x; it < T2 * C; it += NT) {
+        const int ch = it % C, r = it / C, i = r / (2 * S), u = r % (2 * S);
+        if (u < S) G[(m1 * S2 + i * S + u) * C + ch] = X[it];
+        else G[(m2 * S2 + i * S + u - S) * C + ch] = X[it];
+      }
+      __syncthreads();
+    }
+  }
+  // ee row i*3S + m*S + j = grid m row (i, j)
+  float* out = a.ee + g * 3 * S2 * C;
+  for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) {
+    const int ch = it % C, row = it / C, i = row / (3 * S), m = (row / S) % 3, j = row % S;
+    out[it] = G[(m * S2 + i * S + j) * C + ch];
+  }
+}
+
+// ---- decoder ------------------------------------------------------------------------------------------------------
+struct DecArgs {
+  tg_net_config c;
+  Off off;
+  const float* w;
+  const float* ee;
+  int64_t B;
+  int k, R, chunks, teacher;
+  const int64_t* rows;      // sampling: game index of each batch row (keys the stream)
+  uint32_t seed_lo, seed_hi, call_lo;
+  const float* uniforms;    // (B,k,n_steps) or NULL
+  int8_t* tokens;           // (B,k,n_steps)
+  float* probs;             // (B,k)
+  float* q;                 // sampling: (B,) risk value; teacher: (B,n_quantile)
+  const int64_t* g_action;  // teacher: (B,n_steps)
+  float* oo;                // teacher: (B,n_steps,n_logits)
+  float* zz0;               // teacher: (B,W)
+};
+
+__global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const tg_net_config& c = a.c;
+  const int64_t g = blockIdx.x / a.chunks;
+  if (g >= a.B) return;
+  const int s0 = static_cast<int>(blockIdx.x % a.chunks) * a.R;
+  const int R = a.k - s0 < a.R ? a.k - s0 : a.R;  // rows of this workgroup: samples s0 .. s0+R-1
+  const int W = c.W, C = c.c, H = c.heads, d = c.d, hd = H * d, ff = c.ff, J = 3 * c.S * c.S, NS = c.n_steps;
+  const int NL = c.n_logits;
+  const DecPlan P = dec_plan(c, a.R);
+  float *EEN = lds + P.EEN, *CACHE = lds + P.CACHE, *X = lds + P.X, *XB = lds + P.XB, *XN = lds + P.XN,
+        *Q = lds + P.Q, *QK = lds + P.QK, *SC = lds + P.SC, *YB = lds + P.YB, *O = lds + P.O, *H1 = lds + P.H1,
+        *M = lds + P.M, *F = lds + P.F, *LG = lds + P.LG, *Z0 = lds + P.Z0, *V1 = lds + P.V1, *V2 = lds + P.V2;
+  float* PP = lds + P.MISC;
+  int* TOK = reinterpret_cast<int*>(lds + P.MISC + a.R);
+  const int wq = P.wq, nsc = P.nsc;
+  const float sd = sqrtf(static_cast<float>(d));
+  const float* wb = a.w;
+  const float* emb = wb + a.off.emb;
+  const float* pos = wb + a.off.pos;
+  const int cstride = c.blocks * NS * W;  // cache floats per row
+
+  // ln2 of each block's cross-attention over the game's ee
+  const float* eeg = a.ee + g * J * C;
+  for (int b = 0; b < c.blocks; ++b) {
+    const float* bp = wb + a.off.blk0 + b * a.off.blk;
+    const Mha a2 = mha_at(bp + 2 * W + mha_size(W, W, H, d, ff) + 2 * W, W, C, H, d, ff);
+    layernorm(eeg, C, J, C, a2.ln2w, a2.ln2b, EEN + b * J * C, C);
+  }
+  for (int it = threadIdx.x; it < R * W; it += NT) X[it] = emb[NL * W + it % W] + pos[it % W];
+  for (int r = threadIdx.x; r < R; r += NT) PP[r] = 1.f;
+  __syncthreads();
+
+  for (int t = 0; t < NS; ++t) {
+    for (int b = 0; b < c.blocks; ++b) {
+      const float* bp = wb + a.off.blk0 + b * a.off.blk;
+      const float *bln1w = bp, *bln1b = bp + W;
+      const Mha a1 = mha_at(bp + 2 * W, W, W, H, d, ff);
+      const float* bln2 = bp + 2 * W + mha_size(W, W, H, d, ff);
+      const Mha a2 = mha_at(bln2 + 2 * W, W, C, H, d, ff);
+      float* cache = CACHE + b * NS * W;  // row r: + r * cstride; position j: + j * W
+      // ---- self-attention: xb = ln1(x); x = xb + att1(xb, xb)
+      layernorm(X, W, R, W, bln1w, bln1b, XB, W);
+      __syncthreads();
+      layernorm(XB, W, R, W, a1.ln1w, a1.ln1b, XN, W);
+      layernorm(XB, W, R, W, a1.ln2w, a1.ln2b, cache + t * W, cstride);
+      __syncthreads();
+      mm(XN, W, R, W, a1.q, hd, hd, nullptr, Q, hd);
+      __syncthreads();
+      for (int h = 0; h < H; ++h)  // QK[r][h][i] = sum_e q[r][h*d+e] * k[h*d+e][i]
+        mm(Q + h * d, hd, R, d, a1.k + h * d * W, W, W, nullptr, QK + h * wq, H * wq);
+      __syncthreads();
+      for (int it = threadIdx.x; it < R * H * (t + 1); it += NT) {
+        const int j = it % (t + 1), rh = it / (t + 1), r = rh / H, h = rh % H;
+        const float* qk = QK + (r * H + h) * wq;
+        const float* y = cache + r * cstride + j * W;
+        float s = 0.f;
+        for (int i = 0; i < W; ++i) s = fmaf(qk[i], y[i], s);
+        SC[rh * nsc + j] = s / sd;
+      }
+      __syncthreads();
+      softmax_rows(SC, R * H, t + 1, nsc);
+      __syncthreads();
+      for (int it = threadIdx.x; it < R * H * W; it += NT) {
+        const int i = it % W, rh = it / W, r = rh / H;
+        const float* sc = SC + rh * nsc;
+        const float* y = cache + r * cstride + i;
+        float s = 0.f;
+        for (int j = 0; j <= t; ++j) s = fmaf(sc[j], y[j * W], s);
+        YB[rh * wq + i] = s;
+      }
+      __syncthreads();
+      for (int h = 0; h < H; ++h) mm(YB + h * wq, H * wq, R, W, a1.v + h * d, hd, d, nullptr, O + h * d, hd);
+      __syncthreads();
+      mm(O, hd, R, hd, a1.li1w, W, W, a1.li1b, H1, W, ACT_NONE, XB, nullptr, W);
+      __syncthreads();
+      layernorm(H1, W, R, W, a1.ln3w, a1.ln3b, M, W);
+      __syncthreads();
+      mm(M, W, R, W, a1.li2w, ff, ff, a1.li2b, F, ff, ACT_GELU);
+      __syncthreads();
+      mm(F, ff, R, ff, a1.li3w, W, W, a1.li3b, X, W, ACT_NONE, H1, XB, W);
+      __syncthreads();
+      // ---- cross-attention: xb = ln2(x); x = xb + att2(xb, ee)
+      layernorm(X, W, R, W, bln2, bln2 + W, XB, W);
+      __syncthreads();
+      layernorm(XB, W, R, W, a2.ln1w, a2.ln1b, XN, W);
+      __syncthreads();
+      mm(XN, W, R, W, a2.q, hd, hd, nullptr, Q, hd);
+      __syncthreads();
+      for (int h = 0; h < H; ++h) mm(Q + h * d, hd, R, d, a2.k + h * d * C, C, C, nullptr, QK + h * wq, H * wq);
+      __syncthreads();
+      const float* een = EEN + b * J * C;
+      for (int it = threadIdx.x; it < R * H * J; it += NT) {
+        const int j = it % J, rh = it / J;
+        const float* qk = QK + rh * wq;
+        const float* y = een + j * C;
+        float s = 0.f;
+        for (int i = 0; i < C; ++i) s = fmaf(qk[i], y[i], s);
+        SC[rh * nsc + j] = s / sd;
+      }
+      __syncthreads();
+      softmax_rows(SC, R * H, J, nsc);
+      __syncthreads();
+      for (int it = threadIdx.x; it < R * H * C; it += NT) {
+        const int i = it % C, rh = it / C;
+        const float* sc = SC + rh * nsc;
+        float s = 0.f;
+        for (int j = 0; j < J; ++j) s = fmaf(sc[j], een[j * C + i], s);
+        YB[rh * wq + i] = s;
+      }
+      __syncthreads();
+      for (int h = 0; h < H; ++h) mm(YB + h * wq, H * wq, R, C, a2.v + h * d, hd, d, nullptr, O + h * d, hd);
+      __syncthreads();
+      mm(O, hd, R, hd, a2.li1w, W, W, a2.li1b, H1, W, ACT_NONE, XB, nullptr, W);
+      __syncthreads();
+      layernorm(H1, W, R, W, a2.ln3w, a2.ln3b, M, W);
+      __syncthreads();
+      mm(M, W, R, W, a2.li2w, ff, ff, a2.li2b, F, ff, ACT_GELU);
+      __syncthreads();
+      mm(F, ff, R, ff, a2.li3w, W, W, a2.li3b, X, W, ACT_NONE, H1, XB, W);
+      __syncthreads();
+    }
+    if (t == 0)
+      for (int it = threadIdx.x; it < R * W; it += NT) Z0[it] = X[it];
+    // logits = li1(relu(x))
+    for (int it = threadIdx.x; it < R * W; it += NT) XN[it] = X[it] > 0.f ? X[it] : 0.f;
+    __syncthreads();
+    mm(XN, W, R, W, wb + a.off.out, NL, NL, wb + a.off.out + W * NL, LG, TG_NET_MAX_LOGITS);
+    __syncthreads();
+    for (int r = threadIdx.x; r < R; r += NT) {
+      const float* lg = LG + r * TG_NET_MAX_LOGITS;
+      const int s = s0 + r;
+      int tok;
+      if (a.teacher) {
+        float* oo = a.oo ? a.oo + (g * NS + t) * NL : nullptr;
+        if (oo)
+          for (int l = 0; l < NL; ++l) oo[l] = lg[l];
+        const int64_t gt = a.g_action[g * NS + t];
+        tok = gt >= 0 && gt <= NL ? static_cast<int>(gt) : NL;
+      } else {
+        float u;
+        if (a.uniforms) {
+          u = a.uniforms[(g * a.k + s) * NS + t];
+        } else {
+          const U4 ctr{static_cast<uint32_t>(a.rows[g]), a.call_lo, static_cast<uint32_t>(s),
+                       static_cast<uint32_t>(t >> 2)};
+          const U4 wv = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
+          const uint32_t word = (t & 3) == 0 ? wv.x : (t & 3) == 1 ? wv.y : (t & 3) == 2 ? wv.z : wv.w;
+          u = static_cast<float>(word >> 8) * 5.9604644775390625e-8f;
+        }
+        float mx = lg[0];
+        for (int l = 1; l < NL; ++l) mx = fmaxf(mx, lg[l]);
+        float sum = 0.f;
+        for (int l = 0; l < NL; ++l) sum += expf(lg[l] - mx);
+        tok = NL - 1;
+        float cum = 0.f, pt = expf(lg[NL - 1] - mx) / sum;
+        for (int l = 0; l < NL; ++l) {
+          const float p = expf(lg[l] - mx) / sum;
+          cum += p;
+          if (u < cum) {
+            tok = l;
+            pt = p;
+            break;
+          }
+        }
+        PP[r] *= pt;
+        if (a.tokens) a.tokens[(g * a.k + s) * NS + t] = static_cast<int8_t>(tok);
+      }
+      TOK[r] = tok;
+    }
+    __syncthreads();
+    if (t + 1 < NS) {
+      for (int it = threadIdx.x; it < R * W; it += NT) {
+        const int r = it / W, i = it % W;
+        X[it] = emb[TOK[r] * W + i] + pos[(t + 1) * W + i];
+      }
+      __syncthreads();
+    }
+  }
+  if (!a.teacher && a.probs)
+    for (int r = threadIdx.x; r < R; r += NT) a.probs[g * a.k + s0 + r] = PP[r];
+  if (a.teacher && a.zz0)
+    for (int i = threadIdx.x; i < W; i += NT) a.zz0[g * W + i] = Z0[i];
+  // value head on the position-0 output of sample 0 (every sample's is the same)
+  if (s0 != 0 || !a.q) return;
+  const int nh = c.n_hidden, nq = c.n_quantile;
+  mm(Z0, W, 1, W, wb + a.off.v[0], nh, nh, wb + a.off.v[0] + W * nh, V1, nh, ACT_RELU);
+  __syncthreads();
+  mm(V1, nh, 1, nh, wb + a.off.v[1], nh, nh, wb + a.off.v[1] + nh * nh, V2, nh, ACT_RELU);
+  __syncthreads();
+  mm(V2, nh, 1, nh, wb + a.off.v[2], nh, nh, wb + a.off.v[2] + nh * nh, V1, nh, ACT_RELU);
+  __syncthreads();
+  mm(V1, nh, 1, nh, wb + a.off.v[3], nq, nq, wb + a.off.v[3] + nh * nq, V2, nq);
+  __syncthreads();
+  if (a.teacher) {
+    for (int i = threadIdx.x; i < nq; i += NT) a.q[g * nq + i] = V2[i];
+  } else if (threadIdx.x == 0) {
+    const int jj = (3 * nq + 3) / 4 - 1;  // ceil(0.75 n) - 1
+    float s = 0.f;
+    for (int i = jj; i < nq; ++i) s += V2[i];
+    a.q[g] = s / static_cast<float>(nq - jj);
+  }
+}
+
+}  // namespace net
+}  // namespace tg
+
+namespace {
+
+constexpr int kMaxLds = 160 * 1024;
+
+int launched(const char* fn) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return TG_OK;
+}
+
+int check_cfg(const char* fn, const tg_net_config* c) {
+  if (!c) return tg_internal_fail(TG_ERR_INVALID, "%s: null config", fn);
+  const int32_t dims[] = {c->S, c->T, c->dim_s, c->c, c->torso_layers, c->torso_heads, c->torso_d, c->torso_ff, c->W,
+                          c->heads, c->d, c->ff, c->blocks, c->n_steps, c->n_logits, c->n_hidden, c->n_quantile};
+  const char* names[] = {"dim_3d", "dim_t", "dim_s", "dim_c", "torso_layers", "torso_heads", "torso_d", "torso_ff",
+                         "W", "heads", "d", "ff", "blocks", "n_steps", "n_logits", "n_hidden", "n_quantile"};
+  const int32_t maxs[] = {TG_NET_MAX_S, TG_NET_MAX_T, TG_NET_MAX_DIM_S, TG_NET_MAX_C, TG_NET_MAX_LAYERS,
+                          TG_NET_MAX_HEADS, TG_NET_MAX_D, TG_NET_MAX_TORSO_FF, TG_NET_MAX_W, TG_NET_MAX_HEADS,
+                          TG_NET_MAX_D, TG_NET_MAX_FF, TG_NET_MAX_BLOCKS, TG_NET_MAX_STEPS, TG_NET_MAX_LOGITS,
+                          TG_NET_MAX_HIDDEN, TG_NET_MAX_QUANTILE};
+  const char* bound[] = {"TG_NET_MAX_S", "TG_NET_MAX_T", "TG_NET_MAX_DIM_S", "TG_NET_MAX_C", "TG_NET_MAX_LAYERS",
+                         "TG_NET_MAX_HEADS", "TG_NET_MAX_D", "TG_NET_MAX_TORSO_FF", "TG_NET_MAX_W", "TG_NET_MAX_HEADS",
+                         "TG_NET_MAX_D", "TG_NET_MAX_FF", "TG_NET_MAX_BLOCKS", "TG_NET_MAX_STEPS", "TG_NET_MAX_LOGITS",
+                         "TG_NET_MAX_HIDDEN", "TG_NET_MAX_QUANTILE"};
+  for (int i = 0; i < 17; ++i) {
+    if (dims[i] < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, names[i], dims[i]);
+    if (dims[i] > maxs[i])
+      return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, names[i], dims[i], bound[i], maxs[i]);
+  }
+  const size_t lt = tg::net::torso_plan(*c).total * sizeof(float), ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
+  if (lt > kMaxLds || ld > kMaxLds)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: the LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB", fn,
+                            lt, ld);
+  return TG_OK;
+}
+
+int check_common(const char* fn, const tg_net_config* c, const float* w, int64_t B) {
+  if (int rc = check_cfg(fn, c)) return rc;
+  if (B < 0 || B > (1LL << 30)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld out of range", fn, (long long)B);
+  if (!w) return tg_internal_fail(TG_ERR_INVALID, "%s: null weights", fn);
+  if (reinterpret_cast<uintptr_t>(w) & 3) return tg_internal_fail(TG_ERR_INVALID, "%s: weights not 4-byte aligned", fn);
+  return TG_OK;
+}
+
+bool misaligned(const void* p, int bytes) { return p && (reinterpret_cast<uintptr_t>(p) % bytes) != 0; }
+
+// the > 64 KiB dynamic LDS opt-in, once per (kernel, device)
+int lds_opt_in(const char* fn, const void* kernel, int which, size_t bytes) {
+  static std::atomic<unsigned> done[2][64];
+  if (bytes <= 64 * 1024) return TG_OK;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (done[which][dev].load(std::memory_order_relaxed)) return TG_OK;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  done[which][dev].store(1, std::memory_order_relaxed);
+  return TG_OK;
+}
+
+int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
+  // rows per workgroup: up to 8 samples of one game, fewer when the plan would not fit in LDS
+  int R = a.k < 8 ? a.k : 8;
+  while (R > 1 && tg::net::dec_plan(a.c, R).total * sizeof(float) > static_cast<size_t>(kMaxLds)) --R;
+  a.R = R;
+  a.chunks = (a.k + R - 1) / R;
+  if (a.B * a.chunks > INT32_MAX)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn,
+                            (long long)a.B, a.chunks);
+  const size_t lds = tg::net::dec_plan(a.c, R).total * sizeof(float);
+  if (int rc = lds_opt_in(fn, reinterpret_cast<const void*>(tg::net::net_decode_kernel), 1, lds)) return rc;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(tg::net::net_decode_kernel, dim3(static_cast<unsigned>(a.B * a.chunks)), dim3(tg::net::NT), lds, st,
+                     a);
+  return launched(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+// model.py:85-280 (the configuration a state_dict implies)
+int tg_net_check(const tg_net_config* cfg) { return check_cfg("tg_net_check", cfg); }
+
+int tg_net_weights_size(const tg_net_config* cfg, int64_t* floats) {
+  if (int rc = check_cfg("tg_net_weights_size", cfg)) return rc;
+  if (!floats) return tg_internal_fail(TG_ERR_INVALID, "tg_net_weights_size: null output");
+  *floats = tg::net::offsets(*cfg).total;
+  return TG_OK;
+}
+
+// Torso.forward, model.py:97-123
+int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8, const float* scalars,
+                 float* ee, int64_t B, tg_stream_t stream) {
+  const char* fn = "tg_net_torso";
+  if (int rc = check_common(fn, cfg, w, B)) return rc;
+  if (frames_is_i8 != 0 && frames_is_i8 != 1)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_is_i8=%d (0 float32, 1 int8)", fn, frames_is_i8);
+  if (B == 0) return TG_OK;
+  if (!frames || !scalars || !ee) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames, scalars or ee", fn);
+  if (misaligned(frames, frames_is_i8 ? 1 : 4) || misaligned(scalars, 4) || misaligned(ee, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
+  tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B};
+  const size_t lds = tg::net::torso_plan(*cfg).total * sizeof(float);
+  if (int rc = lds_opt_in(fn, reinterpret_cast<const void*>(tg::net::net_torso_kernel), 0, lds)) return rc;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(tg::net::net_torso_kernel, dim3(static_cast<unsigned>(B)), dim3(tg::net::NT), lds,
+                     static_cast<hipStream_t>(stream), a);
+  return launched(fn);
+}
+
+// PolicyHead.fwd_infer + ValueHead + value_risk_mgmt, model.py:234-261, 266-280, 322-324 (AlphaTensor.fwd_infer :347-356)
+int tg_net_sample(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B, int k,
+                  uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
+                  tg_stream_t stream) {
+  const char* fn = "tg_net_sample";
+  if (int rc = check_common(fn, cfg, w, B)) return rc;
+  if (k < 1 || k > TG_NET_MAX_SAMPLES)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: k=%d outside [1, TG_NET_MAX_SAMPLES=%d]", fn, k, TG_NET_MAX_SAMPLES);
+  if (B == 0) return TG_OK;
+  if (!ee || (!rows && !uniforms)) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee, or null rows without uniforms", fn);
+  if (misaligned(ee, 4) || misaligned(rows, 8) || misaligned(uniforms, 4) || misaligned(probs, 4) || misaligned(q, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, rows, uniforms, probs or q not aligned to their elements", fn);
+  tg::net::DecArgs a{};
+  a.c = *cfg;
+  a.off = tg::net::offsets(*cfg);
+  a.w = w;
+  a.ee = ee;
+  a.B = B;
+  a.k = k;
+  a.teacher = 0;
+  a.rows = rows;
+  a.seed_lo = static_cast<uint32_t>(seed);
+  a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.call_lo = static_cast<uint32_t>(call);
+  a.uniforms = uniforms;
+  a.tokens = tokens_i8;
+  a.probs = probs;
+  a.q = q;
+  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+}
+
+// the forward of PolicyHead.fwd_train, model.py:219-232, and ValueHead on its zz[:, 0] (AlphaTensor.fwd_train :335-338)
+int tg_net_logits(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* g_action, int64_t B,
+                  float* oo, float* zz0, float* q, tg_stream_t stream) {
+  const char* fn = "tg_net_logits";
+  if (int rc = check_common(fn, cfg, w, B)) return rc;
+  if (B == 0) return TG_OK;
+  if (!ee || !g_action) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee or g_action", fn);
+  if (misaligned(ee, 4) || misaligned(g_action, 8) || misaligned(oo, 4) || misaligned(zz0, 4) || misaligned(q, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, g_action, oo, zz0 or q not aligned to their elements", fn);
+  tg::net::DecArgs a{};
+  a.c = *cfg;
+  a.off = tg::net::offsets(*cfg);
+  a.w = w;
+  a.ee = ee;
+  a.B = B;
+  a.k = 1;
+  a.teacher = 1;
+  a.q = q;
+  a.g_action = g_action;
+  a.oo = oo;
+  a.zz0 = zz0;
+  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

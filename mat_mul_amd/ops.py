@@ -21,6 +21,7 @@ __all__ = [
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
+    "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
 ]
 
 
@@ -805,3 +806,94 @@ def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=
              _ptr(kind), _ptr(src), len_data, code, _ptr(idx), N, int(T), _ITEM_DTYPES[dtype], _ptr(out),
              _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), _stream(dev))
     return out, scalars, actions, rewards
+
+
+# ---- fused network inference (include/tensor_game_net.h) ------------------------------------------------------------
+
+
+def net_check(cfg) -> None:
+    """Raise TensorGameError (naming the bound) unless ``cfg`` (``_lib.NetConfig``) is in the supported family."""
+    call("tg_net_check", C.byref(cfg))
+
+
+def net_weights_size(cfg) -> int:
+    """Floats in the packed weight blob of ``cfg`` (tg_net_weights_size)."""
+    out = C.c_int64(0)
+    call("tg_net_weights_size", C.byref(cfg), C.byref(out))
+    return int(out.value)
+
+
+def _net_blob(cfg, w: torch.Tensor) -> torch.device:
+    _need_gpu(w, "weights")
+    n = net_weights_size(cfg)
+    if w.dtype != torch.float32 or tuple(w.shape) != (n,) or not w.is_contiguous():
+        raise TensorGameError("weights", -1, f"weights must be a contiguous float32 blob of {n} floats, got {w.dtype} "
+                              f"{tuple(w.shape)}")
+    return w.device
+
+
+def net_torso(cfg, w, frames, scalars, out=None) -> torch.Tensor:
+    """Torso.forward (tg_net_torso): frames (B,T,S,S,S) float32 or int8, scalars float32 (B,dim_s) -> ee float32
+    (B,3S^2,c)."""
+    dev = _net_blob(cfg, w)
+    _need_gpu(frames, "frames")
+    B = frames.shape[0] if frames.dim() == 5 else -1
+    want = (B, cfg.T, cfg.S, cfg.S, cfg.S)
+    if frames.dtype not in (torch.float32, torch.int8) or tuple(frames.shape) != want or frames.device != dev:
+        raise TensorGameError("net_torso", -1, f"frames must be float32 or int8 (B,T,S,S,S) = {want[1:]} per game on "
+                              f"{dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    frames = frames.contiguous()
+    scalars = _flag(scalars.contiguous(), (B, cfg.dim_s), torch.float32, dev, "scalars")
+    shape = (B, 3 * cfg.S * cfg.S, cfg.c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    out = _flag(out, shape, torch.float32, dev, "out")
+    with torch.cuda.device(dev):
+        call("tg_net_torso", C.byref(cfg), _ptr(w), _ptr(frames), 1 if frames.dtype == torch.int8 else 0,
+             _ptr(scalars), _ptr(out), B, _stream(dev))
+    return out
+
+
+def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None, tokens=None, probs=None, q=None):
+    """PolicyHead.fwd_infer + the risk-managed value (tg_net_sample) for ee float32 (B,3S^2,c): returns tokens int8
+    (B,k,n_steps), probs float32 (B,k), q float32 (B,).  ``rows`` int64 (B,) key the random stream with ``seed`` and
+    ``call_idx``; ``uniforms`` float32 (B,k,n_steps) replaces the stream when given."""
+    dev = _net_blob(cfg, w)
+    B = ee.shape[0]
+    ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
+    rows = _flag(rows, (B,), torch.int64, dev, "rows")
+    uniforms = _flag(uniforms, (B, k, cfg.n_steps), torch.float32, dev, "uniforms")
+    if tokens is None:
+        tokens = torch.empty((B, k, cfg.n_steps), dtype=torch.int8, device=dev)
+    if probs is None:
+        probs = torch.empty((B, k), dtype=torch.float32, device=dev)
+    if q is None:
+        q = torch.empty((B,), dtype=torch.float32, device=dev)
+    tokens = _flag(tokens, (B, k, cfg.n_steps), torch.int8, dev, "tokens")
+    probs = _flag(probs, (B, k), torch.float32, dev, "probs")
+    q = _flag(q, (B,), torch.float32, dev, "q")
+    with torch.cuda.device(dev):
+        call("tg_net_sample", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), int(seed) & (2 ** 64 - 1),
+             int(call_idx) & (2 ** 64 - 1), _ptr(uniforms), _ptr(tokens), _ptr(probs), _ptr(q), _stream(dev))
+    return tokens, probs, q
+
+
+def net_logits(cfg, w, ee, g_action):
+    """The forward of PolicyHead.fwd_train and the ValueHead on zz[:, 0] (tg_net_logits): ee float32 (B,3S^2,c),
+    g_action (B,n_steps) integer tokens -> oo float32 (B,n_steps,n_logits), zz0 float32 (B,W), q float32
+    (B,n_quantile)."""
+    dev = _net_blob(cfg, w)
+    B = ee.shape[0]
+    ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
+    _need_gpu(g_action, "g_action")
+    if tuple(g_action.shape) != (B, cfg.n_steps) or g_action.dtype.is_floating_point:
+        raise TensorGameError("net_logits", -1, f"g_action must be integer (B,n_steps) = {(B, cfg.n_steps)}, got "
+                              f"{g_action.dtype} {tuple(g_action.shape)}")
+    g_action = g_action.to(dev, torch.int64).contiguous()
+    oo = torch.empty((B, cfg.n_steps, cfg.n_logits), dtype=torch.float32, device=dev)
+    zz0 = torch.empty((B, cfg.W), dtype=torch.float32, device=dev)
+    q = torch.empty((B, cfg.n_quantile), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        call("tg_net_logits", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q),
+             _stream(dev))
+    return oo, zz0, q

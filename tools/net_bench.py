@@ -1,0 +1,153 @@
+"""The fused network (include/tensor_game_net.h) against the float32 restatement run eagerly, at the training app's
+configuration (tests/net_ref.CONFIGS["a"]: S 4, T 2, c 8, W 32, 8 + 2 layers, n_steps 12), k = 8.
+
+    python tools/net_bench.py OUT_DIR [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
+
+One process, one GPU.  Per B in {256, 1024, 4096}: FusedAlphaTensor.fwd_infer and the eager Ref.fwd_infer (the
+reference's op structure: the whole prefix rerun at every token step, torch's Categorical) alternate call by call;
+HIP events around each call after warm-up; median, p10 and p90 in microseconds.  FLOPs are counted from shapes for the
+fused algorithm (the decoder with its cache).  Then one self-play figure: microseconds per simulation of
+search.actor_prediction with net.policy at S = 4, B = 4096.  --fused-only runs the fused calls alone (for a kernel-trace
+run); --kernel-stats merges a rocprofv3 --stats CSV into an existing OUT_DIR/r08_net.json.  Writes OUT_DIR/r08_net.json.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+from mat_mul_amd import FusedAlphaTensor, search  # noqa: E402
+from net_ref import CONFIGS, Ref, dims, make_inputs, make_weights  # noqa: E402
+
+DEV = "cuda:0"
+FP32_PEAK = 157.3e12  # MI355X vector FP32, FLOP/s (FMA = 2)
+
+
+def flops(m, B, k):
+    """Multiply-adds x 2 of the fused algorithm, from shapes."""
+    S2, T2 = m["S"] ** 2, 2 * m["S"] ** 2
+    c, hd, ff = m["c"], m["torso_heads"] * m["torso_d"], m["torso_ff"]
+    L2 = 2 * m["S"]
+    pair = T2 * c * hd * 3 + m["S"] * L2 * L2 * hd * 2 + T2 * hd * c + T2 * c * ff * 2
+    torso = 3 * S2 * (m["S"] * m["T"] + 1) * c + m["torso_layers"] * 3 * pair
+    W, H, d, J, n = m["W"], m["heads"], m["d"], 3 * S2, m["n_steps"]
+    hd, ff = H * d, m["ff"]
+    mlp = W * hd + W * ff * 2  # li1, li2, li3
+    dec = 0
+    for t in range(n):
+        self_att = W * hd + hd * W + H * (t + 1) * W * 2 + W * hd + mlp
+        cross = W * hd + hd * c + H * J * c * 2 + c * hd + mlp
+        dec += m["blocks"] * (self_att + cross) + W * m["n_logits"]
+    nh = m["n_hidden"]
+    value = W * nh + 2 * nh * nh + nh * m["n_quantile"]
+    return 2 * (B * torso + B * k * dec + B * value)
+
+
+def stats(ts):
+    ts = sorted(ts)
+    q = lambda f: ts[min(len(ts) - 1, int(f * len(ts)))]  # noqa: E731
+    return {"median_us": statistics.median(ts), "p10_us": q(0.1), "p90_us": q(0.9), "n": len(ts)}
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out_dir")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--kernel-stats")
+    args = ap.parse_args()
+    out = Path(args.out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    path = out / "r08_net.json"
+    if args.kernel_stats:
+        res = json.loads(path.read_text())
+        with open(args.kernel_stats) as f:
+            rows = [r for r in csv.DictReader(f) if "net_" in r.get("Name", "")]
+        res["kernel_stats"] = rows
+        path.write_text(json.dumps(res, indent=1))
+        print(json.dumps(rows))
+        return
+    cfg = CONFIGS["a"]
+    m = dims(cfg)
+    k = cfg["n_samples"]
+    sd = make_weights(cfg, 11)
+    net = FusedAlphaTensor.from_state_dict(sd, k, device=DEV)
+    ref = Ref(sd, cfg, device=DEV, dtype=torch.float32)
+    res = {"config": m, "k": k, "fp32_peak_flops": FP32_PEAK, "sizes": []}
+    for B in (256, 1024, 4096):
+        xx, ss = make_inputs(cfg, B, B)
+        xx = torch.from_numpy(xx).to(DEV).float()
+        ss = torch.from_numpy(ss).to(DEV)
+        fused = lambda: net.fwd_infer(xx, ss, seed=1)  # noqa: E731
+        eager = lambda: ref.fwd_infer(xx, ss, k)  # noqa: E731
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                fused()
+                if not args.fused_only:
+                    eager()
+            torch.cuda.synchronize()
+            tf, te = [], []
+            for _ in range(args.reps):
+                tf.append(timed(fused))
+                if not args.fused_only:
+                    te.append(timed(eager))
+        f = flops(m, B, k)
+        row = {"B": B, "fused": stats(tf), "flops": f,
+               "fused_share_of_fp32_peak": f / (statistics.median(tf) * 1e-6) / FP32_PEAK}
+        if te:
+            row["eager_restatement_fp32"] = stats(te)
+            row["eager_over_fused"] = statistics.median(te) / statistics.median(tf)
+        res["sizes"].append(row)
+        print(json.dumps(row), flush=True)
+    if not args.fused_only:
+        B, S, T = 4096, 4, cfg["dim_t"]
+        start = torch.from_numpy(np.random.default_rng(0).integers(-1, 2, size=(B, T, S, S, S)).astype(np.int8)).to(DEV)
+        n_sim, max_actions = 16, 4
+        pol = net.policy(seed=3)
+        first = [0]
+
+        def counted(frames, scalars, games):
+            first[0] += int(games.shape[0] == B)
+            return pol(frames, scalars, games)
+
+        search.actor_prediction(counted, start, 1, n_sim=2, n_bar=100, n_logits=3, k=k)  # warm-up
+        first[0] = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        search.actor_prediction(counted, start, max_actions, n_sim=n_sim, n_bar=100, n_logits=3, k=k)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        res["self_play"] = {"B": B, "S": S, "k": k, "n_sim": n_sim, "max_actions": max_actions,
+                            "simulations": first[0], "us_per_simulation": wall * 1e6 / max(1, first[0]),
+                            "search_only_us_per_simulation_r06": 122}
+        print(json.dumps(res["self_play"]), flush=True)
+    res["device"] = torch.cuda.get_device_name(0)
+    res["command"] = " ".join(sys.argv)
+    if not args.fused_only:
+        path.write_text(json.dumps(res, indent=1))
+        print(f"wrote {path}")
+
+
+if __name__ == "__main__":
+    main()
