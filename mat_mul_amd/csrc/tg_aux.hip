@@ -8,8 +8,7 @@
 #include "../../include/tensor_game.h"
 #include "tg_device.h"
 #include "tg_emit.h"
-
-int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
+#include "tg_host.h"
 
 namespace tg {
 
@@ -359,22 +358,6 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const int8_t* state, int32
 
 }  // namespace tg
 
-namespace {
-int launched(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
-}
-unsigned grid_for(int64_t blocks, int64_t cap) {
-  return static_cast<unsigned>(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-int check_state(const char* fn, int64_t B, int S, int64_t stride) {
-  if (B < 0 || S < 1 || S > TG_MAX_S || stride < (int64_t)S * S * S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: bad B/S/stride", fn);
-  return TG_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int tg_emit_frames(const int8_t* ring, void* out, float* scalars, int out_dtype, int64_t B, int S,
@@ -389,16 +372,14 @@ int tg_emit_frames(const int8_t* ring, void* out, float* scalars, int out_dtype,
   if (B == 0) return TG_OK;
   if (!ring || !out) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
   const int N = S * S * S;
-  if (reinterpret_cast<uintptr_t>(out) & 15) return tg_internal_fail(TG_ERR_INVALID, "%s: out must be 16-byte aligned", fn);
+  if (!aligned(out, 16)) return tg_internal_fail(TG_ERR_INVALID, "%s: out must be 16-byte aligned", fn);
   // dword loads need 4-byte aligned frames
   if (out_dtype < 0 || out_dtype > 2) return tg_internal_fail(TG_ERR_INVALID, "%s: out_dtype must be 0 (f32), 1 (f16) or 2 (bf16)", fn);
   const int per = out_dtype ? 8 : 4;
-  const int vec16 = (reinterpret_cast<uintptr_t>(ring) % 4) == 0 && frame_stride_bytes % 4 == 0 &&
-                    game_stride_bytes % 4 == 0;
+  const int vec16 = aligned(ring, 4) && frame_stride_bytes % 4 == 0 && game_stride_bytes % 4 == 0;
   const int64_t work = (B * T * N + per - 1) / per;
-  const dim3 grid(grid_for((work + tg::kBlock - 1) / tg::kBlock, 32768)), block(tg::kBlock);
+  const unsigned grid = grid_for((work + tg::kBlock - 1) / tg::kBlock, 32768);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
   const int64_t total = B * T * N;
   // outputs the Infinity Cache can hold stay there for their reader (tools measurement on expand's children: nt stores
   // of a 34 MB output speed the producer up and slow the consumer down by the same amount)
@@ -407,23 +388,19 @@ int tg_emit_frames(const int8_t* ring, void* out, float* scalars, int out_dtype,
     // (the 32-bit loop variable passes `total` by at most one grid stride, 2^26 elements: no wrap)
     const uint32_t mN = static_cast<uint32_t>(((1ull << 32) + N - 1) / N);
     const uint32_t mT = T > 1 ? static_cast<uint32_t>(((1ull << 32) + T - 1) / T) : 0u;
-#define TG_EMIT_FAST(OutT_, NT_)                                                                                        \
-  hipLaunchKernelGGL((tg::emit_frames_fast_kernel<OutT_, NT_>), grid, block, 0, st, ring, static_cast<OutT_*>(out), scalars, \
-                     static_cast<int>(B), N, T, head_slot, t_step, frame_stride_bytes, game_stride_bytes, mN, mT)
-    if (out_dtype == 1) { if (nt) TG_EMIT_FAST(__half, true); else TG_EMIT_FAST(__half, false); }
-    else if (out_dtype == 2) { if (nt) TG_EMIT_FAST(__hip_bfloat16, true); else TG_EMIT_FAST(__hip_bfloat16, false); }
-    else { if (nt) TG_EMIT_FAST(float, true); else TG_EMIT_FAST(float, false); }
-#undef TG_EMIT_FAST
-    return launched(fn);
+    return with_out_type(out_dtype, [&](auto t) {
+      using OutT = decltype(t);
+      auto k = nt ? tg::emit_frames_fast_kernel<OutT, true> : tg::emit_frames_fast_kernel<OutT, false>;
+      return launch(fn, k, grid, tg::kBlock, 0, st, ring, static_cast<OutT*>(out), scalars, static_cast<int>(B), N, T,
+                    head_slot, t_step, frame_stride_bytes, game_stride_bytes, mN, mT);
+    });
   }
-#define TG_EMIT(OutT_, NT_)                                                                                              \
-  hipLaunchKernelGGL((tg::emit_frames_kernel<OutT_, NT_>), grid, block, 0, st, ring, static_cast<OutT_*>(out), scalars, B, N, \
-                     T, head_slot, t_step, frame_stride_bytes, game_stride_bytes, vec16)
-  if (out_dtype == 1) { if (nt) TG_EMIT(__half, true); else TG_EMIT(__half, false); }
-  else if (out_dtype == 2) { if (nt) TG_EMIT(__hip_bfloat16, true); else TG_EMIT(__hip_bfloat16, false); }
-  else { if (nt) TG_EMIT(float, true); else TG_EMIT(float, false); }
-#undef TG_EMIT
-  return launched(fn);
+  return with_out_type(out_dtype, [&](auto t) {
+    using OutT = decltype(t);
+    auto k = nt ? tg::emit_frames_kernel<OutT, true> : tg::emit_frames_kernel<OutT, false>;
+    return launch(fn, k, grid, tg::kBlock, 0, st, ring, static_cast<OutT*>(out), scalars, B, N, T, head_slot, t_step,
+                  frame_stride_bytes, game_stride_bytes, vec16);
+  });
 }
 
 // the key pass of tg_expand_keyed_i8 for the kernel families that do not produce the keys themselves (tg_kernels.hip)
@@ -438,17 +415,15 @@ int tg_hash_u64(const int8_t* state, uint64_t* hash_out, int64_t B, int S, int64
   if (B == 0) return TG_OK;
   if (!state || !hash_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
   const int N = S * S * S;
-  const int vec16 = (reinterpret_cast<uintptr_t>(state) & 15) == 0 && game_stride_bytes % 16 == 0;
+  const int vec16 = aligned(state, 16) && game_stride_bytes % 16 == 0;
   int lpg = 1;
   // lanes per game: up to four 16-byte chunks per lane for games of 16 chunks and more (S=9: 16 lanes x 3 chunks, four
   // games per wavefront -- with a wavefront per game 46 lanes did one load each and the launch was latency-bound:
   // 12-16 us for 24 MB), one chunk per lane for the small ones (S=4: 4 lanes)
   while (lpg < 64 && lpg * 16 * (N >= 256 ? 4 : 1) < N) lpg <<= 1;
   const int64_t blocks = (B * lpg + tg::kBlock - 1) / tg::kBlock;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::hash_kernel, dim3(grid_for(blocks, 8192)), dim3(tg::kBlock), 0,
-                     static_cast<hipStream_t>(stream), state, hash_out, B, N, game_stride_bytes, vec16, lpg);
-  return launched(fn);
+  return launch(fn, tg::hash_kernel, dim3(grid_for(blocks, 8192)), tg::kBlock, 0, static_cast<hipStream_t>(stream), state,
+                hash_out, B, N, game_stride_bytes, vec16, lpg);
 }
 
 int tg_seen_u64(const uint64_t* keys, uint64_t* table, int64_t capacity, uint8_t* fresh, const uint8_t* mask,
@@ -458,18 +433,17 @@ int tg_seen_u64(const uint64_t* keys, uint64_t* table, int64_t capacity, uint8_t
   if (capacity < 2 || (capacity & (capacity - 1)) != 0)
     return tg_internal_fail(TG_ERR_INVALID, "%s: capacity=%lld must be a power of two >= 2", fn, (long long)capacity);
   if (!table) return tg_internal_fail(TG_ERR_INVALID, "%s: null table", fn);
-  if ((reinterpret_cast<uintptr_t>(table) & 7) || (reinterpret_cast<uintptr_t>(keys) & 7))
+  if (!aligned(table, 8) || !aligned(keys, 8))
     return tg_internal_fail(TG_ERR_INVALID, "%s: keys and table must be 8-byte aligned", fn);
   if (n == 0) return TG_OK;
   if (!keys || (!fresh && !insert)) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(grid_for((n + tg::kBlock - 1) / tg::kBlock, 8192)), block(tg::kBlock);
-  (void)hipGetLastError();
+  const dim3 grid(grid_for((n + tg::kBlock - 1) / tg::kBlock, 8192));
+  const uint64_t slot_mask = static_cast<uint64_t>(capacity - 1);
   if (fresh)
-    hipLaunchKernelGGL(tg::seen_lookup_kernel, grid, block, 0, st, keys, table, static_cast<uint64_t>(capacity - 1), fresh, mask, n);
-  if (insert)
-    hipLaunchKernelGGL(tg::seen_insert_kernel, grid, block, 0, st, keys, table, static_cast<uint64_t>(capacity - 1), mask, n, status);
-  return launched(fn);
+    if (int rc = launch(fn, tg::seen_lookup_kernel, grid, tg::kBlock, 0, st, keys, table, slot_mask, fresh, mask, n)) return rc;
+  if (insert) return launch(fn, tg::seen_insert_kernel, grid, tg::kBlock, 0, st, keys, table, slot_mask, mask, n, status);
+  return TG_OK;
 }
 
 int tg_rank_i32(const int8_t* state, int32_t* rank_out, int64_t B, int S, int64_t game_stride_bytes,
@@ -478,17 +452,10 @@ int tg_rank_i32(const int8_t* state, int32_t* rank_out, int64_t B, int S, int64_
   if (int rc = check_state(fn, B, S, game_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!state || !rank_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
-  const dim3 grid(grid_for(S == 4 ? (B + 3) / 4 : B, 1 << 20)), block(tg::kBlock);  // (S = 4: a wavefront per game)
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
-  switch (S) {
-    case 4: hipLaunchKernelGGL(tg::rank_kernel<4>, grid, block, 0, st, state, rank_out, B, S, game_stride_bytes); break;
-    case 9: hipLaunchKernelGGL(tg::rank_kernel<9>, grid, block, 0, st, state, rank_out, B, S, game_stride_bytes); break;
-    case 16: hipLaunchKernelGGL(tg::rank_kernel<16>, grid, block, 0, st, state, rank_out, B, S, game_stride_bytes); break;
-    case 25: hipLaunchKernelGGL(tg::rank_kernel<25>, grid, block, 0, st, state, rank_out, B, S, game_stride_bytes); break;
-    default: hipLaunchKernelGGL(tg::rank_kernel<0>, grid, block, 0, st, state, rank_out, B, S, game_stride_bytes); break;
-  }
-  return launched(fn);
+  const unsigned grid = grid_for(S == 4 ? (B + 3) / 4 : B, 1 << 20);  // (S = 4: a wavefront per game)
+  auto k = S == 4 ? tg::rank_kernel<4> : S == 9 ? tg::rank_kernel<9> : S == 16 ? tg::rank_kernel<16>
+         : S == 25 ? tg::rank_kernel<25> : tg::rank_kernel<0>;
+  return launch(fn, k, grid, tg::kBlock, 0, static_cast<hipStream_t>(stream), state, rank_out, B, S, game_stride_bytes);
 }
 
 }  // extern "C"

@@ -8,19 +8,12 @@
 // rank-1 terms of the EMITTED tokens.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
 #include "../../include/tensor_game.h"
 #include "tg_device.h"
-
-int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
-namespace tg { struct Dist; }
-// the generator in one kernel (tg_genfused.h, launched from tg_kernels.hip): 1 = launched, 0 = not applicable
-int tg_internal_gen_fused(int8_t* target, int8_t* actions, uint8_t* overflow, const int8_t* basis, int64_t B, int S,
-                          int R, const tg::Dist& D, int shift, uint64_t seed, uint64_t gid0, int64_t stride,
-                          hipStream_t st);
+#include "tg_host.h"
 
 namespace tg {
 
@@ -799,15 +792,28 @@ int make_dist(const char* fn, const uint32_t* thresholds, const int8_t* values, 
   return TG_OK;
 }
 
-int launched(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
+// The token kernel of tg_gen_demos_i8 with M vectors per lane.
+template <int ST, int M>
+int launch_tokens(const char* fn, int8_t* actions_out, uint8_t* overflow, int64_t B, int S, int R, const tg::Dist& D,
+                  int shift, uint64_t seed, uint64_t game_id_offset, hipStream_t st) {
+  const int64_t nvec = B * R * 3;
+  const int64_t wgs = (nvec + tg::kBlock * M - 1) / (tg::kBlock * M);
+  const int vec16 = aligned(actions_out, 16);
+  return launch(fn, (tg::gen_tokens_kernel<ST, M>), dim3(grid_for(wgs > 16384 ? 16384 : wgs)), tg::kBlock, 0, st,
+                actions_out, overflow, B, S, R, D, shift, seed, game_id_offset, nullptr, vec16);
 }
 
-unsigned grid_for(int64_t blocks) {
-  const int64_t cap = 1 << 20;
-  return static_cast<unsigned>(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+// The change of basis on the matrix cores (NW wavefronts per workgroup) and in the vector form (CB threads).
+template <int S, int NW, typename... A>
+int change_basis_mfma(const char* fn, dim3 grid, hipStream_t st, const A&... args) {
+  constexpr int ldsb = tg::CBGeo<S>::LDS_BYTES;
+  if (int rc = lds_opt_in<tg::change_basis_mfma_kernel<S, NW>>(fn, ldsb)) return rc;
+  return launch(fn, tg::change_basis_mfma_kernel<S, NW>, grid, 64 * NW, ldsb, st, args...);
+}
+template <int S, int CB, typename... A>
+int change_basis(const char* fn, unsigned grid, size_t lds, hipStream_t st, const A&... args) {
+  if (int rc = lds_opt_in<tg::change_basis_kernel<S, CB>>(fn, lds)) return rc;
+  return launch(fn, tg::change_basis_kernel<S, CB>, grid, CB, lds, st, args...);
 }
 
 }  // namespace
@@ -819,8 +825,7 @@ int tg_gen_demos_i8(int8_t* target_out, int8_t* actions_out, uint8_t* overflow, 
                     int shift, uint64_t seed, uint64_t game_id_offset, const int8_t* basis,
                     int64_t game_stride_bytes, tg_stream_t stream) {
   const char* fn = "tg_gen_demos_i8";
-  if (B < 0 || S < 1 || S > TG_MAX_S || game_stride_bytes < (int64_t)S * S * S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: bad B/S/stride", fn);
+  if (int rc = check_state(fn, B, S, game_stride_bytes)) return rc;
   if (R < 1 || R > 4096) return tg_internal_fail(TG_ERR_INVALID, "%s: R=%d outside [1,4096]", fn, R);
   tg::Dist D;
   if (int rc = make_dist(fn, thresholds, values, n_values, &D)) return rc;
@@ -833,48 +838,47 @@ int tg_gen_demos_i8(int8_t* target_out, int8_t* actions_out, uint8_t* overflow, 
     return rc < 0 ? rc : TG_OK;
   // otherwise: tokens (+ change of basis on the tokens), then the accumulation of tg_gen_from_factors_i8
   const int64_t nvec = B * R * 3;
-  const int vec16 = (reinterpret_cast<uintptr_t>(actions_out) & 15) == 0;
-  (void)hipGetLastError();
-#define TG_GT(ST, M)                                                                                      \
-  do {                                                                                                    \
-    const int64_t wgs = (nvec + tg::kBlock * M - 1) / (tg::kBlock * M);                                   \
-    hipLaunchKernelGGL((tg::gen_tokens_kernel<ST, M>), dim3(grid_for(wgs > 16384 ? 16384 : wgs)),        \
-                       dim3(tg::kBlock), 0, st, actions_out, overflow, B, S, R, D, shift, seed,           \
-                       game_id_offset, nullptr, vec16);                                                     \
-  } while (0)
+  auto tokens = [&](auto launcher) {
+    return launcher(fn, actions_out, overflow, B, S, R, D, shift, seed, game_id_offset, st);
+  };
+  int rc;
   switch (S) {
     case 4:  // 24 % of the draws are rejected: several vectors per lane, as long as the chip stays full
-      if (nvec >= (int64_t)tg::kBlock * 16 * 2048) TG_GT(4, 16);
-      else if (nvec >= (int64_t)tg::kBlock * 4 * 1024) TG_GT(4, 4);
-      else TG_GT(4, 1);
+      if (nvec >= (int64_t)tg::kBlock * 16 * 2048) rc = tokens(launch_tokens<4, 16>);
+      else if (nvec >= (int64_t)tg::kBlock * 4 * 1024) rc = tokens(launch_tokens<4, 4>);
+      else rc = tokens(launch_tokens<4, 1>);
       break;
     case 9:  // 4 %
-      if (nvec >= (int64_t)tg::kBlock * 4 * 2048) TG_GT(9, 4);
-      else TG_GT(9, 1);
+      if (nvec >= (int64_t)tg::kBlock * 4 * 2048) rc = tokens(launch_tokens<9, 4>);
+      else rc = tokens(launch_tokens<9, 1>);
       break;
-    case 16: TG_GT(16, 1); break;
-    case 25: TG_GT(25, 1); break;
-    default: TG_GT(0, 1); break;
+    case 16: rc = tokens(launch_tokens<16, 1>); break;
+    case 25: rc = tokens(launch_tokens<25, 1>); break;
+    default: rc = tokens(launch_tokens<0, 1>); break;
   }
-#undef TG_GT
+  if (rc) return rc;
   if (basis) {
     const size_t lds = 3 * static_cast<size_t>(S) * S * sizeof(int) + 64 * 3 * static_cast<size_t>(S);
-    const dim3 bgrid(grid_for(B > 16384 ? 16384 : B)), bblock(192);
     const bool no_mfma = TG_SWITCH("TG_NO_MFMA");  // A/B switch for measurements
+    const dim3 bgrid(grid_for(B > 16384 ? 16384 : B)), bblock(192);
     const int mjob = 3 * ((R + 31) / 32);
     const dim3 mgrid(grid_for(B > 65536 ? 65536 : B)), mblock(64 * (mjob < 8 ? mjob : 8));
+    auto mfma = [&](auto kernel) { return launch(fn, kernel, mgrid, mblock, 0, st, actions_out, overflow, B, R, shift, basis); };
+    auto vector = [&](auto kernel) {
+      return launch(fn, kernel, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis);
+    };
     switch (no_mfma ? -S : S) {
-      case 9: hipLaunchKernelGGL(tg::basis_tokens_mfma_kernel<9>, mgrid, mblock, 0, st, actions_out, overflow, B, R, shift, basis); break;
-      case 16: hipLaunchKernelGGL(tg::basis_tokens_mfma_kernel<16>, mgrid, mblock, 0, st, actions_out, overflow, B, R, shift, basis); break;
-      case 25: hipLaunchKernelGGL(tg::basis_tokens_mfma_kernel<25>, mgrid, mblock, 0, st, actions_out, overflow, B, R, shift, basis); break;
-      case 4: hipLaunchKernelGGL(tg::basis_tokens_kernel<4>, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis); break;
-      case -9: hipLaunchKernelGGL(tg::basis_tokens_kernel<9>, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis); break;
-      case -16: hipLaunchKernelGGL(tg::basis_tokens_kernel<16>, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis); break;
-      case -25: hipLaunchKernelGGL(tg::basis_tokens_kernel<25>, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis); break;
-      default: hipLaunchKernelGGL(tg::basis_tokens_kernel<0>, bgrid, bblock, lds, st, actions_out, overflow, B, S, R, shift, basis); break;
+      case 9: rc = mfma(tg::basis_tokens_mfma_kernel<9>); break;
+      case 16: rc = mfma(tg::basis_tokens_mfma_kernel<16>); break;
+      case 25: rc = mfma(tg::basis_tokens_mfma_kernel<25>); break;
+      case 4: rc = vector(tg::basis_tokens_kernel<4>); break;
+      case -9: rc = vector(tg::basis_tokens_kernel<9>); break;
+      case -16: rc = vector(tg::basis_tokens_kernel<16>); break;
+      case -25: rc = vector(tg::basis_tokens_kernel<25>); break;
+      default: rc = vector(tg::basis_tokens_kernel<0>); break;
     }
+    if (rc) return rc;
   }
-  if (int rc = launched(fn)) return rc;
   return tg_gen_from_factors_i8(actions_out, target_out, overflow, B, S, R, game_stride_bytes, shift, stream);
 }
 
@@ -895,82 +899,44 @@ int tg_sample_basis_i8(int8_t* basis_out, int8_t* lower_out, int8_t* upper_out, 
   if (B == 0) return TG_OK;
   if (!basis_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
   const bool no_mfma = TG_SWITCH("TG_NO_MFMA");  // A/B switch for measurements
-  (void)hipGetLastError();
-  if (!no_mfma)  // one wavefront per matrix, four per workgroup
-    hipLaunchKernelGGL(tg::sample_basis_mfma_kernel, dim3(grid_for((3 * B + 3) / 4)), dim3(tg::kBlock), 0,
-                       static_cast<hipStream_t>(stream), basis_out, lower_out, upper_out, B, S, D, seed, game_id_offset);
-  else
-    hipLaunchKernelGGL(tg::sample_basis_kernel, dim3(grid_for(3 * B)), dim3(tg::kBlock), 0,
-                       static_cast<hipStream_t>(stream), basis_out, lower_out, upper_out, B, S, D, seed,
-                       game_id_offset);
-  return launched(fn);
+  // the MFMA kernel: one wavefront per matrix, four per workgroup
+  return launch(fn, no_mfma ? tg::sample_basis_kernel : tg::sample_basis_mfma_kernel,
+                grid_for(no_mfma ? 3 * B : (3 * B + 3) / 4), tg::kBlock, 0, static_cast<hipStream_t>(stream), basis_out,
+                lower_out, upper_out, B, S, D, seed, game_id_offset);
 }
 
 int tg_change_basis_i8(const int8_t* state_in, const int32_t* basis, int8_t* state_out,
                        uint8_t* overflow, int64_t B, int S, int64_t game_stride_bytes,
                        tg_stream_t stream) {
   const char* fn = "tg_change_basis_i8";
-  if (B < 0 || S < 1 || S > TG_MAX_S || game_stride_bytes < (int64_t)S * S * S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: bad B/S/stride", fn);
+  if (int rc = check_state(fn, B, S, game_stride_bytes)) return rc;
   if (B && state_in && state_in == state_out) return tg_internal_fail(TG_ERR_INVALID, "%s: in-place is not supported", fn);
   if (B == 0) return TG_OK;
   if (!state_in || !basis || !state_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null pointer", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // S = 9 / 16 / 25 on aligned layouts: the matrix-core kernel (games it cannot do exactly take the vector form inside it)
-  if (!TG_SWITCH("TG_NO_MFMA") && (S == 9 || S == 16 || S == 25) && (reinterpret_cast<uintptr_t>(state_in) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(state_out) & 15) == 0 && game_stride_bytes % 16 == 0) {
-    static std::atomic<unsigned> attr_set[3][64];  // per (S, device): the > 64 KiB dynamic LDS opt-in, once
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  if (!TG_SWITCH("TG_NO_MFMA") && (S == 9 || S == 16 || S == 25) && aligned(state_in, 16) && aligned(state_out, 16) &&
+      game_stride_bytes % 16 == 0) {
+    const int cus = device_cu_count();
     const dim3 mgrid(grid_for(B > 4LL * cus ? 4LL * cus : B));
-#define TG_CBM(S_, IDX_, NW_)                                                                                  \
-  do {                                                                                                         \
-    constexpr int ldsb = tg::CBGeo<S_>::LDS_BYTES;                                                             \
-    if (ldsb > 64 * 1024 && !attr_set[IDX_][dev].load(std::memory_order_relaxed)) {                            \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tg::change_basis_mfma_kernel<S_, NW_>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);                    \
-      if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));            \
-      attr_set[IDX_][dev].store(1, std::memory_order_relaxed);                                                 \
-    }                                                                                                          \
-    (void)hipGetLastError();                                                                                   \
-    hipLaunchKernelGGL((tg::change_basis_mfma_kernel<S_, NW_>), mgrid, dim3(64 * NW_), ldsb, st, state_in, basis, state_out, \
-                       overflow, B, game_stride_bytes);                                                        \
-    return launched(fn);                                                                                       \
-  } while (0)
-    if (S == 9) TG_CBM(9, 0, 4);
-    if (S == 16) TG_CBM(16, 1, 4);
-    TG_CBM(25, 2, 8);
-#undef TG_CBM
+    if (S == 9) return change_basis_mfma<9, 4>(fn, mgrid, st, state_in, basis, state_out, overflow, B, game_stride_bytes);
+    if (S == 16) return change_basis_mfma<16, 4>(fn, mgrid, st, state_in, basis, state_out, overflow, B, game_stride_bytes);
+    return change_basis_mfma<25, 8>(fn, mgrid, st, state_in, basis, state_out, overflow, B, game_stride_bytes);
   }
   // int32 tensor with rows padded to S+1, then one mode's matrix with rows padded to whole 16-byte reads (+ slack
   // for the run-time-S kernel, whose unrolled row loop may read past the last row into zero-weighted entries)
   const size_t lds = ((static_cast<size_t>(S) * S * (S + 1) + 3) / 4 * 4 + static_cast<size_t>(S) * ((S + 3) / 4 * 4) + 32) * sizeof(int);
-  if (lds > 160 * 1024) return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: S=%d needs %zu B of LDS", fn, S, lds);
-  const dim3 grid(grid_for(B));
-#define TG_CB(ST, CB)                                                                                  \
-  do {                                                                                                 \
-    if (lds > 64 * 1024) {                                                                             \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tg::change_basis_kernel<ST, CB>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-      if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));    \
-    }                                                                                                  \
-    (void)hipGetLastError(); hipLaunchKernelGGL((tg::change_basis_kernel<ST, CB>), grid, dim3(CB), lds, st, state_in, basis, state_out,  \
-                       overflow, B, S, game_stride_bytes);                                             \
-  } while (0)
+  if (lds > tg::kMaxDynamicLds) return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: S=%d needs %zu B of LDS", fn, S, lds);
+  const unsigned grid = grid_for(B);
   switch (S) {
-    case 4: TG_CB(4, 256); break;
-    case 9: TG_CB(9, 256); break;
-    case 16: TG_CB(16, 256); break;
-    case 25: TG_CB(25, 1024); break;
+    case 4: return change_basis<4, 256>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
+    case 9: return change_basis<9, 256>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
+    case 16: return change_basis<16, 256>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
+    case 25: return change_basis<25, 1024>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
     default:
-      if (S > 16) TG_CB(0, 1024);
-      else TG_CB(0, 256);
-      break;
+      if (S > 16) return change_basis<0, 1024>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
+      return change_basis<0, 256>(fn, grid, lds, st, state_in, basis, state_out, overflow, B, S, game_stride_bytes);
   }
-#undef TG_CB
-  return launched(fn);
 }
 
 }  // extern "C"

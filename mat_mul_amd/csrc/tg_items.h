@@ -20,12 +20,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
+#include "../../include/tensor_game_demos.h"
 #include "tg_device.h"
 #include "tg_emit.h"
-
-int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
+#include "tg_host.h"
 
 namespace tg {
 
@@ -387,57 +385,14 @@ __global__ __launch_bounds__(kBlock) void items_mfma_kernel(ItemArgs a, X... x) 
 
 }  // namespace tg
 
-// (an anonymous namespace: every translation unit that includes this keeps its own occupancy caches)
 namespace {
-
-constexpr int kMaxDevices = 64;
-
-int items_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -1;
-  return dev;
-}
-
-// CU count of the current device (256 on MI355X), cached per device with relaxed atomics (tensor_game.h)
-int items_cu_count() {
-  static std::atomic<int> cached[kMaxDevices];
-  const int dev = items_device();
-  if (dev < 0) return 256;
-  int n = cached[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    cached[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-// workgroups of `kernel` per CU at `lds` bytes of dynamic LDS, cached per (instantiation, device, lds); a host-side
-// calculation, legal during stream capture
-template <typename K>
-int items_per_cu(K kernel, int lds, std::atomic<uint64_t> (&slots)[kMaxDevices]) {
-  const int dev = items_device();
-  const uint64_t tag = (static_cast<uint64_t>(lds) + 1) << 32;
-  if (dev >= 0) {
-    const uint64_t c = slots[dev].load(std::memory_order_relaxed);
-    if ((c & ~0xffffffffull) == tag) return static_cast<int>(c & 0xffffffffull);
-  }
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, tg::kBlock, lds) != hipSuccess || n < 1) n = 1;
-  (void)hipGetLastError();
-  if (dev >= 0) slots[dev].store(tag | static_cast<uint32_t>(n), std::memory_order_relaxed);
-  return n;
-}
 
 template <typename K, typename... X>
 int launch_items(K kernel, const char* fn, const tg::ItemArgs& a, int64_t items, int lds, int per_cu, hipStream_t st,
                  const X&... x) {
-  const int64_t resident = static_cast<int64_t>(per_cu) * items_cu_count();
+  const int64_t resident = static_cast<int64_t>(per_cu) * device_cu_count();
   const int64_t grid = items < resident ? items : resident;  // several items per workgroup beyond one wave of them
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(tg::kBlock), lds, st, a, x...);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
+  return launch(fn, kernel, static_cast<unsigned>(grid), tg::kBlock, lds, st, a, x...);
 }
 
 // The per-size kernel choice of every items entry.  Kn names the entry (kName) and its __global__ instantiations
@@ -447,7 +402,7 @@ int dispatch_items(const tg::ItemArgs& a0, hipStream_t st, const X&... x) {
   tg::ItemArgs a = a0;
   const int S = a.S;
   if (S == 4) {
-    a.vec = (reinterpret_cast<uintptr_t>(a.frames) & 15) == 0;
+    a.vec = aligned(a.frames, 16);
     const double fmax = 128.0 + (a.shift < 0 ? -static_cast<double>(a.shift) : a.shift);
     const bool narrow = (a.R - 1) * fmax * fmax * fmax + 128.0 < 2147483647.0;
     const int64_t wgs = (a.N + tg::kBlock / 16 - 1) / (tg::kBlock / 16);
@@ -456,22 +411,57 @@ int dispatch_items(const tg::ItemArgs& a0, hipStream_t st, const X&... x) {
   }
   if ((S == 16 || S == 25) && a.R <= 256) {
     a.RS = ((a.R - 1 + 31) & ~31) + 16;
-    a.vec = (reinterpret_cast<uintptr_t>(a.targets) & 15) == 0 && a.tstride % 16 == 0;
-#define TG_ITEMS_MFMA(S_)                                                                         \
-  do {                                                                                            \
-    static std::atomic<uint64_t> occ[kMaxDevices];                                                \
-    const int lds = tg::items_mfma_lds_bytes<S_>(a.RS);                                           \
-    return launch_items(Kn::template mfma<S_, OutT>(), Kn::kName, a, a.N, lds,                   \
-                        items_per_cu(Kn::template mfma<S_, OutT>(), lds, occ), st, x...);         \
-  } while (0)
-    if (S == 16) TG_ITEMS_MFMA(16);
-    TG_ITEMS_MFMA(25);
-#undef TG_ITEMS_MFMA
+    a.vec = aligned(a.targets, 16) && a.tstride % 16 == 0;
+    if (S == 16) {
+      constexpr auto k = Kn::template mfma<16, OutT>();
+      const int lds = tg::items_mfma_lds_bytes<16>(a.RS);
+      return launch_items(k, Kn::kName, a, a.N, lds, resident_per_cu<k>(lds), st, x...);
+    }
+    constexpr auto k = Kn::template mfma<25, OutT>();
+    const int lds = tg::items_mfma_lds_bytes<25>(a.RS);
+    return launch_items(k, Kn::kName, a, a.N, lds, resident_per_cu<k>(lds), st, x...);
   }
-  static std::atomic<uint64_t> occ[kMaxDevices];
+  constexpr auto k = Kn::template exact<OutT>();
   const int lds = (S * S * S + 15) & ~15;
-  return launch_items(Kn::template exact<OutT>(), Kn::kName, a, a.N, lds,
-                      items_per_cu(Kn::template exact<OutT>(), lds, occ), st, x...);
+  return launch_items(k, Kn::kName, a, a.N, lds, resident_per_cu<k>(lds), st, x...);
+}
+
+// An items entry after its own checks: the checks on the item list and the output, then the launch in the output dtype.
+template <typename Kn, typename... X>
+int run_items(const tg::ItemArgs& a, int out_dtype, hipStream_t st, const X&... x) {
+  const char* fn = Kn::kName;
+  const int64_t N3 = static_cast<int64_t>(a.S) * a.S * a.S;
+  if (a.N < 0 || a.N > INT64_MAX / (a.T * N3))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: N=%lld out of range", fn, (long long)a.N);
+  if (a.N == 0) return TG_OK;
+  if (!a.idx || !a.frames) return tg_internal_fail(TG_ERR_INVALID, "%s: null item_idx or frames_out", fn);
+  if (a.n_demos > 0 && (!a.tokens || !a.targets)) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens or targets", fn);
+  const int esize = out_dtype == 3 ? 1 : out_dtype == 0 ? 4 : 2;
+  if (!aligned(a.frames, esize))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_out not aligned to its %d-byte elements", fn, esize);
+  switch (out_dtype) {
+    case 0: return dispatch_items<float, Kn>(a, st, x...);
+    case 1: return dispatch_items<__half, Kn>(a, st, x...);
+    case 2: return dispatch_items<__hip_bfloat16, Kn>(a, st, x...);
+    default: return dispatch_items<int8_t, Kn>(a, st, x...);
+  }
+}
+
+// The checks every items entry makes first: the demonstration set and the item shape.
+int check_items(const char* fn, int64_t n_demos, int R, int S, int64_t target_stride_bytes, int T, int out_dtype) {
+  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
+  if (R < 1 || R > TG_DEMO_MAX_ACTIONS)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: R=%d outside [1,%d]", fn, R, TG_DEMO_MAX_ACTIONS);
+  if (T < 1 || T > TG_DEMO_MAX_T) return tg_internal_fail(TG_ERR_INVALID, "%s: T=%d outside [1,%d]", fn, T, TG_DEMO_MAX_T);
+  if (n_demos < 0 || n_demos > INT64_MAX / R)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: n_demos=%lld out of range", fn, (long long)n_demos);
+  const int64_t N3 = static_cast<int64_t>(S) * S * S;
+  if (target_stride_bytes < N3)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: target_stride_bytes=%lld < S^3=%lld", fn, (long long)target_stride_bytes,
+                            (long long)N3);
+  if (out_dtype < 0 || out_dtype > 3)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: out_dtype=%d (0 f32, 1 f16, 2 bf16, 3 int8)", fn, out_dtype);
+  return TG_OK;
 }
 
 }  // namespace

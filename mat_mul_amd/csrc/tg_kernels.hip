@@ -28,6 +28,7 @@
 
 #include "../../include/tensor_game.h"
 #include "tg_device.h"
+#include "tg_host.h"
 
 namespace tg {
 
@@ -2375,7 +2376,7 @@ __global__ __launch_bounds__(kBlock) void copy_bytes_kernel(const int8_t* src, i
 // =============================================================================================
 static thread_local char g_err[512] = "";
 
-// shared with tg_gen.hip (same library); not part of the C ABI
+// every source of the library reports through this (tg_host.h); not part of the C ABI
 int tg_internal_fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -2387,69 +2388,49 @@ int tg_internal_fail(int code, const char* fmt, ...) {
 
 namespace {
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return TG_OK;
+// One launch of the packed int16 kernels (tg_packed.h) or the row kernels (tg_rows.h): GPB games per workgroup, the
+// actions in LDS tiles of up to ATILE.
+template <int S, int TS, int MODE, bool... F>
+int launch_packed(const char* fn, const tg::ApplyArgs& a, int flim, hipStream_t st) {
+  using G = tg::PGeo<S, TS>;
+  const int64_t blocks = (a.B + G::GPB - 1) / G::GPB;
+  if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
+  const int at = a.nact < G::ATILE ? a.nact : G::ATILE;
+  return launch(fn, tg::packed_kernel<S, TS, MODE, F...>, (unsigned)blocks, tg::kBlock,
+                tg::packed_lds_bytes<S, TS, MODE>(at), st, a, flim, at);
+}
+template <int S, int TS, int MODE>
+int launch_rows(const char* fn, const tg::ApplyArgs& a, int flim, hipStream_t st) {
+  using G = tg::RGeo<S, TS>;
+  const int64_t blocks = (a.B + G::GPB - 1) / G::GPB;
+  if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
+  const int at = a.nact < G::ATILE ? a.nact : G::ATILE;
+  return launch(fn, tg::rows_kernel<S, TS, MODE>, (unsigned)blocks, tg::kBlock, tg::rows_lds_bytes<S, TS, MODE>(at), st,
+                a, flim, at);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-int validate_common(const char* fn, int64_t B, int S, int64_t stride) {
-  if (B < 0) return fail(TG_ERR_INVALID, "%s: B=%lld < 0", fn, (long long)B);
-  if (S < 1 || S > TG_MAX_S) return fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (stride < (int64_t)S * S * S)
-    return fail(TG_ERR_INVALID, "%s: game_stride_bytes=%lld < S^3=%d", fn, (long long)stride, S * S * S);
-  return TG_OK;
+// A workgroup's set-up (tile offsets, staging addresses) is a third of one game's work in the matrix-core kernels: every
+// workgroup takes several games, as many workgroups as the chip holds at once, games split evenly.
+template <auto K>
+int launch_resident(const char* fn, const tg::ApplyArgs& a, int Rp, int ldsb, hipStream_t st) {
+  const int64_t resident = static_cast<int64_t>(resident_per_cu<K>(ldsb)) * device_cu_count();
+  return launch(fn, K, even_grid(a.B, resident), tg::kBlock, ldsb, st, a, Rp);
 }
-
-// Per-device caches of device constants.  Entries are written with relaxed atomics: two host threads racing
-// on a cold entry both query and store the same value.  Nothing else in the library is mutable host state.
-constexpr int kMaxDevices = 64;
-
-int current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -1;
-  return dev;
+template <int S>
+int launch_genf_mfma(const char* fn, const tg::ApplyArgs& a, hipStream_t st) {
+  const int Rp = (a.nact + 31) & ~31;
+  const int ldsb = tg::mfma_lds_bytes<S>(Rp);
+  if (Rp == 32) return launch_resident<tg::genf_mfma_kernel<S, 1>>(fn, a, Rp, ldsb, st);
+  if (Rp == 64) return launch_resident<tg::genf_mfma_kernel<S, 2>>(fn, a, Rp, ldsb, st);
+  return launch_resident<tg::genf_mfma_kernel<S, 0>>(fn, a, Rp, ldsb, st);
 }
-
-int device_cu_count() {  // of the current device; 256 on MI355X
-  static std::atomic<int> cached[kMaxDevices];
-  const int dev = current_device();
-  if (dev < 0) return 256;
-  int n = cached[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    cached[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-// Workgroups of `kernel` one CU holds at `lds` bytes of dynamic LDS, cached per (kernel instantiation, device):
-// the slot packs (lds + 1) << 32 | value, so a different LDS size simply re-queries.  The query is a host-side
-// calculation on the code object (no stream operation), so it is legal while `st` is being captured.
-struct OccupancySlots {
-  std::atomic<uint64_t> v[kMaxDevices];
-};
-template <typename K>
-int resident_per_cu(K kernel, int lds, OccupancySlots& slots) {
-  const int dev = current_device();
-  const uint64_t tag = (static_cast<uint64_t>(lds) + 1) << 32;
-  if (dev >= 0) {
-    const uint64_t c = slots.v[dev].load(std::memory_order_relaxed);
-    if ((c & ~0xffffffffull) == tag) return static_cast<int>(c & 0xffffffffull);
-  }
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, tg::kBlock, lds) != hipSuccess || n < 1) n = 1;
-  (void)hipGetLastError();
-  if (dev >= 0) slots.v[dev].store(tag | static_cast<uint32_t>(n), std::memory_order_relaxed);
-  return n;
-}
-
-unsigned capped_grid(int64_t blocks) {
-  const int64_t cap = 1 << 20;
-  return static_cast<unsigned>(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+template <int S>
+int launch_many_mfma(const char* fn, const tg::ApplyArgs& a, hipStream_t st) {
+  const int Rp = (a.nact + 31) & ~31;
+  const int ldsb = tg::many_mfma_lds_bytes<S>(Rp);
+  if (Rp == 32) return launch_resident<tg::many_mfma_kernel<S, 1>>(fn, a, Rp, ldsb, st);
+  if (Rp == 64) return launch_resident<tg::many_mfma_kernel<S, 2>>(fn, a, Rp, ldsb, st);
+  return launch_resident<tg::many_mfma_kernel<S, 0>>(fn, a, Rp, ldsb, st);
 }
 
 template <int MODE>
@@ -2457,12 +2438,12 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
   using namespace tg;
   ApplyArgs a = a_in;
   if (a.B == 0) return TG_OK;
-  const bool al = (MODE == GENF || (aligned16(a.in) && a.in_stride % 16 == 0)) && aligned16(a.out) &&
+  const bool al = (MODE == GENF || (aligned(a.in, 16) && a.in_stride % 16 == 0)) && aligned(a.out, 16) &&
                   a.out_stride % 16 == 0;
   const int64_t B = a.B;
   if constexpr (MODE == EXPAND)
     a.stream_out = (B * a.nact * a.out_stride >= kStreamOutBytes || TG_SWITCH("TG_EXPAND_NT")) && !TG_SWITCH("TG_EXPAND_NO_NT");
-  if (al && a.S == 4 && aligned4(a.actions) && a.in_stride < (1 << 20) && a.out_stride < (1 << 20)) {
+  if (al && a.S == 4 && aligned(a.actions, 4) && a.in_stride < (1 << 20) && a.out_stride < (1 << 20)) {
     const int64_t blocks = (B * 4 + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
     if constexpr (MODE == EXPAND) {
@@ -2470,20 +2451,16 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
         const int PB = 64 / a.nact, recip = (65536 + a.nact - 1) / a.nact;
         const int64_t eblocks = (B + PB - 1) / PB;
         if (eblocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
-        (void)hipGetLastError();
+        const dim3 grid((unsigned)eblocks);
         if (a.keys) {
-          if (a.stream_out) hipLaunchKernelGGL((s4_expand_kernel<true, true>), dim3((unsigned)eblocks), dim3(kBlock), 0, st, a, PB, recip);
-          else hipLaunchKernelGGL((s4_expand_kernel<false, true>), dim3((unsigned)eblocks), dim3(kBlock), 0, st, a, PB, recip);
           if (keys_fused) *keys_fused = true;
-        } else if (a.stream_out) {
-          hipLaunchKernelGGL((s4_expand_kernel<true>), dim3((unsigned)eblocks), dim3(kBlock), 0, st, a, PB, recip);
-        } else {
-          hipLaunchKernelGGL((s4_expand_kernel<false>), dim3((unsigned)eblocks), dim3(kBlock), 0, st, a, PB, recip);
+          if (a.stream_out) return launch(fn, s4_expand_kernel<true, true>, grid, kBlock, 0, st, a, PB, recip);
+          return launch(fn, s4_expand_kernel<false, true>, grid, kBlock, 0, st, a, PB, recip);
         }
-        return check_launch(fn);
+        if (a.stream_out) return launch(fn, s4_expand_kernel<true>, grid, kBlock, 0, st, a, PB, recip);
+        return launch(fn, s4_expand_kernel<false>, grid, kBlock, 0, st, a, PB, recip);
       }
     }
-    (void)hipGetLastError();
     if constexpr (MODE == STEP) {
       // Non-temporal state loads from 96 MiB of states on (in place, measured: 64 MiB 23.1 / 24.0 us plain / nt,
       // 128 MiB 48.6 / 44.9, 192 MiB 71.8 / 65.1, 256 MiB 92.4 / 85.4, 512 MiB 205 / 202, 1 GiB 432 / 410, 2 GiB
@@ -2496,23 +2473,21 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
       // (a batch that sits in the XCDs' L2s anyway -- BASELINE config 2 -- is swept in one direction)
       const S4StepArgs sa{a.in, a.out, a.actions, a.done, a.overflow, a.B, static_cast<uint32_t>(a.in_stride), a.shift,
                           s4_digits_limit(a.shift), bytes > (16ll << 20) ? a.sweep : 0};
+      const dim3 grid((unsigned)blocks);
 #ifdef TG_AB_SWITCHES
       if (TG_SWITCH("TG_S4_NO_DIGITS")) {  // the packed form alone
-        if (tw) hipLaunchKernelGGL((s4_step_kernel<true, true, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-        else if (nt) hipLaunchKernelGGL((s4_step_kernel<true, false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-        else hipLaunchKernelGGL((s4_step_kernel<false, false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-        return check_launch(fn);
+        if (tw) return launch(fn, s4_step_kernel<true, true, false>, grid, kBlock, 0, st, sa);
+        if (nt) return launch(fn, s4_step_kernel<true, false, false>, grid, kBlock, 0, st, sa);
+        return launch(fn, s4_step_kernel<false, false, false>, grid, kBlock, 0, st, sa);
       }
 #endif
       // (fewer resident wavefronts, which helps the S = 16 / 25 steps beyond 1.25 GiB, costs here: 2 GiB of states with
       // 24 / 32 / 48 KB of unused LDS per workgroup: 841 / 942 / 1366 us against 772)
-      if (tw) hipLaunchKernelGGL((s4_step_kernel<true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-      else if (nt) hipLaunchKernelGGL((s4_step_kernel<true, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-      else hipLaunchKernelGGL((s4_step_kernel<false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, sa);
-      return check_launch(fn);
+      if (tw) return launch(fn, s4_step_kernel<true, true>, grid, kBlock, 0, st, sa);
+      if (nt) return launch(fn, s4_step_kernel<true, false>, grid, kBlock, 0, st, sa);
+      return launch(fn, s4_step_kernel<false, false>, grid, kBlock, 0, st, sa);
     } else {
-      hipLaunchKernelGGL((s4_kernel<MODE>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-      return check_launch(fn);
+      return launch(fn, s4_kernel<MODE>, (unsigned)blocks, kBlock, 0, st, a);
     }
   }
   // packed int16 path: exact while nact * f^3 <= 32000 for every |factor| <= f (checked on device)
@@ -2523,59 +2498,14 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
     const int64_t n = (MODE == GENF) ? a.nact : 1;  // STEP, EXPAND: one action per result
     while (flim < 31 && static_cast<int64_t>(flim + 1) * (flim + 1) * (flim + 1) * n <= 32000) ++flim;
   }
-#define TG_PACKED(S_, TS_)                                                                      \
-  do {                                                                                          \
-    const int64_t blocks = (B + PGeo<S_, TS_>::GPB - 1) / PGeo<S_, TS_>::GPB;                   \
-    if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);              \
-    const int at = a.nact < PGeo<S_, TS_>::ATILE ? a.nact : PGeo<S_, TS_>::ATILE;               \
-    const int ldsb = packed_lds_bytes<S_, TS_, MODE>(at);                                       \
-    (void)hipGetLastError();                                                                    \
-    hipLaunchKernelGGL((packed_kernel<S_, TS_, MODE>), dim3((unsigned)blocks), dim3(kBlock),    \
-                       ldsb, st, a, flim, at);                                                  \
-    return check_launch(fn);                                                                    \
-  } while (0)
-#define TG_ROWS(S_, TS_)                                                                        \
-  do {                                                                                          \
-    const int64_t blocks = (B + RGeo<S_, TS_>::GPB - 1) / RGeo<S_, TS_>::GPB;                   \
-    if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);              \
-    const int at = a.nact < RGeo<S_, TS_>::ATILE ? a.nact : RGeo<S_, TS_>::ATILE;               \
-    const int ldsb = rows_lds_bytes<S_, TS_, MODE>(at);                                         \
-    (void)hipGetLastError();                                                                    \
-    hipLaunchKernelGGL((rows_kernel<S_, TS_, MODE>), dim3((unsigned)blocks), dim3(kBlock),      \
-                       ldsb, st, a, flim, at);                                                  \
-    return check_launch(fn);                                                                    \
-  } while (0)
   const bool no_mfma = TG_SWITCH("TG_NO_MFMA");  // A/B switch for measurements
   if constexpr (MODE == GENF) {
     // the accumulation over R is a dense contraction: matrix cores (tg_mfma.h); u*v must fit int8 (checked
     // on device, per game), the transposed factors of one game must fit LDS
-    if (aligned16(a.out) && a.out_stride % 16 == 0 && a.nact <= 256 && !no_mfma) {
-#define TG_MFMA_K(S_, KS_)                                                                      \
-  do {                                                                                           \
-    /* a workgroup's set-up (tile offsets, staging addresses) is a third of one game's work: give every */ \
-    /* workgroup several games, as many workgroups as the chip holds at once, games split evenly */ \
-    static OccupancySlots occ;                                                                   \
-    const int per_cu = resident_per_cu(genf_mfma_kernel<S_, KS_>, ldsb, occ);                    \
-    const int64_t resident = static_cast<int64_t>(per_cu) * device_cu_count();                   \
-    const int64_t per_wg = (B + resident - 1) / resident;                                        \
-    const int64_t grid = (B + per_wg - 1) / per_wg;                                              \
-    (void)hipGetLastError();                                                                     \
-    hipLaunchKernelGGL((genf_mfma_kernel<S_, KS_>), dim3((unsigned)grid), dim3(kBlock), ldsb, st, a, Rp); \
-    return check_launch(fn);                                                                     \
-  } while (0)
-#define TG_MFMA(S_)                                                                              \
-  do {                                                                                           \
-    const int Rp = (a.nact + 31) & ~31;                                                          \
-    const int ldsb = mfma_lds_bytes<S_>(Rp);                                                     \
-    if (Rp == 32) TG_MFMA_K(S_, 1);                                                              \
-    if (Rp == 64) TG_MFMA_K(S_, 2);                                                              \
-    TG_MFMA_K(S_, 0);                                                                            \
-  } while (0)
-      if (a.S == 9) TG_MFMA(9);
-      if (a.S == 16) TG_MFMA(16);
-      if (a.S == 25) TG_MFMA(25);
-#undef TG_MFMA_K
-#undef TG_MFMA
+    if (aligned(a.out, 16) && a.out_stride % 16 == 0 && a.nact <= 256 && !no_mfma) {
+      if (a.S == 9) return launch_genf_mfma<9>(fn, a, st);
+      if (a.S == 16) return launch_genf_mfma<16>(fn, a, st);
+      if (a.S == 25) return launch_genf_mfma<25>(fn, a, st);
     }
   }
   if constexpr (MODE == MANY) {
@@ -2591,30 +2521,9 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
     //  S=16 B=8192 whatever K is -- staging, the tiles' fixed part, verdict; the lattice kernels 30 / 50 / 52 us at K = 2 / 3 / 4
     //  (S=25), 24 / 35 / 41 / 45 / 55 at K = 8 / 16 / 20 / 24 / 32 (S=16), 58 / 82 / 106 against 88 / 96 / 99 at K = 12 / 24 / 32 (S=9))
     if (al && a.nact <= 256 && !no_mfma && (a.S == 9 || a.S == 16 || a.S == 25) && (pays || many_always)) {
-      const int Rp = (a.nact + 31) & ~31;
-#define TG_MANY_K(S_, KS_)                                                                       \
-  do {                                                                                           \
-    const int ldsb = many_mfma_lds_bytes<S_>(Rp);                                                \
-    static OccupancySlots occ;                                                                   \
-    const int64_t resident = static_cast<int64_t>(resident_per_cu(many_mfma_kernel<S_, KS_>, ldsb, occ)) * device_cu_count(); \
-    const int64_t per_wg = (B + resident - 1) / resident;                                        \
-    const int64_t grid = (B + per_wg - 1) / per_wg;                                              \
-    (void)hipGetLastError();                                                                     \
-    hipLaunchKernelGGL((many_mfma_kernel<S_, KS_>), dim3((unsigned)grid), dim3(kBlock), ldsb, st, a, Rp); \
-    a.only_flagged = 0;                                                                          \
-    if (int rc = check_launch(fn)) return rc;                                                    \
-  } while (0)
-#define TG_MANY(S_)                                                                              \
-  do {                                                                                           \
-    if (Rp == 32) TG_MANY_K(S_, 1);                                                              \
-    else if (Rp == 64) TG_MANY_K(S_, 2);                                                         \
-    else TG_MANY_K(S_, 0);                                                                       \
-  } while (0)
-      if (a.S == 9) TG_MANY(9);
-      if (a.S == 16) TG_MANY(16);
-      if (a.S == 25) TG_MANY(25);
-#undef TG_MANY
-#undef TG_MANY_K
+      const int rc = a.S == 9 ? launch_many_mfma<9>(fn, a, st) : a.S == 16 ? launch_many_mfma<16>(fn, a, st)
+                                                                           : launch_many_mfma<25>(fn, a, st);
+      if (rc) return rc;
       a.only_flagged = 1;
     }
   }
@@ -2623,17 +2532,16 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
     // odd S, several actions: each lane owns whole rows (tg_rows.h); the LDS transposition is
     // amortised over the actions
     if (al && flim >= 1 && !no_rows && a.nact >= 3) {
-      if (a.S == 9) TG_ROWS(9, 64);
-      if (a.S == 25) TG_ROWS(25, 256);
+      if (a.S == 9) return launch_rows<9, 64, MODE>(fn, a, flim, st);
+      if (a.S == 25) return launch_rows<25, 256, MODE>(fn, a, flim, st);
     }
   }
-#undef TG_ROWS
   const bool no_s16 = TG_SWITCH("TG_NO_S16_DIRECT");  // A/B switch for measurements
   if constexpr (MODE == STEP) {
-    if (al && a.S == 16 && aligned16(a.actions) && !no_s16) {
+    if (al && a.S == 16 && aligned(a.actions, 16) && !no_s16) {
       const int64_t blocks = (B + 3) / 4;
       if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
-      (void)hipGetLastError();
+      const dim3 grid((unsigned)blocks);
       // whole-line stores pay from ~100 MiB of states on (measured: 6.0 / 7.0 us at 32 MiB, 26.3 / 25.5 at 128 MiB,
       // 50.3 / 47.0 at 256 MiB, 150 / 128 at 512 MiB, 16-byte stores / whole lines)
       // non-temporal state loads where the Infinity Cache can still assist a pass but not hold it: 320 MiB .. 1.25 GiB
@@ -2646,21 +2554,18 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
 #ifdef TG_AB_SWITCHES
       if (TG_SWITCH("TG_S16_NO_DIGITS")) {  // the packed int16 form alone
         if (nt_band || TG_SWITCH("TG_S16_NT_LOADS"))
-          hipLaunchKernelGGL((s16_step_kernel<MODE, true, true, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-        else if (B * a.in_stride >= (96ll << 20) || TG_SWITCH("TG_S16_LINES"))
-          hipLaunchKernelGGL((s16_step_kernel<MODE, true, false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-        else
-          hipLaunchKernelGGL((s16_step_kernel<MODE, false, false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-        return check_launch(fn);
+          return launch(fn, s16_step_kernel<MODE, true, true, false>, grid, kBlock, 0, st, a);
+        if (B * a.in_stride >= (96ll << 20) || TG_SWITCH("TG_S16_LINES"))
+          return launch(fn, s16_step_kernel<MODE, true, false, false>, grid, kBlock, 0, st, a);
+        return launch(fn, s16_step_kernel<MODE, false, false, false>, grid, kBlock, 0, st, a);
       }
 #endif
       if ((nt_band || TG_SWITCH("TG_S16_NT_LOADS")))  // (A/B switches: tests)
-        hipLaunchKernelGGL((s16_step_kernel<MODE, true, true>), dim3((unsigned)blocks), dim3(kBlock), s16_lds_pad, st, a);
+        return launch(fn, s16_step_kernel<MODE, true, true>, grid, kBlock, s16_lds_pad, st, a);
       else if ((B * a.in_stride >= (96ll << 20) || TG_SWITCH("TG_S16_LINES")))  // (A/B switch: tests at small batches)
-        hipLaunchKernelGGL((s16_step_kernel<MODE, true>), dim3((unsigned)blocks), dim3(kBlock), s16_lds_pad, st, a);
+        return launch(fn, s16_step_kernel<MODE, true>, grid, kBlock, s16_lds_pad, st, a);
       else
-        hipLaunchKernelGGL((s16_step_kernel<MODE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-      return check_launch(fn);
+        return launch(fn, s16_step_kernel<MODE, false>, grid, kBlock, 0, st, a);
     }
   }
   const bool no_s25 = TG_SWITCH("TG_NO_S25_DIRECT");  // A/B switch for measurements
@@ -2669,24 +2574,17 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
     if (al && a.S == 9 && a.shift >= -127 && a.shift <= 127 && !no_s9) {
       const int64_t blocks = (B + 15) / 16;  // four wavefronts of four games
       if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(s9_step_kernel<STEP>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-      return check_launch(fn);
+      return launch(fn, s9_step_kernel<STEP>, (unsigned)blocks, kBlock, 0, st, a);
     }
   }
   if constexpr (MODE == EXPAND) {
     // one 16-lane team per child (s9_step_kernel<EXPAND>): 80 -> 61 us at B = 32 768, k = 8
-    if (al && a.S == 9 && a.shift >= -127 && a.shift <= 127 && !no_s9 && B * a.nact < 0x7fffffffLL) {
-      const int64_t blocks = (B * a.nact + 15) / 16;
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(s9_step_kernel<EXPAND>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-      return check_launch(fn);
-    }
+    if (al && a.S == 9 && a.shift >= -127 && a.shift <= 127 && !no_s9 && B * a.nact < 0x7fffffffLL)
+      return launch(fn, s9_step_kernel<EXPAND>, (unsigned)((B * a.nact + 15) / 16), kBlock, 0, st, a);
   }
   if constexpr (MODE == STEP) {
     // (|shift| <= 127: factors within +-255, which the 32-bit redo of s25_step_kernel takes from its int16 tables)
     if (al && a.S == 25 && a.shift >= -127 && a.shift <= 127 && B <= 0x7fffffffLL && !no_s25) {
-      (void)hipGetLastError();
       // as at S=16: whole-line stores once the batch leaves the caches, non-temporal state loads beyond the Infinity
       // Cache (A/B switches: the variants at test sizes)
       // (round 3 sweep, 16-byte stores / whole lines / whole lines + nt loads: 244 MiB 46.8 / 47.2 / 52.9 us, 488 MiB
@@ -2699,137 +2597,110 @@ int launch_apply(const char* fn, const tg::ApplyArgs& a_in, hipStream_t st, bool
       // 572 us; two per CU: 751.  (BASELINE config 5's share, 61 MB: 15.0 / 15.1 / - / 16.1 / 16.1 -- there occupancy wins.)
       int s25_lds_pad = bytes25 >= kNtLoadsToBytes ? 36000 : 0;
       const bool nt_band = bytes25 >= kNtLoadsFromBytes && bytes25 < kNtLoadsToBytes;
+      const dim3 grid((unsigned)B);
       if ((nt_band || TG_SWITCH("TG_S25_NT_LOADS")))
-        hipLaunchKernelGGL((s25_step_kernel<true, true>), dim3((unsigned)B), dim3(kBlock), s25_lds_pad, st, a);
-      else if (((bytes25 >= (96ll << 20) && bytes25 < kNtLoadsToBytes) || TG_SWITCH("TG_S25_LINES")))
-        hipLaunchKernelGGL((s25_step_kernel<true, false>), dim3((unsigned)B), dim3(kBlock), s25_lds_pad, st, a);
-      else
-        hipLaunchKernelGGL((s25_step_kernel<false, false>), dim3((unsigned)B), dim3(kBlock), s25_lds_pad, st, a);
-      return check_launch(fn);
+        return launch(fn, s25_step_kernel<true, true>, grid, kBlock, s25_lds_pad, st, a);
+      if (((bytes25 >= (96ll << 20) && bytes25 < kNtLoadsToBytes) || TG_SWITCH("TG_S25_LINES")))
+        return launch(fn, s25_step_kernel<true, false>, grid, kBlock, s25_lds_pad, st, a);
+      return launch(fn, s25_step_kernel<false, false>, grid, kBlock, s25_lds_pad, st, a);
     }
   }
   if (al && flim >= 1) {
     // S=9: a game is only 46 chunks, so a wavefront takes FOUR games (teams of 16 lanes, 9 active, 6
     // chunks per lane): measured 0.48 of the HBM peak at 2^19 games against 0.43 (TS=32) and 0.29 (TS=64)
-    if (a.S == 9) TG_PACKED(9, 16);
+    if (a.S == 9) return launch_packed<9, 16, MODE>(fn, a, flim, st);
     if constexpr (MODE == EXPAND) {
       // S = 16: children of 128 MiB and more leave by non-temporal stores; with keys asked for (tg_expand_keyed_i8) they
       // are formed in the same launch while a child is in registers
-      const bool keyed = a.keys != nullptr;
-      if (a.S == 16 && (a.stream_out || keyed)) {
-        const int64_t blocks = (B + PGeo<16, 64>::GPB - 1) / PGeo<16, 64>::GPB;
-        if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
-        const int at = a.nact < PGeo<16, 64>::ATILE ? a.nact : PGeo<16, 64>::ATILE;
-        const int ldsb = packed_lds_bytes<16, 64, MODE>(at);
-        (void)hipGetLastError();
-        if (keyed) {
-          if (a.stream_out) hipLaunchKernelGGL((packed_kernel<16, 64, MODE, true, true>), dim3((unsigned)blocks), dim3(kBlock), ldsb, st, a, flim, at);
-          else hipLaunchKernelGGL((packed_kernel<16, 64, MODE, false, true>), dim3((unsigned)blocks), dim3(kBlock), ldsb, st, a, flim, at);
-          if (keys_fused) *keys_fused = true;
-        } else {
-          hipLaunchKernelGGL((packed_kernel<16, 64, MODE, true>), dim3((unsigned)blocks), dim3(kBlock), ldsb, st, a, flim, at);
-        }
-        return check_launch(fn);
+      if (a.S == 16 && a.keys) {
+        if (keys_fused) *keys_fused = true;
+        if (a.stream_out) return launch_packed<16, 64, MODE, true, true>(fn, a, flim, st);
+        return launch_packed<16, 64, MODE, false, true>(fn, a, flim, st);
       }
-    }
-    if constexpr (MODE == EXPAND) {
-      if (a.S == 25 && a.keys != nullptr) {  // tg_expand_keyed_i8 at S = 25: the keys from the same launch (a workgroup per parent)
+      if (a.S == 16 && a.stream_out) return launch_packed<16, 64, MODE, true>(fn, a, flim, st);
+      if (a.S == 25 && a.keys) {  // tg_expand_keyed_i8 at S = 25: the keys from the same launch (a workgroup per parent)
         if (B > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
         const int at = a.nact < PGeo<25, 256>::ATILE ? a.nact : PGeo<25, 256>::ATILE;
-        const int ldsb = packed_lds_bytes<25, 256, MODE, true>(at);
-        (void)hipGetLastError();
-        hipLaunchKernelGGL((packed_kernel<25, 256, MODE, false, true>), dim3((unsigned)B), dim3(kBlock), ldsb, st, a, flim, at);
         if (keys_fused) *keys_fused = true;
-        return check_launch(fn);
+        return launch(fn, packed_kernel<25, 256, MODE, false, true>, (unsigned)B, kBlock,
+                      packed_lds_bytes<25, 256, MODE, true>(at), st, a, flim, at);
       }
     }
-    if (a.S == 16) TG_PACKED(16, 64);
-    if (a.S == 25) TG_PACKED(25, 256);
+    if (a.S == 16) return launch_packed<16, 64, MODE>(fn, a, flim, st);
+    if (a.S == 25) return launch_packed<25, 256, MODE>(fn, a, flim, st);
   }
-#undef TG_PACKED
-  (void)hipGetLastError(); hipLaunchKernelGGL((slow_kernel<MODE>), dim3(capped_grid(B)), dim3(kBlock), 0, st, a);
-  return check_launch(fn);
+  return launch(fn, slow_kernel<MODE>, grid_for(B), kBlock, 0, st, a);
+}
+
+// The fused generator's launch (tg_genfused.h) for one shape: twice as many workgroups as fit at once (two games each at
+// B = 4096): the second wave of workgroups fills the chip as the first ones finish, which evens out the tail (measured:
+// 40 -> 38 us).  TG_GF_WGS (A/B library) sets the workgroups per CU instead.
+struct GenFused {
+  const char* fn;
+  tg::GenArgs ga;
+  int Rp, wgs_override;
+  bool lut_values;
+  hipStream_t st;
+};
+template <auto K>
+int launch_gen_fused(const GenFused& g, int ldsb) {
+  const int64_t resident = g.wgs_override > 0 ? static_cast<int64_t>(g.wgs_override) * device_cu_count()
+                                              : static_cast<int64_t>(resident_per_cu<K>(ldsb)) * device_cu_count() * 2;
+  if (int rc = launch(g.fn, K, even_grid(g.ga.B, resident), tg::kBlock, ldsb, g.st, g.ga, g.Rp)) return rc;
+  return 1;
+}
+template <int S, int KS, bool BAS, bool CHK>
+int gen_fused_k(const GenFused& g) {
+  const int ldsb = tg::genfused_lds_bytes<S>(g.Rp);
+  if (g.ga.D.nthr == 2 && KS != 0) {  // the reference's three values: the specialised draw evaluation
+    constexpr bool kLutShape = !BAS && !CHK;  // values exactly (-1,0,1): byte products by table lookup
+    if (kLutShape && g.lut_values) return launch_gen_fused<tg::gen_fused_kernel<S, KS, BAS, 4, CHK, true, kLutShape>>(g, ldsb);
+    return launch_gen_fused<tg::gen_fused_kernel<S, KS, BAS, 4, CHK, true>>(g, ldsb);
+  }
+  return launch_gen_fused<tg::gen_fused_kernel<S, KS, BAS, 4, CHK>>(g, ldsb);
+}
+template <int S, bool BAS, bool CHK>
+int gen_fused_r(const GenFused& g) {
+  if (g.Rp == 32) return gen_fused_k<S, 1, BAS, CHK>(g);
+  if (g.Rp == 64) return gen_fused_k<S, 2, BAS, CHK>(g);
+  return gen_fused_k<S, 0, BAS, CHK>(g);
+}
+template <int S>
+int gen_fused_s(const GenFused& g, bool basis, bool in_range) {
+  if (basis) return gen_fused_r<S, true, true>(g);
+  if (!in_range) return gen_fused_r<S, false, true>(g);
+  return gen_fused_r<S, false, false>(g);
 }
 
 }  // namespace
 
-// The generator in one kernel (tg_genfused.h); called by tg_gen_demos_i8 (tg_gen.hip).
-// Returns 1 = launched, 0 = not applicable (the caller takes the token kernel + tg_gen_from_factors_i8), < 0 = error.
 int tg_internal_gen_fused(int8_t* target, int8_t* actions, uint8_t* overflow, const int8_t* basis, int64_t B, int S,
                           int R, const tg::Dist& D, int shift, uint64_t seed, uint64_t gid0, int64_t stride,
                           hipStream_t st) {
-  using namespace tg;
-  const char* fn = "tg_gen_demos_i8";
   if (TG_SWITCH("TG_NO_FUSED_GEN") || TG_SWITCH("TG_NO_MFMA")) return 0;
   if (!(S == 9 || S == 16 || S == 25) || R > 256 || B == 0) return 0;
-  if (!aligned16(target) || stride % 16 != 0) return 0;
+  if (!aligned(target, 16) || stride % 16 != 0) return 0;
   if (!basis) {  // the drawn values are the factors: u * v must fit a byte product, tokens must fit int8
     for (int t = 0; t < D.nv; ++t) {
       const int v = D.val[t];
       if (v > 11 || v < -11 || v + shift > 127 || v + shift < -128) return 0;
     }
   }
-  const int Rp = (R + 31) & ~31;
-  GenArgs ga{target, actions, overflow, basis, B, stride, seed, gid0, R, shift, D};
-  int wgs_override = 0;
+  GenFused g{"tg_gen_demos_i8", {target, actions, overflow, basis, B, stride, seed, gid0, R, shift, D}, (R + 31) & ~31, 0,
+             false, st};
 #ifdef TG_AB_SWITCHES
-  ga.ablate = getenv("TG_GF_ABLATE") ? atoi(getenv("TG_GF_ABLATE")) : 0;
-  wgs_override = getenv("TG_GF_WGS") ? atoi(getenv("TG_GF_WGS")) : 0;
+  g.ga.ablate = getenv("TG_GF_ABLATE") ? atoi(getenv("TG_GF_ABLATE")) : 0;
+  g.wgs_override = getenv("TG_GF_WGS") ? atoi(getenv("TG_GF_WGS")) : 0;
 #endif
-#define TG_GF_K(S_, KS_, BAS_, CHK_)                                                               \
-  do {                                                                                             \
-    const int ldsb = genfused_lds_bytes<S_>(Rp);                                                   \
-    static OccupancySlots occ;                                                                     \
-    if (D.nthr == 2 && KS_ != 0) {  /* the reference's three values: the specialised draw evaluation */ \
-      static OccupancySlots occ3, occ3l;                                                           \
-      constexpr bool kLutShape = !(BAS_) && !(CHK_);  /* values exactly (-1,0,1): byte products by table lookup */ \
-      const bool lut = kLutShape && lut_values;                                                    \
-      void (*kern)(GenArgs, int) = lut ? gen_fused_kernel<S_, KS_, BAS_, 4, CHK_, true, kLutShape>        \
-                                       : gen_fused_kernel<S_, KS_, BAS_, 4, CHK_, true>;           \
-      const int per_cu3 = wgs_override > 0 ? wgs_override : resident_per_cu(kern, ldsb, lut ? occ3l : occ3); \
-      const int64_t resident3 = static_cast<int64_t>(per_cu3) * device_cu_count() * (wgs_override > 0 ? 1 : 2); \
-      const int64_t per_wg3 = (B + resident3 - 1) / resident3;                                     \
-      const int64_t grid3 = (B + per_wg3 - 1) / per_wg3;                                           \
-      (void)hipGetLastError();                                                                     \
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid3), dim3(kBlock), ldsb, st, ga, Rp);             \
-      if (int rc = check_launch(fn)) return rc;                                                    \
-      return 1;                                                                                    \
-    }                                                                                              \
-    const int per_cu = wgs_override > 0 ? wgs_override : resident_per_cu(gen_fused_kernel<S_, KS_, BAS_, 4, CHK_>, ldsb, occ); \
-    /* twice as many workgroups as fit at once (two games each at B = 4096): the second wave of workgroups fills */ \
-    /* the chip as the first ones finish, which evens out the tail (measured: 40 -> 38 us) */     \
-    const int64_t resident = static_cast<int64_t>(per_cu) * device_cu_count() * (wgs_override > 0 ? 1 : 2); \
-    const int64_t per_wg = (B + resident - 1) / resident;                                          \
-    const int64_t grid = (B + per_wg - 1) / per_wg;                                                \
-    (void)hipGetLastError();                                                                       \
-    hipLaunchKernelGGL((gen_fused_kernel<S_, KS_, BAS_, 4, CHK_>), dim3((unsigned)grid), dim3(kBlock), ldsb, st, ga, Rp); \
-    if (int rc = check_launch(fn)) return rc;                                                      \
-    return 1;                                                                                      \
-  } while (0)
-#define TG_GF_B(S_, BAS_, CHK_)                                                                    \
-  do {                                                                                             \
-    if (Rp == 32) TG_GF_K(S_, 1, BAS_, CHK_);                                                      \
-    if (Rp == 64) TG_GF_K(S_, 2, BAS_, CHK_);                                                      \
-    TG_GF_K(S_, 0, BAS_, CHK_);                                                                    \
-  } while (0)
-#define TG_GF(S_)                                                                                  \
-  do {                                                                                             \
-    if (basis) TG_GF_B(S_, true, true);                                                            \
-    if (!in_range) TG_GF_B(S_, false, true);                                                       \
-    TG_GF_B(S_, false, false);                                                                     \
-  } while (0)
   // without a basis the factors are the drawn values: when R * max|value|^3 <= 127 no entry of a target can leave
   // int8 (the reference's {-1,0,1} up to R = 127) and the tiles need no range tracking
   int fmax = 0;
   for (int t = 0; t < D.nv; ++t) fmax = D.val[t] > fmax ? D.val[t] : (-D.val[t] > fmax ? -D.val[t] : fmax);
   const bool in_range = !basis && static_cast<int64_t>(R) * fmax * fmax * fmax <= 127;
-  const bool lut_values = D.nv == 3 && D.val[0] == -1 && D.val[1] == 0 && D.val[2] == 1 && !TG_SWITCH("TG_GF_NO_LUT");
-  if (S == 9) TG_GF(9);
-  if (S == 16) TG_GF(16);
-  TG_GF(25);
-#undef TG_GF
-#undef TG_GF_B
-#undef TG_GF_K
+  g.lut_values = D.nv == 3 && D.val[0] == -1 && D.val[1] == 0 && D.val[2] == 1 && !TG_SWITCH("TG_GF_NO_LUT");
+  if (S == 9) return gen_fused_s<9>(g, basis, in_range);
+  if (S == 16) return gen_fused_s<16>(g, basis, in_range);
+  return gen_fused_s<25>(g, basis, in_range);
 }
 
 extern "C" {
@@ -2859,7 +2730,7 @@ static std::atomic<unsigned> g_sweep{0};  // direction of the next tg_step_i8 sw
 int tg_step_i8(const int8_t* state_in, int8_t* state_out, const int8_t* actions, uint8_t* done,
                uint8_t* overflow, int64_t B, int S, int64_t game_stride_bytes, int shift,
                tg_stream_t stream) {
-  if (int rc = validate_common("tg_step_i8", B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_step_i8", B, S, game_stride_bytes)) return rc;
   if (B && (!state_in || !state_out || !actions || !done))
     return fail(TG_ERR_INVALID, "tg_step_i8: null pointer");
   tg::ApplyArgs a{state_in, state_out, actions, done, nullptr, nullptr, overflow, B,
@@ -2875,14 +2746,13 @@ constexpr uint32_t kStreamWaitTicks = 100000000u;  // 1.0 s of s_memrealtime (10
 // one-game-per-lane kernel (kStreamLanes; four workgroups per CU at 122 VGPRs).
 constexpr int kStreamLanes = 0;
 static int64_t stream_units_resident(int S, int ng) {
-  static OccupancySlots occ1, occ2, occ16, occ25, occl;
   const int64_t cus = device_cu_count();
-  if (S == 16) return cus * 4 * resident_per_cu(tg::s16_stream_kernel, 0, occ16);
-  if (S == 25) return cus * 4 * resident_per_cu(tg::s25_stream_kernel, 0, occ25);
+  if (S == 16) return cus * 4 * resident_per_cu<tg::s16_stream_kernel>(0);
+  if (S == 25) return cus * 4 * resident_per_cu<tg::s25_stream_kernel>(0);
   switch (ng) {
-    case kStreamLanes: return cus * 4 * resident_per_cu(tg::s4_stream_kernel_lanes, 0, occl);
-    case 1: return cus * 4 * resident_per_cu(tg::s4_stream_kernel<1>, 0, occ1);
-    default: return cus * 4 * resident_per_cu(tg::s4_stream_kernel<2>, 0, occ2);
+    case kStreamLanes: return cus * 4 * resident_per_cu<tg::s4_stream_kernel_lanes>(0);
+    case 1: return cus * 4 * resident_per_cu<tg::s4_stream_kernel<1>>(0);
+    default: return cus * 4 * resident_per_cu<tg::s4_stream_kernel<2>>(0);
   }
 }
 
@@ -2957,7 +2827,7 @@ int tg_step_stream_i8(int8_t* state, const int8_t* actions, uint8_t* done, uint8
                       uint32_t* progress, uint32_t* status, int64_t B, int S, int K, int64_t game_stride_bytes, int shift,
                       tg_stream_t stream) {
   const char* fn = "tg_step_stream_i8";
-  if (int rc = validate_common(fn, B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state(fn, B, S, game_stride_bytes)) return rc;
   if (K < 1 || K > (1 << 24)) return fail(TG_ERR_INVALID, "%s: K=%d outside [1,2^24]", fn, K);
   if (B == 0) return TG_OK;
   if (!state || !actions || !done) return fail(TG_ERR_INVALID, "%s: null pointer", fn);
@@ -2987,30 +2857,22 @@ int tg_step_stream_i8(int8_t* state, const int8_t* actions, uint8_t* done, uint8
                 fn, (long long)B, (long long)stream_units_resident(S, 1), S);
   // (a single game has no stride to speak of; S = 25 reads the 16-byte chunk that holds the game's last byte: it lies inside
   // the last game's final aligned 16 bytes, and only the game's own 9 bytes of it are ever written)
-  if (!aligned16(state) || (game_stride_bytes % 16 != 0 && B > 1) || !(S == 16 ? aligned16(actions) : aligned4(actions)) ||
+  if (!aligned(state, 16) || (game_stride_bytes % 16 != 0 && B > 1) || !(S == 16 ? aligned(actions, 16) : aligned(actions, 4)) ||
       B * game_stride_bytes > 0x7fffffffLL || static_cast<int64_t>(K) * B > 0x7fffffffLL ||
       static_cast<unsigned>(shift + 127) > 254u)
     return fail(TG_ERR_UNSUPPORTED, "%s: needs 16-byte aligned states, aligned actions (4 bytes at S=4, 16 at S=16), B*stride and K*B < 2^31, |shift| <= 127", fn);
-  if ((ready && (reinterpret_cast<uintptr_t>(ready) & 3)) || (progress && (reinterpret_cast<uintptr_t>(progress) & 3)))
+  if (!aligned(ready, 4) || !aligned(progress, 4))
     return fail(TG_ERR_INVALID, "%s: ready / progress must be 4-byte aligned", fn);
   tg::StreamArgs a{state, actions, done, overflow, ready, progress, status, B, game_stride_bytes, K, shift, kStreamWaitTicks};
   const unsigned grid = static_cast<unsigned>((units + 3) / 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
-  if (S == 16) {
-    hipLaunchKernelGGL(tg::s16_stream_kernel, dim3(grid), dim3(tg::kBlock), 0, st, a);
-    return check_launch(fn);
-  }
-  if (S == 25) {
-    hipLaunchKernelGGL(tg::s25_stream_kernel, dim3(grid), dim3(tg::kBlock), 0, st, a);
-    return check_launch(fn);
-  }
+  if (S == 16) return launch(fn, tg::s16_stream_kernel, grid, tg::kBlock, 0, st, a);
+  if (S == 25) return launch(fn, tg::s25_stream_kernel, grid, tg::kBlock, 0, st, a);
   switch (variant) {
-    case kStreamLanes: hipLaunchKernelGGL(tg::s4_stream_kernel_lanes, dim3(grid), dim3(tg::kBlock), 0, st, a); break;
-    case 1: hipLaunchKernelGGL(tg::s4_stream_kernel<1>, dim3(grid), dim3(tg::kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL(tg::s4_stream_kernel<2>, dim3(grid), dim3(tg::kBlock), 0, st, a); break;
+    case kStreamLanes: return launch(fn, tg::s4_stream_kernel_lanes, grid, tg::kBlock, 0, st, a);
+    case 1: return launch(fn, tg::s4_stream_kernel<1>, grid, tg::kBlock, 0, st, a);
+    default: return launch(fn, tg::s4_stream_kernel<2>, grid, tg::kBlock, 0, st, a);
   }
-  return check_launch(fn);
 }
 
 constexpr int64_t kTrackedSparse25 = 2048;  // games (placed by tools/tracked_time.py sweeps)
@@ -3018,32 +2880,27 @@ constexpr int64_t kTrackedSparse25 = 2048;  // games (placed by tools/tracked_ti
 int tg_step_tracked_i8(int8_t* state, const int8_t* actions, int32_t* nnz, uint8_t* done, uint8_t* overflow, int64_t B,
                        int S, int64_t game_stride_bytes, int shift, tg_stream_t stream) {
   const char* fn = "tg_step_tracked_i8";
-  if (int rc = validate_common(fn, B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state(fn, B, S, game_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!state || !actions || !nnz || !done) return fail(TG_ERR_INVALID, "%s: null pointer", fn);
-  if (reinterpret_cast<uintptr_t>(nnz) & 3) return fail(TG_ERR_INVALID, "%s: nnz must be 4-byte aligned", fn);
+  if (!aligned(nnz, 4)) return fail(TG_ERR_INVALID, "%s: nnz must be 4-byte aligned", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (S == 25 && aligned16(state) && game_stride_bytes % 16 == 0 && static_cast<unsigned>(shift + 127) <= 254u &&
+  if (S == 25 && aligned(state, 16) && game_stride_bytes % 16 == 0 && static_cast<unsigned>(shift + 127) <= 254u &&
       B <= 0x7fffffffLL) {
     // sparse kernel from kTrackedSparse25 games on, fewer: the full step's kernel with the count updated (one round trip
     // instead of two).  Measured, tg_step_i8 / full + count / sparse: 512 games 5.0 / 5.8 / 8.1 us, 1 024 6.1 / 7.1 / 8.3,
     // 2 048 8.5 / 10.7 / 10.0, 4 096 14.9 / 17.0 / 13.1, 32 768 102 / - / 65, 139 264 (2 GiB) 574 / - / 303
     tg::ApplyArgs a{state, state, actions, done, nnz, nullptr, overflow, B, game_stride_bytes, game_stride_bytes, S, 1, shift};
-    (void)hipGetLastError();
     if ((B >= kTrackedSparse25 || TG_SWITCH("TG_TRACKED_SPARSE")) && !TG_SWITCH("TG_TRACKED_FULL"))
-      hipLaunchKernelGGL(tg::s25_tracked_kernel, dim3(static_cast<unsigned>((B + 3) / 4)), dim3(tg::kBlock), 0, st, a, nnz);
-    else
-      hipLaunchKernelGGL((tg::s25_step_kernel<false, false, true>), dim3(static_cast<unsigned>(B)), dim3(tg::kBlock), 0, st, a);
-    return check_launch(fn);
+      return launch(fn, tg::s25_tracked_kernel, static_cast<unsigned>((B + 3) / 4), tg::kBlock, 0, st, a, nnz);
+    return launch(fn, tg::s25_step_kernel<false, false, true>, static_cast<unsigned>(B), tg::kBlock, 0, st, a);
   }
-  if (S == 16 && aligned16(state) && aligned16(actions) && game_stride_bytes % 16 == 0 && B <= 0x7fffffffLL) {
+  if (S == 16 && aligned(state, 16) && aligned(actions, 16) && game_stride_bytes % 16 == 0 && B <= 0x7fffffffLL) {
     // The sparse kernel pays two dependent round trips for ~28 % of the lines (measured, tg_step_i8 / this: 2 048 games 3.3 /
     // 3.5 us, 8 192 5.8 / 6.5, 12 288 11.1 / 8.4, 32 768 26.7 / 16.6, 131 072 99.7 / 73.7, 2 GiB 504 / 296).  The full step's
     // kernel with the count added was no better at the small end (3.8 / 6.6 us): one kernel for every batch.
     tg::ApplyArgs a{state, state, actions, done, nullptr, nullptr, overflow, B, game_stride_bytes, game_stride_bytes, S, 1, shift};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tg::s16_tracked_kernel, dim3(static_cast<unsigned>((B + 3) / 4)), dim3(tg::kBlock), 0, st, a, nnz);
-    return check_launch(fn);
+    return launch(fn, tg::s16_tracked_kernel, static_cast<unsigned>((B + 3) / 4), tg::kBlock, 0, st, a, nnz);
   }
   // other sizes and layouts: the full step, then the count (two launches inside this call; same results)
   if (int rc = tg_step_i8(state, state, actions, done, overflow, B, S, game_stride_bytes, shift, stream)) return rc;
@@ -3053,7 +2910,7 @@ int tg_step_tracked_i8(int8_t* state, const int8_t* actions, int32_t* nnz, uint8
 int tg_step_many_i8(const int8_t* state_in, int8_t* state_out, const int8_t* actions,
                     int32_t* done_step, uint8_t* overflow, int64_t B, int S, int K,
                     int64_t game_stride_bytes, int shift, tg_stream_t stream) {
-  if (int rc = validate_common("tg_step_many_i8", B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_step_many_i8", B, S, game_stride_bytes)) return rc;
   if (K < 1 || K > TG_MAX_ACTIONS)
     return fail(TG_ERR_INVALID, "tg_step_many_i8: K=%d outside [1,%d]", K, TG_MAX_ACTIONS);
   if (B && (!state_in || !state_out || !actions || !done_step))
@@ -3063,17 +2920,15 @@ int tg_step_many_i8(const int8_t* state_in, int8_t* state_out, const int8_t* act
   return launch_apply<tg::MANY>("tg_step_many_i8", a, static_cast<hipStream_t>(stream));
 }
 
-int tg_internal_hash(const int8_t* state, uint64_t* hash_out, int64_t B, int S, int64_t stride, hipStream_t st);  // tg_aux.hip
-
 static int expand_common(const char* fn, const int8_t* state_in, int8_t* state_out, const int8_t* actions, uint8_t* done,
                          uint8_t* changed, uint8_t* overflow, uint64_t* keys_out, int64_t B, int S, int k,
                          int64_t in_stride_bytes, int64_t out_stride_bytes, int shift, tg_stream_t stream) {
-  if (int rc = validate_common(fn, B, S, in_stride_bytes)) return rc;
-  if (int rc = validate_common(fn, B, S, out_stride_bytes)) return rc;
+  if (int rc = check_state(fn, B, S, in_stride_bytes)) return rc;
+  if (int rc = check_state(fn, B, S, out_stride_bytes)) return rc;
   if (k < 1 || k > TG_MAX_ACTIONS) return fail(TG_ERR_INVALID, "%s: k=%d outside [1,%d]", fn, k, TG_MAX_ACTIONS);
   if (B && (!state_in || !state_out || !actions || !done)) return fail(TG_ERR_INVALID, "%s: null pointer", fn);
   if (B && state_in == state_out) return fail(TG_ERR_INVALID, "%s: in-place expansion is not defined", fn);
-  if (reinterpret_cast<uintptr_t>(keys_out) & 7) return fail(TG_ERR_INVALID, "%s: keys_out must be 8-byte aligned", fn);
+  if (!aligned(keys_out, 8)) return fail(TG_ERR_INVALID, "%s: keys_out must be 8-byte aligned", fn);
   tg::ApplyArgs a{state_in, state_out, actions, done, nullptr, changed, overflow, B,
                   in_stride_bytes, out_stride_bytes, S, k, shift};
   a.keys = keys_out;
@@ -3100,14 +2955,11 @@ int tg_expand_keyed_i8(const int8_t* state_in, int8_t* state_out, const int8_t* 
                        in_stride_bytes, out_stride_bytes, shift, stream);
 }
 
-int tg_emit_frames(const int8_t* ring, void* out, float* scalars, int out_dtype, int64_t B, int S, int T, int head_slot,
-                   float t_step, int64_t frame_stride_bytes, int64_t game_stride_bytes, tg_stream_t stream);  // tg_aux.hip
-
 int tg_step_emit(int8_t* ring, const int8_t* actions, void* out, float* scalars, uint8_t* done, uint8_t* overflow,
                  int out_dtype, int64_t B, int S, int T, int head_slot, float t_step, int64_t frame_stride_bytes,
                  int64_t game_stride_bytes, int shift, tg_stream_t stream) {
   const char* fn = "tg_step_emit";
-  if (int rc = validate_common(fn, B, S, frame_stride_bytes)) return rc;
+  if (int rc = check_state(fn, B, S, frame_stride_bytes)) return rc;
   if (T < 1 || T > 64 || head_slot < 0 || head_slot >= T)
     return fail(TG_ERR_INVALID, "%s: need 1 <= T <= 64 and 0 <= head_slot < T", fn);
   if (game_stride_bytes < static_cast<int64_t>(T - 1) * frame_stride_bytes + static_cast<int64_t>(S) * S * S)
@@ -3115,7 +2967,7 @@ int tg_step_emit(int8_t* ring, const int8_t* actions, void* out, float* scalars,
   if (out_dtype < 0 || out_dtype > 2) return fail(TG_ERR_INVALID, "%s: out_dtype must be 0 (f32), 1 (f16) or 2 (bf16)", fn);
   if (B == 0) return TG_OK;
   if (!ring || !actions || !out || !done) return fail(TG_ERR_INVALID, "%s: null pointer", fn);
-  if (reinterpret_cast<uintptr_t>(out) & 15) return fail(TG_ERR_INVALID, "%s: out must be 16-byte aligned", fn);
+  if (!aligned(out, 16)) return fail(TG_ERR_INVALID, "%s: out must be 16-byte aligned", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nxt = head_slot + 1 < T ? head_slot + 1 : 0;
   // One launch while the model input stays in the caches (65 536 games, T = 4: 9.9 us against 14.3 for step + frames in
@@ -3123,48 +2975,36 @@ int tg_step_emit(int8_t* ring, const int8_t* actions, void* out, float* scalars,
   // 16-byte-per-thread write stream wins over the fused kernel's 64-byte team runs (2^20 games: 243 against 185 us,
   // 350 against 320), so from kStreamOutBytes of output on this entry is the two launches.
   const int64_t out_bytes = B * T * 64 * (out_dtype ? 2 : 4);
-  const bool fused = S == 4 && (reinterpret_cast<uintptr_t>(ring) & 3) == 0 && frame_stride_bytes % 4 == 0 &&
-                     game_stride_bytes % 4 == 0 && aligned4(actions) && static_cast<unsigned>(shift + 127) <= 254u &&
+  const bool fused = S == 4 && aligned(ring, 4) && frame_stride_bytes % 4 == 0 &&
+                     game_stride_bytes % 4 == 0 && aligned(actions, 4) && static_cast<unsigned>(shift + 127) <= 254u &&
                      (out_bytes < tg::kStreamOutBytes || TG_SWITCH("TG_STEP_EMIT_FUSED"));
   if (fused) {
     tg::StepEmitArgs a{ring, actions, out, scalars, done, overflow, B, frame_stride_bytes, game_stride_bytes, T, head_slot, shift, t_step};
     const int64_t blocks = (B * 4 + tg::kBlock - 1) / tg::kBlock;
     if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
     const bool nt = out_bytes >= tg::kStreamOutBytes || TG_SWITCH("TG_EMIT_NT");  // (A/B library only, see above)
-    const dim3 grid(static_cast<unsigned>(blocks)), block(tg::kBlock);
-    (void)hipGetLastError();
-#define TG_SE(OutT_)                                                                              \
-  do {                                                                                            \
-    if (nt) hipLaunchKernelGGL((tg::s4_step_emit_kernel<OutT_, true>), grid, block, 0, st, a);   \
-    else hipLaunchKernelGGL((tg::s4_step_emit_kernel<OutT_, false>), grid, block, 0, st, a);     \
-  } while (0)
-    if (out_dtype == 1) TG_SE(__half);
-    else if (out_dtype == 2) TG_SE(__hip_bfloat16);
-    else TG_SE(float);
-#undef TG_SE
-    return check_launch(fn);
+    const unsigned grid = static_cast<unsigned>(blocks);
+    return with_out_type(out_dtype, [&](auto t) {
+      using OutT = decltype(t);
+      if (nt) return launch(fn, tg::s4_step_emit_kernel<OutT, true>, grid, tg::kBlock, 0, st, a);
+      return launch(fn, tg::s4_step_emit_kernel<OutT, false>, grid, tg::kBlock, 0, st, a);
+    });
   }
   // S = 16 while the output stays in the caches: one launch (s16_step_emit_kernel)
   const int64_t out_bytes16 = B * T * 4096 * (out_dtype ? 2 : 4);
-  const bool fused16 = S == 16 && aligned16(ring) && frame_stride_bytes % 16 == 0 && game_stride_bytes % 16 == 0 && aligned16(actions) &&
+  const bool fused16 = S == 16 && aligned(ring, 16) && frame_stride_bytes % 16 == 0 && game_stride_bytes % 16 == 0 && aligned(actions, 16) &&
                        (out_bytes16 < tg::kStreamOutBytes || TG_SWITCH("TG_STEP_EMIT_FUSED"));
   if (fused16) {
     tg::StepEmitArgs a{ring, actions, out, scalars, done, overflow, B, frame_stride_bytes, game_stride_bytes, T, head_slot, shift, t_step};
     const int64_t blocks = (B + 3) / 4;
     if (blocks > 0x7fffffffLL) return fail(TG_ERR_INVALID, "%s: B too large", fn);
     const bool nt = out_bytes16 >= tg::kStreamOutBytes;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(tg::kBlock);
-    (void)hipGetLastError();
-#define TG_SE16(OutT_)                                                                             \
-  do {                                                                                             \
-    if (nt) hipLaunchKernelGGL((tg::s16_step_emit_kernel<OutT_, true>), grid, block, 0, st, a);   \
-    else hipLaunchKernelGGL((tg::s16_step_emit_kernel<OutT_, false>), grid, block, 0, st, a);     \
-  } while (0)
-    if (out_dtype == 1) TG_SE16(__half);
-    else if (out_dtype == 2) TG_SE16(__hip_bfloat16);
-    else TG_SE16(float);
-#undef TG_SE16
-    return check_launch(fn);
+    const unsigned grid = static_cast<unsigned>(blocks);
+    return with_out_type(out_dtype, [&](auto t) {
+      using OutT = decltype(t);
+      if (nt) return launch(fn, tg::s16_step_emit_kernel<OutT, true>, grid, tg::kBlock, 0, st, a);
+      return launch(fn, tg::s16_step_emit_kernel<OutT, false>, grid, tg::kBlock, 0, st, a);
+    });
   }
   // other sizes and layouts: the step into the next ring slot, then the frames (two launches inside this call)
   if (int rc = tg_step_i8(ring + head_slot * frame_stride_bytes, ring + nxt * frame_stride_bytes, actions, done, overflow, B, S,
@@ -3175,7 +3015,7 @@ int tg_step_emit(int8_t* ring, const int8_t* actions, void* out, float* scalars,
 
 int tg_gen_from_factors_i8(const int8_t* actions, int8_t* target_out, uint8_t* overflow, int64_t B,
                            int S, int R, int64_t game_stride_bytes, int shift, tg_stream_t stream) {
-  if (int rc = validate_common("tg_gen_from_factors_i8", B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_gen_from_factors_i8", B, S, game_stride_bytes)) return rc;
   if (R < 1 || R > TG_MAX_ACTIONS)
     return fail(TG_ERR_INVALID, "tg_gen_from_factors_i8: R=%d outside [1,%d]", R, TG_MAX_ACTIONS);
   if (B && (!actions || !target_out)) return fail(TG_ERR_INVALID, "tg_gen_from_factors_i8: null pointer");
@@ -3186,15 +3026,18 @@ int tg_gen_from_factors_i8(const int8_t* actions, int8_t* target_out, uint8_t* o
 
 int tg_copy_i8(const int8_t* state_in, int8_t* state_out, int64_t B, int S, int64_t in_stride_bytes,
                int64_t out_stride_bytes, tg_stream_t stream) {
-  if (int rc = validate_common("tg_copy_i8", B, S, in_stride_bytes)) return rc;
-  if (int rc = validate_common("tg_copy_i8", B, S, out_stride_bytes)) return rc;
+  if (int rc = check_state("tg_copy_i8", B, S, in_stride_bytes)) return rc;
+  if (int rc = check_state("tg_copy_i8", B, S, out_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!state_in || !state_out) return fail(TG_ERR_INVALID, "tg_copy_i8: null pointer");
   if (state_in == state_out) return in_stride_bytes == out_stride_bytes ? TG_OK : fail(TG_ERR_INVALID, "tg_copy_i8: in place with different strides");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int N = S * S * S;
-  (void)hipGetLastError();
-  if (aligned16(state_in) && aligned16(state_out) && in_stride_bytes % 16 == 0 && out_stride_bytes % 16 == 0) {
+  auto copy = [&](auto kernel, unsigned grid, auto... x) {
+    return launch("tg_copy_i8", kernel, grid, tg::kBlock, 0, st, state_in, state_out, B, x..., in_stride_bytes,
+                  out_stride_bytes);
+  };
+  if (aligned(state_in, 16) && aligned(state_out, 16) && in_stride_bytes % 16 == 0 && out_stride_bytes % 16 == 0) {
     const int nchunk = (N + 15) / 16;
     int sh = -1;
     for (int t = 0; t < 12; ++t)
@@ -3205,31 +3048,21 @@ int tg_copy_i8(const int8_t* state_in, int8_t* state_out, int64_t B, int S, int6
     // nt loads / nt loads + stores): 256 MiB 33 / 34 / 41 us, 384 MiB 67 / 49 / 61, 512 MiB 88 / 71 / 81, 768 MiB
     // 131 / 127 / 120, 1 GiB 172 / 167 / 160.  This kernel is the bench's copy ceiling: it has to be the best copy.
     const int64_t both = state_in == state_out ? 0 : B * (in_stride_bytes + out_stride_bytes);
-    if (TG_SWITCH("TG_COPY_PLAIN"))
-      hipLaunchKernelGGL(tg::copy_kernel<0>, dim3((unsigned)blocks), dim3(tg::kBlock), 0, st, state_in, state_out, B, nchunk,
-                         sh, N % 16, in_stride_bytes, out_stride_bytes);
-    else if (both > (640ll << 20) || TG_SWITCH("TG_COPY_NT2"))
-      hipLaunchKernelGGL(tg::copy_kernel<2>, dim3((unsigned)blocks), dim3(tg::kBlock), 0, st, state_in, state_out, B, nchunk,
-                         sh, N % 16, in_stride_bytes, out_stride_bytes);
-    else if (both > (256ll << 20) || TG_SWITCH("TG_COPY_NT1"))
-      hipLaunchKernelGGL(tg::copy_kernel<1>, dim3((unsigned)blocks), dim3(tg::kBlock), 0, st, state_in, state_out, B, nchunk,
-                         sh, N % 16, in_stride_bytes, out_stride_bytes);
-    else
-      hipLaunchKernelGGL(tg::copy_kernel<0>, dim3((unsigned)blocks), dim3(tg::kBlock), 0, st, state_in, state_out, B, nchunk,
-                         sh, N % 16, in_stride_bytes, out_stride_bytes);
-  } else {
-    hipLaunchKernelGGL(tg::copy_bytes_kernel, dim3(capped_grid(B > 65536 ? 65536 : B)), dim3(tg::kBlock), 0, st, state_in,
-                       state_out, B, N, in_stride_bytes, out_stride_bytes);
+    const unsigned grid = static_cast<unsigned>(blocks);
+    if (TG_SWITCH("TG_COPY_PLAIN")) return copy(tg::copy_kernel<0>, grid, nchunk, sh, N % 16);
+    else if (both > (640ll << 20) || TG_SWITCH("TG_COPY_NT2")) return copy(tg::copy_kernel<2>, grid, nchunk, sh, N % 16);
+    else if (both > (256ll << 20) || TG_SWITCH("TG_COPY_NT1")) return copy(tg::copy_kernel<1>, grid, nchunk, sh, N % 16);
+    else return copy(tg::copy_kernel<0>, grid, nchunk, sh, N % 16);
   }
-  return check_launch("tg_copy_i8");
+  return copy(tg::copy_bytes_kernel, grid_for(B, 65536), N);
 }
 
 int tg_done_i8(const int8_t* state, uint8_t* done, int32_t* nnz, int64_t B, int S,
                int64_t game_stride_bytes, tg_stream_t stream) {
-  if (int rc = validate_common("tg_done_i8", B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_done_i8", B, S, game_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!state || !done) return fail(TG_ERR_INVALID, "tg_done_i8: null pointer");
-  const int vec16 = aligned16(state) && game_stride_bytes % 16 == 0;
+  const int vec16 = aligned(state, 16) && game_stride_bytes % 16 == 0;
   const int N = S * S * S;
   int lpg = 1;
   // lanes per game: up to four 16-byte chunks per lane for games of 16 chunks and more (S=9: 16 lanes x 3 chunks, four
@@ -3237,43 +3070,39 @@ int tg_done_i8(const int8_t* state, uint8_t* done, int32_t* nnz, int64_t B, int 
   // 12-16 us for 24 MB), one chunk per lane for the small ones (S=4: 4 lanes)
   while (lpg < 64 && lpg * 16 * (N >= 256 ? 4 : 1) < N) lpg <<= 1;
   const int64_t blocks = (B * lpg + tg::kBlock - 1) / tg::kBlock;
-  (void)hipGetLastError(); hipLaunchKernelGGL(tg::done_kernel, dim3(capped_grid(blocks > 8192 ? 8192 : blocks)), dim3(tg::kBlock), 0,
-                     static_cast<hipStream_t>(stream), state, done, nnz, B, N, game_stride_bytes, vec16, lpg);
-  return check_launch("tg_done_i8");
+  return launch("tg_done_i8", tg::done_kernel, grid_for(blocks, 8192), tg::kBlock, 0, static_cast<hipStream_t>(stream),
+                state, done, nnz, B, N, game_stride_bytes, vec16, lpg);
 }
 
 int tg_reset_matmul_i8(int8_t* state_out, int64_t B, int n, int64_t game_stride_bytes,
                        tg_stream_t stream) {
   if (n < 1 || n * n > TG_MAX_S) return fail(TG_ERR_INVALID, "tg_reset_matmul_i8: n=%d, need 1 <= n*n <= %d", n, TG_MAX_S);
-  if (int rc = validate_common("tg_reset_matmul_i8", B, n * n, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_reset_matmul_i8", B, n * n, game_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!state_out) return fail(TG_ERR_INVALID, "tg_reset_matmul_i8: null pointer");
   const int S = n * n, N = S * S * S;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::matmul_template_kernel, dim3((N + tg::kBlock - 1) / tg::kBlock), dim3(tg::kBlock), 0, st,
-                     state_out, n);
-  if (B > 1) {
-    const int vec16 = aligned16(state_out) && game_stride_bytes % 16 == 0;
-    const int64_t work = (B - 1) * (vec16 ? (N + 15) / 16 : N);
-    hipLaunchKernelGGL(tg::broadcast_kernel, dim3(capped_grid((work + tg::kBlock - 1) / tg::kBlock > 8192 ? 8192 : (work + tg::kBlock - 1) / tg::kBlock)),
-                       dim3(tg::kBlock), 0, st, state_out, state_out, (int64_t)1, B, N, game_stride_bytes, vec16);
-  }
-  return check_launch("tg_reset_matmul_i8");
+  const char* fn = "tg_reset_matmul_i8";
+  if (int rc = launch(fn, tg::matmul_template_kernel, (N + tg::kBlock - 1) / tg::kBlock, tg::kBlock, 0, st, state_out, n))
+    return rc;
+  if (B == 1) return TG_OK;
+  const int vec16 = aligned(state_out, 16) && game_stride_bytes % 16 == 0;
+  const int64_t work = (B - 1) * (vec16 ? (N + 15) / 16 : N);
+  return launch(fn, tg::broadcast_kernel, grid_for((work + tg::kBlock - 1) / tg::kBlock, 8192), tg::kBlock, 0, st,
+                state_out, state_out, (int64_t)1, B, N, game_stride_bytes, vec16);
 }
 
 int tg_reset_broadcast_i8(const int8_t* start, int8_t* state_out, int64_t B, int S,
                           int64_t game_stride_bytes, tg_stream_t stream) {
-  if (int rc = validate_common("tg_reset_broadcast_i8", B, S, game_stride_bytes)) return rc;
+  if (int rc = check_state("tg_reset_broadcast_i8", B, S, game_stride_bytes)) return rc;
   if (B == 0) return TG_OK;
   if (!start || !state_out) return fail(TG_ERR_INVALID, "tg_reset_broadcast_i8: null pointer");
-  const int vec16 = aligned16(start) && aligned16(state_out) && game_stride_bytes % 16 == 0;
+  const int vec16 = aligned(start, 16) && aligned(state_out, 16) && game_stride_bytes % 16 == 0;
   const int N = S * S * S;
   const int64_t work = B * (vec16 ? (N + 15) / 16 : N);
   const int64_t blocks = (work + tg::kBlock - 1) / tg::kBlock;
-  (void)hipGetLastError(); hipLaunchKernelGGL(tg::broadcast_kernel, dim3(capped_grid(blocks > 8192 ? 8192 : blocks)), dim3(tg::kBlock), 0,
-                     static_cast<hipStream_t>(stream), start, state_out, (int64_t)0, B, N, game_stride_bytes, vec16);
-  return check_launch("tg_reset_broadcast_i8");
+  return launch("tg_reset_broadcast_i8", tg::broadcast_kernel, grid_for(blocks, 8192), tg::kBlock, 0,
+                static_cast<hipStream_t>(stream), start, state_out, (int64_t)0, B, N, game_stride_bytes, vec16);
 }
 
 }  // extern "C"

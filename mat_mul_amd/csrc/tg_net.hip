@@ -17,14 +17,12 @@
 // RB rows, the rows read from LDS as broadcasts.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 
 #include "../../include/tensor_game.h"
 #include "../../include/tensor_game_net.h"
 #include "tg_device.h"
-
-int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
+#include "tg_host.h"
 
 namespace tg {
 namespace net {
@@ -594,14 +592,6 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
 
 namespace {
 
-constexpr int kMaxLds = 160 * 1024;
-
-int launched(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
-}
-
 int check_cfg(const char* fn, const tg_net_config* c) {
   if (!c) return tg_internal_fail(TG_ERR_INVALID, "%s: null config", fn);
   const int32_t dims[] = {c->S, c->T, c->dim_s, c->c, c->torso_layers, c->torso_heads, c->torso_d, c->torso_ff, c->W,
@@ -622,7 +612,7 @@ int check_cfg(const char* fn, const tg_net_config* c) {
       return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, names[i], dims[i], bound[i], maxs[i]);
   }
   const size_t lt = tg::net::torso_plan(*c).total * sizeof(float), ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
-  if (lt > kMaxLds || ld > kMaxLds)
+  if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: the LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB", fn,
                             lt, ld);
   return TG_OK;
@@ -632,40 +622,22 @@ int check_common(const char* fn, const tg_net_config* c, const float* w, int64_t
   if (int rc = check_cfg(fn, c)) return rc;
   if (B < 0 || B > (1LL << 30)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld out of range", fn, (long long)B);
   if (!w) return tg_internal_fail(TG_ERR_INVALID, "%s: null weights", fn);
-  if (reinterpret_cast<uintptr_t>(w) & 3) return tg_internal_fail(TG_ERR_INVALID, "%s: weights not 4-byte aligned", fn);
-  return TG_OK;
-}
-
-bool misaligned(const void* p, int bytes) { return p && (reinterpret_cast<uintptr_t>(p) % bytes) != 0; }
-
-// the > 64 KiB dynamic LDS opt-in, once per (kernel, device)
-int lds_opt_in(const char* fn, const void* kernel, int which, size_t bytes) {
-  static std::atomic<unsigned> done[2][64];
-  if (bytes <= 64 * 1024) return TG_OK;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (done[which][dev].load(std::memory_order_relaxed)) return TG_OK;
-  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  done[which][dev].store(1, std::memory_order_relaxed);
+  if (!aligned(w, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: weights not 4-byte aligned", fn);
   return TG_OK;
 }
 
 int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
   // rows per workgroup: up to 8 samples of one game, fewer when the plan would not fit in LDS
   int R = a.k < 8 ? a.k : 8;
-  while (R > 1 && tg::net::dec_plan(a.c, R).total * sizeof(float) > static_cast<size_t>(kMaxLds)) --R;
+  while (R > 1 && tg::net::dec_plan(a.c, R).total * sizeof(float) > static_cast<size_t>(tg::kMaxDynamicLds)) --R;
   a.R = R;
   a.chunks = (a.k + R - 1) / R;
   if (a.B * a.chunks > INT32_MAX)
     return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn,
                             (long long)a.B, a.chunks);
   const size_t lds = tg::net::dec_plan(a.c, R).total * sizeof(float);
-  if (int rc = lds_opt_in(fn, reinterpret_cast<const void*>(tg::net::net_decode_kernel), 1, lds)) return rc;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::net::net_decode_kernel, dim3(static_cast<unsigned>(a.B * a.chunks)), dim3(tg::net::NT), lds, st,
-                     a);
-  return launched(fn);
+  if (int rc = lds_opt_in<tg::net::net_decode_kernel>(fn, lds)) return rc;
+  return launch(fn, tg::net::net_decode_kernel, static_cast<unsigned>(a.B * a.chunks), tg::net::NT, lds, st, a);
 }
 
 }  // namespace
@@ -691,15 +663,12 @@ int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, i
     return tg_internal_fail(TG_ERR_INVALID, "%s: frames_is_i8=%d (0 float32, 1 int8)", fn, frames_is_i8);
   if (B == 0) return TG_OK;
   if (!frames || !scalars || !ee) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames, scalars or ee", fn);
-  if (misaligned(frames, frames_is_i8 ? 1 : 4) || misaligned(scalars, 4) || misaligned(ee, 4))
+  if (!aligned(frames, frames_is_i8 ? 1 : 4) || !aligned(scalars, 4) || !aligned(ee, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
   tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B};
   const size_t lds = tg::net::torso_plan(*cfg).total * sizeof(float);
-  if (int rc = lds_opt_in(fn, reinterpret_cast<const void*>(tg::net::net_torso_kernel), 0, lds)) return rc;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::net::net_torso_kernel, dim3(static_cast<unsigned>(B)), dim3(tg::net::NT), lds,
-                     static_cast<hipStream_t>(stream), a);
-  return launched(fn);
+  if (int rc = lds_opt_in<tg::net::net_torso_kernel>(fn, lds)) return rc;
+  return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);
 }
 
 // PolicyHead.fwd_infer + ValueHead + value_risk_mgmt, model.py:234-261, 266-280, 322-324 (AlphaTensor.fwd_infer :347-356)
@@ -712,7 +681,7 @@ int tg_net_sample(const tg_net_config* cfg, const float* w, const float* ee, con
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: k=%d outside [1, TG_NET_MAX_SAMPLES=%d]", fn, k, TG_NET_MAX_SAMPLES);
   if (B == 0) return TG_OK;
   if (!ee || (!rows && !uniforms)) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee, or null rows without uniforms", fn);
-  if (misaligned(ee, 4) || misaligned(rows, 8) || misaligned(uniforms, 4) || misaligned(probs, 4) || misaligned(q, 4))
+  if (!aligned(ee, 4) || !aligned(rows, 8) || !aligned(uniforms, 4) || !aligned(probs, 4) || !aligned(q, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: ee, rows, uniforms, probs or q not aligned to their elements", fn);
   tg::net::DecArgs a{};
   a.c = *cfg;
@@ -740,7 +709,7 @@ int tg_net_logits(const tg_net_config* cfg, const float* w, const float* ee, con
   if (int rc = check_common(fn, cfg, w, B)) return rc;
   if (B == 0) return TG_OK;
   if (!ee || !g_action) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee or g_action", fn);
-  if (misaligned(ee, 4) || misaligned(g_action, 8) || misaligned(oo, 4) || misaligned(zz0, 4) || misaligned(q, 4))
+  if (!aligned(ee, 4) || !aligned(g_action, 8) || !aligned(oo, 4) || !aligned(zz0, 4) || !aligned(q, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: ee, g_action, oo, zz0 or q not aligned to their elements", fn);
   tg::net::DecArgs a{};
   a.c = *cfg;

@@ -16,7 +16,6 @@
 
 #include <cmath>
 
-#include "../../include/tensor_game_demos.h"
 #include "../../include/tensor_game_replay.h"
 #include "tg_items.h"
 
@@ -269,11 +268,11 @@ namespace {
 struct MixKernels {
   static constexpr const char* kName = "tg_replay_items";
   template <typename OutT, typename Acc>
-  static auto s4() { return tg::items_s4_kernel<tg::MixedRows, OutT, Acc, tg::MixArgs>; }
+  static constexpr auto s4() { return tg::items_s4_kernel<tg::MixedRows, OutT, Acc, tg::MixArgs>; }
   template <int S, typename OutT>
-  static auto mfma() { return tg::items_mfma_kernel<tg::MixedRows, S, OutT, tg::MixArgs>; }
+  static constexpr auto mfma() { return tg::items_mfma_kernel<tg::MixedRows, S, OutT, tg::MixArgs>; }
   template <typename OutT>
-  static auto exact() { return tg::items_exact_kernel<tg::MixedRows, OutT, tg::MixArgs>; }
+  static constexpr auto exact() { return tg::items_exact_kernel<tg::MixedRows, OutT, tg::MixArgs>; }
 };
 
 int check_buffer(const char* fn, const char* what, const tg_replay_buffer* b) {
@@ -287,8 +286,7 @@ int check_buffer(const char* fn, const char* what, const tg_replay_buffer* b) {
     return tg_internal_fail(TG_ERR_INVALID, "%s: %s S=%d outside [1,%d]", fn, what, b->S, TG_MAX_S);
   if (!b->frames || !b->tokens || !b->rewards || !b->length || !b->offset || !b->ring)
     return tg_internal_fail(TG_ERR_INVALID, "%s: null %s buffer array", fn, what);
-  if ((reinterpret_cast<uintptr_t>(b->rewards) | reinterpret_cast<uintptr_t>(b->length)) % 4 ||
-      (reinterpret_cast<uintptr_t>(b->offset) | reinterpret_cast<uintptr_t>(b->ring)) % 8)
+  if (!aligned(b->rewards, 4) || !aligned(b->length, 4) || !aligned(b->offset, 8) || !aligned(b->ring, 8))
     return tg_internal_fail(TG_ERR_INVALID, "%s: %s buffer arrays not aligned to their elements", fn, what);
   return TG_OK;
 }
@@ -308,19 +306,14 @@ extern "C" int tg_replay_add(const tg_replay_buffer* buf, const int8_t* states, 
   if (B == 0) return TG_OK;
   if (!states || !policy || !rewards || !lengths)
     return tg_internal_fail(TG_ERR_INVALID, "%s: null states, policy, rewards or lengths", fn);
-  if (reinterpret_cast<uintptr_t>(policy) % 4 || reinterpret_cast<uintptr_t>(rewards) % 4 ||
-      reinterpret_cast<uintptr_t>(lengths) % 8)
+  if (!aligned(policy, 4) || !aligned(rewards, 4) || !aligned(lengths, 8))
     return tg_internal_fail(TG_ERR_INVALID, "%s: policy, rewards or lengths not aligned to their elements", fn);
   const tg::AddArgs p{*buf, states, policy, rewards, lengths, B, n_logits, select, status};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t copies = select ? 1 : (B < buf->C ? B : buf->C);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::replay_plan_kernel, dim3(1), dim3(tg::kScanBlock), 0, st, p);
-  hipLaunchKernelGGL(tg::replay_copy_kernel, dim3(static_cast<unsigned>(copies)), dim3(tg::kBlock), 0, st, p);
-  hipLaunchKernelGGL(tg::replay_scan_kernel, dim3(1), dim3(tg::kScanBlock), 0, st, *buf);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
+  if (int rc = launch(fn, tg::replay_plan_kernel, 1, tg::kScanBlock, 0, st, p)) return rc;
+  if (int rc = launch(fn, tg::replay_copy_kernel, static_cast<unsigned>(copies), tg::kBlock, 0, st, p)) return rc;
+  return launch(fn, tg::replay_scan_kernel, 1, tg::kScanBlock, 0, st, *buf);
 }
 
 extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int64_t n_demos, int R, int S,
@@ -330,18 +323,7 @@ extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int6
                                void* frames_out, float* scalars_out, int8_t* actions_out, float* rewards_out,
                                uint8_t* overflow, uint32_t* status, tg_stream_t stream) {
   const char* fn = "tg_replay_items";
-  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (R < 1 || R > TG_DEMO_MAX_ACTIONS)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: R=%d outside [1,%d]", fn, R, TG_DEMO_MAX_ACTIONS);
-  if (T < 1 || T > TG_DEMO_MAX_T) return tg_internal_fail(TG_ERR_INVALID, "%s: T=%d outside [1,%d]", fn, T, TG_DEMO_MAX_T);
-  if (n_demos < 0 || n_demos > INT64_MAX / R)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: n_demos=%lld out of range", fn, (long long)n_demos);
-  const int64_t N3 = static_cast<int64_t>(S) * S * S;
-  if (target_stride_bytes < N3)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: target_stride_bytes=%lld < S^3=%lld", fn, (long long)target_stride_bytes,
-                            (long long)N3);
-  if (out_dtype < 0 || out_dtype > 3)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: out_dtype=%d (0 f32, 1 f16, 2 bf16, 3 int8)", fn, out_dtype);
+  if (int rc = check_items(fn, n_demos, R, S, target_stride_bytes, T, out_dtype)) return rc;
   const tg_replay_buffer* bufs[2] = {played, best};
   const char* names[2] = {"played", "best"};
   for (int q = 0; q < 2; ++q) {
@@ -357,13 +339,6 @@ extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int6
   } else if (direct_kind < TG_REPLAY_SYNTH || direct_kind > TG_REPLAY_BEST) {
     return tg_internal_fail(TG_ERR_INVALID, "%s: direct_kind=%d outside [0,2]", fn, direct_kind);
   }
-  if (N < 0 || N > INT64_MAX / (T * N3)) return tg_internal_fail(TG_ERR_INVALID, "%s: N=%lld out of range", fn, (long long)N);
-  if (N == 0) return TG_OK;
-  if (!item_idx || !frames_out) return tg_internal_fail(TG_ERR_INVALID, "%s: null item_idx or frames_out", fn);
-  if (n_demos > 0 && (!tokens || !targets)) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens or targets", fn);
-  const int esize = out_dtype == 3 ? 1 : out_dtype == 0 ? 4 : 2;
-  if (reinterpret_cast<uintptr_t>(frames_out) % esize)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_out not aligned to its %d-byte elements", fn, esize);
   tg::MixArgs x{};
   for (int q = 0; q < 2; ++q)
     if (bufs[q]) x.buf[q] = tg::BufView{bufs[q]->frames, bufs[q]->tokens, bufs[q]->rewards, bufs[q]->offset,
@@ -372,13 +347,7 @@ extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int6
   x.src = src;
   x.len_data = len_data;
   x.direct_kind = direct_kind;
-  tg::ItemArgs a{tokens, targets, n_demos, target_stride_bytes, item_idx, N, frames_out, scalars_out, actions_out,
-                 rewards_out, overflow, status, R, S, T, shift, 0, 0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (out_dtype) {
-    case 0: return dispatch_items<float, MixKernels>(a, st, x);
-    case 1: return dispatch_items<__half, MixKernels>(a, st, x);
-    case 2: return dispatch_items<__hip_bfloat16, MixKernels>(a, st, x);
-    default: return dispatch_items<int8_t, MixKernels>(a, st, x);
-  }
+  const tg::ItemArgs a{tokens, targets, n_demos, target_stride_bytes, item_idx, N, frames_out, scalars_out, actions_out,
+                       rewards_out, overflow, status, R, S, T, shift, 0, 0};
+  return run_items<MixKernels>(a, out_dtype, static_cast<hipStream_t>(stream), x);
 }

@@ -21,8 +21,7 @@
 #include "../../include/tensor_game.h"
 #include "../../include/tensor_game_search.h"
 #include "tg_device.h"
-
-int tg_internal_fail(int code, const char* fmt, ...);  // tg_kernels.hip
+#include "tg_host.h"
 
 namespace tg {
 namespace search {
@@ -613,14 +612,6 @@ __global__ __launch_bounds__(kBlock) void policy_kernel(tg_search_forest f, floa
 
 namespace {
 
-int launched(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tg_internal_fail(TG_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TG_OK;
-}
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_forest(const char* fn, const tg_search_forest* f) {
   if (!f) return tg_internal_fail(TG_ERR_INVALID, "%s: null forest", fn);
   if (f->B < 0 || f->S < 1 || f->S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: bad B=%lld or S=%d", fn, (long long)f->B, f->S);
@@ -640,16 +631,21 @@ int check_forest(const char* fn, const tg_search_forest* f) {
                         f->depth, f->flags, f->attempt, f->traj_frames, f->traj_node, f->traj_choice};
   for (const void* p : need)
     if (!p) return tg_internal_fail(TG_ERR_INVALID, "%s: null forest array", fn);
-  if (!a16(f->node_frames) || !a16(f->root_frames) || !a16(f->leaf_frames) || !a16(f->traj_frames))
+  if (!aligned(f->node_frames, 16) || !aligned(f->root_frames, 16) || !aligned(f->leaf_frames, 16) ||
+      !aligned(f->traj_frames, 16))
     return tg_internal_fail(TG_ERR_INVALID, "%s: frame arrays must be 16-byte aligned", fn);
-  if ((reinterpret_cast<uintptr_t>(f->node_key) | reinterpret_cast<uintptr_t>(f->child_key) |
-       reinterpret_cast<uintptr_t>(f->index_key) | reinterpret_cast<uintptr_t>(f->root_key) |
-       reinterpret_cast<uintptr_t>(f->leaf_key)) & 7)
+  if (!aligned(f->node_key, 8) || !aligned(f->child_key, 8) || !aligned(f->index_key, 8) || !aligned(f->root_key, 8) ||
+      !aligned(f->leaf_key, 8))
     return tg_internal_fail(TG_ERR_INVALID, "%s: key arrays must be 8-byte aligned", fn);
   return TG_OK;
 }
 
-dim3 grid_games(int64_t n) { return dim3(static_cast<unsigned>((n + tg::search::kWaves - 1) / tg::search::kWaves)); }
+// one wavefront per game (or per (game, move) for the policy)
+template <typename K, typename... A>
+int launch_games(const char* fn, K kernel, int64_t n, tg_stream_t stream, const A&... args) {
+  return launch(fn, kernel, static_cast<unsigned>((n + tg::search::kWaves - 1) / tg::search::kWaves), tg::kBlock, 0,
+                static_cast<hipStream_t>(stream), args...);
+}
 
 }  // namespace
 
@@ -661,10 +657,7 @@ int tg_search_reset(const tg_search_forest* f, const int8_t* states, int n_sim, 
   if (n_sim < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: n_sim=%d < 0", fn, n_sim);
   if (f->B == 0) return TG_OK;
   if (!states) return tg_internal_fail(TG_ERR_INVALID, "%s: null states", fn);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::search::reset_kernel, grid_games(f->B), dim3(tg::kBlock), 0, static_cast<hipStream_t>(stream),
-                     *f, states, n_sim);
-  return launched(fn);
+  return launch_games(fn, tg::search::reset_kernel, f->B, stream, *f, states, n_sim);
 }
 
 int tg_search_select(const tg_search_forest* f, void* model_in, int out_dtype, float* scalars, tg_stream_t stream) {
@@ -673,10 +666,7 @@ int tg_search_select(const tg_search_forest* f, void* model_in, int out_dtype, f
   if (model_in && (out_dtype < 0 || out_dtype > 2))
     return tg_internal_fail(TG_ERR_INVALID, "%s: out_dtype must be 0 (f32), 1 (f16) or 2 (bf16)", fn);
   if (f->B == 0) return TG_OK;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::search::select_kernel, grid_games(f->B), dim3(tg::kBlock), 0, static_cast<hipStream_t>(stream),
-                     *f, model_in, out_dtype, scalars);
-  return launched(fn);
+  return launch_games(fn, tg::search::select_kernel, f->B, stream, *f, model_in, out_dtype, scalars);
 }
 
 int tg_search_commit(const tg_search_forest* f, const int8_t* tokens, const float* leaf_q, const float* prior,
@@ -685,10 +675,7 @@ int tg_search_commit(const tg_search_forest* f, const int8_t* tokens, const floa
   if (int rc = check_forest(fn, f)) return rc;
   if (f->B == 0) return TG_OK;
   if (!tokens || !leaf_q) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens or leaf_q", fn);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::search::commit_kernel, grid_games(f->B), dim3(tg::kBlock), 0, static_cast<hipStream_t>(stream),
-                     *f, tokens, leaf_q, prior, mask);
-  return launched(fn);
+  return launch_games(fn, tg::search::commit_kernel, f->B, stream, *f, tokens, leaf_q, prior, mask);
 }
 
 int tg_search_advance(const tg_search_forest* f, int n_sim, tg_stream_t stream) {
@@ -696,10 +683,7 @@ int tg_search_advance(const tg_search_forest* f, int n_sim, tg_stream_t stream) 
   if (int rc = check_forest(fn, f)) return rc;
   if (n_sim < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: n_sim=%d < 0", fn, n_sim);
   if (f->B == 0) return TG_OK;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::search::advance_kernel, grid_games(f->B), dim3(tg::kBlock), 0, static_cast<hipStream_t>(stream),
-                     *f, n_sim);
-  return launched(fn);
+  return launch_games(fn, tg::search::advance_kernel, f->B, stream, *f, n_sim);
 }
 
 int tg_search_policy(const tg_search_forest* f, float* policy, int n_logits, int n_bar, tg_stream_t stream) {
@@ -709,10 +693,7 @@ int tg_search_policy(const tg_search_forest* f, float* policy, int n_logits, int
   if (n_bar < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: n_bar=%d < 1", fn, n_bar);
   if (f->B == 0) return TG_OK;
   if (!policy) return tg_internal_fail(TG_ERR_INVALID, "%s: null policy", fn);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(tg::search::policy_kernel, grid_games(f->B * f->max_actions), dim3(tg::kBlock), 0,
-                     static_cast<hipStream_t>(stream), *f, policy, n_logits, n_bar);
-  return launched(fn);
+  return launch_games(fn, tg::search::policy_kernel, f->B * f->max_actions, stream, *f, policy, n_logits, n_bar);
 }
 
 }  // extern "C"

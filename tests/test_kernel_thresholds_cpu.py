@@ -21,7 +21,7 @@ PINS = [
     ("tg_kernels.hip", r"const int64_t out_bytes16 = B \* T \* (\d+) \* \(out_dtype \? 2 : 4\);", 4096, "step_emit_s16_two_launches"),
     # the fused generator declines an S=9 target whose game stride is not a multiple of 16 (or R beyond 256): only then does
     # tg_gen_demos_i8 reach the capped basis-token grid
-    ("tg_kernels.hip", r"if \(!aligned16\(target\) \|\| stride % (\d+) != 0\) return 0;", 16, "gen_s9_basis_grid_cap"),
+    ("tg_kernels.hip", r"if \(!aligned\(target, 16\) \|\| stride % (\d+) != 0\) return 0;", 16, "gen_s9_basis_grid_cap"),
     ("tg_kernels.hip", r"if \(!\(S == 9 \|\| S == 16 \|\| S == 25\) \|\| R > (\d+) \|\| B == 0\) return 0;", 256,
      "gen_s9_basis_grid_cap"),
     ("tg_kernels.hip", r"constexpr int64_t kS4TokenWaitBytes = (\d+)ll << 20;", 384, "step_s4_nt_loads, step_s4_token_wait"),
@@ -41,16 +41,17 @@ PINS = [
     # copy: by the bytes of both buffers, and the byte path's grid
     ("tg_kernels.hip", r"else if \(both > \((\d+)ll << 20\) \|\| TG_SWITCH\(\"TG_COPY_NT2\"\)\)", 640, "copy_s16_nt1, copy_s16_nt2"),
     ("tg_kernels.hip", r"else if \(both > \((\d+)ll << 20\) \|\| TG_SWITCH\(\"TG_COPY_NT1\"\)\)", 256, "copy_s16_nt1"),
-    ("tg_kernels.hip", r"copy_bytes_kernel, dim3\(capped_grid\(B > (\d+) \?", 65536, "copy_bytes_grid_cap"),
+    ("tg_kernels.hip", r"copy_bytes_kernel, grid_for\(B, (\d+)\)", 65536, "copy_bytes_grid_cap"),
     # grid caps
-    ("tg_kernels.hip", r"done_kernel, dim3\(capped_grid\(blocks > (\d+) \?", 8192, "done_s4_grid_cap, done_s16_grid_cap"),
-    ("tg_kernels.hip", r"tg_reset_broadcast_i8[\s\S]*?broadcast_kernel, dim3\(capped_grid\(blocks > (\d+) \?", 8192,
+    ("tg_kernels.hip", r"done_kernel, grid_for\(blocks, (\d+)\)", 8192, "done_s4_grid_cap, done_s16_grid_cap"),
+    ("tg_kernels.hip", r"tg_reset_broadcast_i8[\s\S]*?broadcast_kernel, grid_for\(blocks, (\d+)\)", 8192,
      "reset_broadcast_s4_grid_cap"),
     ("tg_aux.hip", r"hash_kernel, dim3\(grid_for\(blocks, (\d+)\)\)", 8192, "hash_s4_grid_cap"),
     ("tg_aux.hip", r"const dim3 grid\(grid_for\(\(n \+ tg::kBlock - 1\) / tg::kBlock, (\d+)\)\)", 8192, "seen_grid_cap"),
     ("tg_aux.hip", r"grid_for\(S == 4 \? \(B \+ 3\) / 4 : B, 1 << (\d+)\)", 20, "rank_s4_grid_cap, rank_s5_grid_cap"),
     ("tg_gen.hip", r"gen_tokens_kernel<ST, M>\), dim3\(grid_for\(wgs > (\d+) \?", 16384, "gen_s4_tokens_grid_cap"),
-    ("tg_gen.hip", r"if \(nvec >= \(int64_t\)tg::kBlock \* 16 \* (\d+)\) TG_GT\(4, 16\)", 2048, "gen_s4_tokens_grid_cap"),
+    ("tg_gen.hip", r"if \(nvec >= \(int64_t\)tg::kBlock \* 16 \* (\d+)\) rc = tokens\(launch_tokens<4, 16>\)", 2048,
+     "gen_s4_tokens_grid_cap"),
     ("tg_gen.hip", r"const dim3 bgrid\(grid_for\(B > (\d+) \?", 16384, "gen_s4_basis_grid_cap"),
     ("tg_gen.hip", r"const dim3 mgrid\(grid_for\(B > (\d+) \?", 65536, "gen_s9_basis_grid_cap"),
     ("tg_gen.hip", r"const dim3 mgrid\(grid_for\(B > (\d+)LL \* cus \?", 4, "change_basis_s16_rounds"),
