@@ -2,7 +2,7 @@
 """bench.py -- env steps/s of the tensor-game step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--samples n] [--scaling weak|strong] [--global-batch G]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is ONE launch of the hot-path kernel (tg_step_i8, in place) over the whole batch of games resident in
 HBM.  Workloads:
@@ -20,7 +20,8 @@ bracketed by a barrier + torch.cuda.synchronize() on both sides; per sample the 
 (each consumes the state the previous one wrote), replayed as one hipGraph, and cycle through an action schedule
 that returns every game to its start state, so the timed region checks itself.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: set-up, the W warm-up steps, the
+timed samples, the self-check, --dump-outputs and the line with the contract fields.  With --full, the line carries as well
   roofline     -- the step kernel against the 8 TB/s HBM peak.  `avg_launch_us` is measured with HIP events on the
                   launch stream around each of the `samples` replays of the K-launch graph, enqueued back to back
                   (no host sync in between, so the one-off submit latency of a replay overlaps the previous one),
@@ -33,7 +34,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline -- the oracle's reference-dtype torch-CPU port (oracle/ref_dtype_torch.py) timed on this box's
                   host cores on a bounded sample of the same workload;
   also         -- the same measurement on the other single-GPU BASELINE configs, SURVEY 8(d)'s dense-state inputs,
-                  HBM-streaming batches, the fused step_many and the generator (rank 0, N=1 only).
+                  HBM-streaming batches, the fused step_many and the generator (rank 0, N=1 only);
+  N > 1        -- the sharded extras (sharded_extras) and the per-rank event timings.
 """
 from __future__ import annotations
 
@@ -248,10 +250,11 @@ class StepTimer:
         take = (lambda t: t.clone()) if games is None else (lambda t: t.index_select(0, games))
         return {"state": take(self.state), "done": take(self.done), "overflow": take(self.ovf)}
 
-    def measure(self, K, W, samples, sync=None, keep=False, keep_games=None):
+    def measure(self, K, W, samples, sync=None, keep=False, keep_games=None, events=True):
         """Returns dict(wall_s=[...], event_ms=[...], ok).  Wall samples are sync-bracketed; event samples come
-        from a second pass with the replays enqueued back to back.  keep=True adds `outputs`: self.outputs(keep_games)
-        as the last step of the last wall sample left them (copied after that sample's clock stopped)."""
+        from a second pass with the replays enqueued back to back (events=False: no such pass, no event keys).
+        keep=True adds `outputs`: self.outputs(keep_games) as the last step of the last wall sample left them (copied
+        after that sample's clock stopped)."""
         self.eager(W)
         torch.cuda.synchronize(self.dev)
         p0 = self.pos
@@ -273,6 +276,8 @@ class StepTimer:
         last = self.outputs(keep_games) if keep else None
         if sync:
             sync()
+        if not events:
+            return {"wall_s": walls, "ok": self.check(), "outputs": last}
         self._rewind(p0)
         torch.cuda.synchronize(self.dev)
         # kernel time.  One replay of a hipGraph costs a fixed ~13 us on top of its nodes (ROCm 7.2; measured by
@@ -583,11 +588,12 @@ def demo_rank(S):
     return 7 if S == 4 else 8
 
 
-def sharded_step(group, G, S, dev, mode, K, W, samples, seed=0, keep=False):
+def sharded_step(group, G, S, dev, mode, K, W, samples, seed=0, keep=False, events=True):
     """One sharded measurement, every rank taking part: G games in total, this rank's contiguous range of global ids,
     W warm-up + `samples` samples of exactly K in-place steps, each bracketed by barrier + synchronize; the wall time
-    per sample and the event-timed launch time are MAX-reduced over the ranks.  keep=True: res["outputs"] holds this
-    rank's outputs of the last timed step (dump_games chooses the games)."""
+    per sample and the event-timed launch time are MAX-reduced over the ranks (events=False: the wall time only, the
+    launch times are None).  keep=True: res["outputs"] holds this rank's outputs of the last timed step (dump_games
+    chooses the games)."""
     from mat_mul_amd import shard_range
 
     lo, hi = shard_range(G, group.rank, group.world)
@@ -595,13 +601,17 @@ def sharded_step(group, G, S, dev, mode, K, W, samples, seed=0, keep=False):
     start, sched, _ = make_demo_schedule(B, S, demo_rank(S), dev, seed, lo)
     tm = StepTimer(start, sched, dev, mode)
     games = dump_games(B, S, group.world, dev) if keep else None
-    res = tm.measure(K, W, samples, sync=group.barrier, keep=keep, keep_games=games)
+    res = tm.measure(K, W, samples, sync=group.barrier, keep=keep, keep_games=games, events=events)
     if keep:
         res["outputs_games"] = games
-    my_launch_us = statistics.median(res["event_ms"]) * 1e3 / K
-    my_fixed_us = statistics.median(res["run_ms_lead_in_only"]) * 1e3 - res["lead_in"] * my_launch_us
-    reduced = group.max_over_ranks(*res["wall_s"], 0.0 if res["ok"] else 1.0, my_launch_us, my_fixed_us)
-    walls, bad, launch_us_max, fixed_us_max = list(reduced[:-3]), reduced[-3], reduced[-2], reduced[-1]
+    if events:
+        my_launch_us = statistics.median(res["event_ms"]) * 1e3 / K
+        my_fixed_us = statistics.median(res["run_ms_lead_in_only"]) * 1e3 - res["lead_in"] * my_launch_us
+        reduced = group.max_over_ranks(*res["wall_s"], 0.0 if res["ok"] else 1.0, my_launch_us, my_fixed_us)
+        walls, bad, launch_us_max, fixed_us_max = list(reduced[:-3]), reduced[-3], reduced[-2], reduced[-1]
+    else:
+        reduced = group.max_over_ranks(*res["wall_s"], 0.0 if res["ok"] else 1.0)
+        walls, bad, launch_us_max, fixed_us_max = list(reduced[:-1]), reduced[-1], None, None
     if bad:
         raise SystemExit(f"bench self-check failed (S={S}, {G} games over {group.world} ranks): the state did not return "
                          "to its start after full cycles")
@@ -734,8 +744,11 @@ def main(argv=None):
     ap.add_argument("--global-batch", type=int, default=1 << 20, help="games in total under --scaling strong")
     ap.add_argument("--dim", type=int, default=4, help="S of the timed workload (4 = BASELINE config 2 / 4)")
     ap.add_argument("--batch", type=int, default=0, help="games per GPU (default: 65536 for S=4, 8192 for S=16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure what it does not need: the roofline objects, the CPU baseline, the "
+                         "`also` workloads (N=1) and the sharded extras (N>1); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full without the `also` workloads (N=1) or sharded extras (N>1)")
     ap.add_argument("--print-also", action="store_true", help="print the `also` entries as separate lines BEFORE the contract line")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous, shard arithmetic and the JSON line only -- no GPU work (CPU test of the N>1 path)")
@@ -786,7 +799,7 @@ def main(argv=None):
         if rank == 0:
             head["dry_run"] = True
             head["config"].update({"batch_rank0": B, "last_game_id": int(tot)})
-            if world > 1:  # the shard arithmetic of the extras an N>1 run measures (sharded_extras)
+            if world > 1 and args.full:  # the shard arithmetic of the extras an N>1 run measures (sharded_extras)
                 head["shards"] = {}
                 for key, (g2, s2) in {"s16_weak": (8192 * world, 16), "s16_strong": (8192, 16), "s4_strong": (1 << 20, 4),
                                       "s4_weak": (65536 * world, 4)}.items():
@@ -813,60 +826,23 @@ def main(argv=None):
     group.barrier()
     from mat_mul_amd import _lib  # noqa: F401  (raises if libtensorgame.so or a symbol is missing: no CPU path)
 
-    m = sharded_step(group, G, S, dev, args.mode, args.steps, args.warmup, args.samples, keep=bool(args.dump_outputs))
-    res, sched, walls, wall = m["res"], m["sched"], m["walls"], m["wall"]
-    extras = sharded_extras(group, world, dev, args.mode, args.steps, m) if world > 1 and not args.no_also else {}
+    m = sharded_step(group, G, S, dev, args.mode, args.steps, args.warmup, args.samples, keep=bool(args.dump_outputs),
+                     events=args.full)
+    res, walls, wall = m["res"], m["walls"], m["wall"]
+    extras = sharded_extras(group, world, dev, args.mode, args.steps, m) if world > 1 and args.full and not args.no_also else {}
     if args.dump_outputs and rank != 0:
         write_outputs(args.dump_outputs, res, lo, rank, world)
 
     if rank == 0:
-        need = needed_bytes_per_launch(B, S, sched)
-        copy = copy_ceiling_gbps(B, S, dev)
-        hbm_copy = hbm_copy_ceiling(dev) if world == 1 and not args.no_also else None
         out = dict(head)
         out.update({"value": round(G * args.steps / wall, 1), "ms_per_step": round(wall * 1e3 / args.steps, 6)})
         out["config"] = dict(head["config"], timing=f"{args.samples} samples of exactly {args.steps} steps, each bracketed by "
                              f"barrier + synchronize, max over ranks per sample, median over samples",
                              wall_us_per_sample=[round(w * 1e6, 1) for w in walls])
-        out["roofline"] = roofline(B, S, args.steps, res["event_ms"], need, copy, res=res, hbm_copy=hbm_copy)
-        if world > 1:
-            out["per_rank"] = {"event_launch_us_max_over_ranks": round(m["launch_us_max"], 3),
-                               "graph_replay_fixed_cost_us_max_over_ranks": round(m["fixed_us_max"], 2),
-                               "event_steps_per_s": round(G / (m["launch_us_max"] * 1e-6), 1),
-                               "wall_us_per_step": round(wall * 1e6 / args.steps, 3)}
-            out.update(extras)
-        if not args.no_cpu_baseline:  # rank 0, after every timed region; a shorter sample when other ranks wait for it
-            out["cpu_baseline"] = cpu_baseline(G // world, S, budget_s=12.0 if world == 1 else 5.0, sweep_s=1.0 if world == 1 else 0.4)
-        also = []
-        if world == 1 and not args.no_also:
-            also = also_lines(S, G, dev, args.mode, hbm_copy)
-            # BASELINE's metric names S=4 and S=16: surface config 3 at the top level as well
-            for a3 in also:
-                wl = a3["workload"]
-                if wl.startswith("S=16 batch=8192 (BASELINE config 3)"):
-                    out["value_s16"] = a3["value"]
-                    out["ms_per_step_s16"] = round(a3["roofline"]["avg_launch_us"] * 1e-3, 6)
-                    out["roofline_s16"] = a3["roofline"]
-                elif wl.startswith("S=4 batch=131072 (BASELINE config 4 per-GPU share"):
-                    out.setdefault("cfg4_one_gpu", {})["share_of_8_launch_us"] = a3["roofline"]["avg_launch_us"]
-                elif wl.startswith("S=4 batch=1048576 (BASELINE config 4 on ONE GPU"):
-                    out.setdefault("cfg4_one_gpu", {})["whole_launch_us"] = a3["roofline"]["avg_launch_us"]
-                elif wl.startswith("STREAMED tg_step_stream_i8: S=4 batch=131072"):
-                    out.setdefault("cfg4_one_gpu", {})["streamed_share_of_8_us_per_step"] = a3["us_per_step"]
-                elif wl.startswith("STREAMED tg_step_stream_i8: S=4 batch=1048576"):
-                    out.setdefault("cfg4_one_gpu", {})["streamed_whole_us_per_step"] = a3["us_per_step"]
-                elif wl.startswith("GENERATOR tg_gen_demos_i8") and "basis" not in wl:
-                    out["generator_cfg5"] = {"us_per_launch": a3["us_per_launch"], "demos_per_s": a3["value"],
-                                             "bound": a3.get("bound"), "valu_issue_frac": a3.get("valu_issue_frac")}
-            c4 = out.get("cfg4_one_gpu", {})
-            if "share_of_8_launch_us" in c4 and "whole_launch_us" in c4:  # what 8 GPUs can reach on kernel time
-                c4["predicted_speedup_8gpu_event"] = round(c4["whole_launch_us"] / c4["share_of_8_launch_us"], 3)
-            if "streamed_share_of_8_us_per_step" in c4 and "streamed_whole_us_per_step" in c4:
-                c4["predicted_speedup_8gpu_streamed"] = round(c4["streamed_whole_us_per_step"] / c4["streamed_share_of_8_us_per_step"], 3)
-            out["also_ok"] = {"entries": len(also), "failed": [a["workload"][:60] for a in also if not a.get("ok", True)]}
+        also = full_figures(out, m, extras, world, dev, args) if args.full else []
         if args.dump_outputs:
             out["dumped_outputs"] = write_outputs(args.dump_outputs, res, lo, rank, world)
-        if also or world > 1:
+        if also or (args.full and world > 1):
             out["also_file"] = write_side_file(out, also)
         if args.print_also:
             for a in also:
@@ -875,6 +851,53 @@ def main(argv=None):
     group.barrier()
     group.close()
     return 0
+
+
+def full_figures(out, m, extras, world, dev, args):
+    """--full, rank 0, after the headline's timed region: the roofline object of the headline workload, the per-rank
+    timings and sharded extras of an N>1 run, the CPU baseline and the `also` workloads of an N=1 run, added to `out`.
+    Returns the `also` entries."""
+    B, S, G, res, wall = m["B"], m["S"], m["G"], m["res"], m["wall"]
+    need = needed_bytes_per_launch(B, S, m["sched"])
+    copy = copy_ceiling_gbps(B, S, dev)
+    hbm_copy = hbm_copy_ceiling(dev) if world == 1 and not args.no_also else None
+    out["roofline"] = roofline(B, S, args.steps, res["event_ms"], need, copy, res=res, hbm_copy=hbm_copy)
+    if world > 1:
+        out["per_rank"] = {"event_launch_us_max_over_ranks": round(m["launch_us_max"], 3),
+                           "graph_replay_fixed_cost_us_max_over_ranks": round(m["fixed_us_max"], 2),
+                           "event_steps_per_s": round(G / (m["launch_us_max"] * 1e-6), 1),
+                           "wall_us_per_step": round(wall * 1e6 / args.steps, 3)}
+        out.update(extras)
+    if not args.no_cpu_baseline:  # rank 0, after every timed region; a shorter sample when other ranks wait for it
+        out["cpu_baseline"] = cpu_baseline(G // world, S, budget_s=12.0 if world == 1 else 5.0, sweep_s=1.0 if world == 1 else 0.4)
+    also = []
+    if world == 1 and not args.no_also:
+        also = also_lines(S, G, dev, args.mode, hbm_copy)
+        # BASELINE's metric names S=4 and S=16: surface config 3 at the top level as well
+        for a3 in also:
+            wl = a3["workload"]
+            if wl.startswith("S=16 batch=8192 (BASELINE config 3)"):
+                out["value_s16"] = a3["value"]
+                out["ms_per_step_s16"] = round(a3["roofline"]["avg_launch_us"] * 1e-3, 6)
+                out["roofline_s16"] = a3["roofline"]
+            elif wl.startswith("S=4 batch=131072 (BASELINE config 4 per-GPU share"):
+                out.setdefault("cfg4_one_gpu", {})["share_of_8_launch_us"] = a3["roofline"]["avg_launch_us"]
+            elif wl.startswith("S=4 batch=1048576 (BASELINE config 4 on ONE GPU"):
+                out.setdefault("cfg4_one_gpu", {})["whole_launch_us"] = a3["roofline"]["avg_launch_us"]
+            elif wl.startswith("STREAMED tg_step_stream_i8: S=4 batch=131072"):
+                out.setdefault("cfg4_one_gpu", {})["streamed_share_of_8_us_per_step"] = a3["us_per_step"]
+            elif wl.startswith("STREAMED tg_step_stream_i8: S=4 batch=1048576"):
+                out.setdefault("cfg4_one_gpu", {})["streamed_whole_us_per_step"] = a3["us_per_step"]
+            elif wl.startswith("GENERATOR tg_gen_demos_i8") and "basis" not in wl:
+                out["generator_cfg5"] = {"us_per_launch": a3["us_per_launch"], "demos_per_s": a3["value"],
+                                         "bound": a3.get("bound"), "valu_issue_frac": a3.get("valu_issue_frac")}
+        c4 = out.get("cfg4_one_gpu", {})
+        if "share_of_8_launch_us" in c4 and "whole_launch_us" in c4:  # what 8 GPUs can reach on kernel time (DESIGN.md section 6)
+            c4["predicted_speedup_8gpu_event"] = round(c4["whole_launch_us"] / c4["share_of_8_launch_us"], 3)
+        if "streamed_share_of_8_us_per_step" in c4 and "streamed_whole_us_per_step" in c4:
+            c4["predicted_speedup_8gpu_streamed"] = round(c4["streamed_whole_us_per_step"] / c4["streamed_share_of_8_us_per_step"], 3)
+        out["also_ok"] = {"entries": len(also), "failed": [a["workload"][:60] for a in also if not a.get("ok", True)]}
+    return also
 
 
 def also_lines(S_main, B_main, dev, mode, hbm_copy=None):

@@ -10,11 +10,11 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-also"
+LEAN="--full --no-cpu-baseline --no-also"   # --full: the roofline objects (event-timed pass, copy ceiling) in every line
 PART=${2:-all}   # "a": steps 0-3 (bench runs, kernel traces, HBM traffic counters); "b": the rest; "c": step 10 only; default all
 if [ "$PART" = "all" ] || [ "$PART" = "a" ]; then
-# 0. unprofiled: the driver's own command (what BENCH_rNN.json records) and the default command, full JSON lines
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err || exit 1
+# 0. unprofiled: the driver's own command (what BENCH_rNN.json records) with --full and the default command, full JSON lines
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err || exit 1
 cp $R/bench_also.json $OUT/bench_also_driver_cmd.json
 python3 $R/bench.py $LEAN > $OUT/bench_default_lean.json 2> $OUT/bench_default_lean.err || exit 1
 # 1. kernel trace + stats of the driver's command and of the default command (hipGraph replay), headline workload only

@@ -97,11 +97,11 @@ def _last_line(stdout):
 def test_self_launch_two_ranks_dry_run(tmp_path, bench):
     """`python bench.py --gpus 2` with no launcher in the environment starts its two ranks itself and relays
     rank 0's line (dry run: rendezvous over gloo + shard arithmetic, no GPU).  Default at N>1: weak scaling of the
-    N=1 workload (65 536 games per GPU); the line also names the shards of the extras an N>1 run measures."""
+    N=1 workload (65 536 games per GPU); with --full the line also names the shards of the extras such a run measures."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run"],
-                         env=env, capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run",
+                          "--full"], env=env, capture_output=True, text=True, timeout=300, cwd=tmp_path)
     assert res.returncode == 0, res.stderr[-3000:]
     line = _last_line(res.stdout)
     assert len(line) < bench.MAX_LINE_BYTES
@@ -120,6 +120,7 @@ def test_self_launch_two_ranks_dry_run(tmp_path, bench):
     out = json.loads(_last_line(res.stdout))
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 1 << 20 and out["config"]["batch_rank0"] == 1 << 19
     assert "config 4" in out["config"]["workload"]
+    assert "shards" not in out                                   # a plain run measures no extras
 
 
 def _full_object(bench, world):

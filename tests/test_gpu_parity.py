@@ -1291,12 +1291,14 @@ def test_integration_md_stub_runs_against_strassen_golden(golden, tmp_path):
 
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     """`bench.py --dump-outputs DIR` writes what the timed step handed its caller after the last timed step -- state,
-    done and overflow in float32 -- the same files again for the same arguments, equal to the oracle's replay of the
-    bench schedule to that step (W + samples * K steps into it); beyond 64 MB (S=16, 8 192 games) a seeded sample."""
+    done and overflow in float32 -- the same files again for the same arguments and with --full, equal to the oracle's
+    replay of the bench schedule to that step (W + samples * K steps into it); beyond 64 MB (S=16, 8 192 games) a seeded
+    sample."""
     import json, subprocess, sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     W, K, n = 5, 16, 2
+    lines = {}
 
     def run(out, *extra):
         res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
@@ -1305,6 +1307,7 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
         assert res.returncode == 0, res.stderr[-3000:]
         line = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
         assert line["steps"] == K and line["samples"] == n and line["ms_per_step"] > 0
+        lines[out.name] = line
         assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
         return {p.stem: np.load(p) for p in out.iterdir()}
 
@@ -1312,6 +1315,9 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     assert sorted(a) == sorted(b) == ["done", "overflow", "state"]
     for k in a:
         assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert not {"roofline", "cpu_baseline", "also_file"} & set(lines["a"])   # a plain run: the headline alone
+    d = run(tmp_path / "d", "--full")               # --full measures more after the timed steps, which compute the same
+    assert "roofline" in lines["d"] and sorted(d) == sorted(a) and all(np.array_equal(a[k], d[k]) for k in a)
     c = run(tmp_path / "c", "--dim", "16", "--batch", "8192")
     assert sorted(c) == ["done", "game_index", "overflow", "state"] and 0 < len(c["game_index"]) < 8192
     for S, B, got in ((4, 65536, a), (16, 8192, c)):
@@ -1333,14 +1339,15 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
 def test_bench_two_ranks_self_launched_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2` with no launcher: bench.py starts its own ranks (torch.distributed.run children).
     On the one-GPU box both ranks share the GPU and the control plane is gloo (TG_BENCH_BACKEND).  The contract line is
-    the LAST line of stdout, under 4 KB, and carries the sharded extras of an N>1 run: S=16 weak (value_s16) and strong,
-    config 4 strong with its single-GPU denominator, the resident stepper on the share, a short cpu_baseline."""
+    the LAST line of stdout, under 4 KB, and with --full carries the sharded extras of an N>1 run: S=16 weak (value_s16)
+    and strong, config 4 strong with its single-GPU denominator, the resident stepper on the share, a short cpu_baseline;
+    a plain run carries the headline alone."""
     import json, os, subprocess, sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TG_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
-    res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -1364,6 +1371,8 @@ def test_bench_two_ranks_self_launched_on_one_gpu(tmp_path):
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 131072 and out["config"]["batch_per_gpu"] == 65536
+    assert out["value"] > 1e9 and out["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline", "value_s16", "s16_strong", "s4_weak", "s4_strong", "streamed_s4", "also_file"} & set(out)
 
 
 # ------------------------------------------------------------------ alternating sweep direction of tg_step_i8
