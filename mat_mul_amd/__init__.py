@@ -15,9 +15,9 @@ import importlib
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
-           "FusedAlphaTensor", "net"]
+           "FusedAlphaTensor", "net", "FusedTrainer", "train"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -28,6 +28,7 @@ _ATTRS = {
     "GameBuffer": "replay",
     "TensorGameData": "replay",
     "FusedAlphaTensor": "net",
+    "FusedTrainer": "train",
 }
 
 

@@ -117,6 +117,16 @@ NET_SIGNATURES = {
     "tg_net_logits": [_p, _p, _p, _p, _i64, _p, _p, _p, _p],
 }
 
+# name -> argtypes; every symbol include/tensor_game_train.h declares
+TRAIN_SIGNATURES = {
+    "tg_net_train_check": [_p],
+    "tg_net_train_workspace_size": [_p, _i64, _p],
+    "tg_net_loss_grad": [_p, _p, _p, _p, _i, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_float, _u64, _u64, _p, _p, _p,
+                         _i64, _p, _p, _p, _p],
+}
+TG_NET_TRAIN_PARTIALS = 256
+TG_TRAIN_STATUS_BAD_TOKEN = 1
+
 # the supported family of include/tensor_game_net.h
 NET_LIMITS = {"S": 5, "T": 8, "dim_s": 4, "c": 32, "torso_layers": 16, "torso_heads": 8, "torso_d": 64, "torso_ff": 128,
               "W": 64, "heads": 8, "d": 64, "ff": 256, "blocks": 4, "n_steps": 16, "n_logits": 8, "n_hidden": 512,
@@ -159,7 +169,7 @@ def _load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
-                           **NET_SIGNATURES}.items():
+                           **NET_SIGNATURES, **TRAIN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

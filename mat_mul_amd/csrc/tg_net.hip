@@ -23,75 +23,10 @@
 #include "../../include/tensor_game_net.h"
 #include "tg_device.h"
 #include "tg_host.h"
+#include "tg_net_common.h"
 
 namespace tg {
 namespace net {
-
-constexpr int NT = 256;  // threads per workgroup (both kernels)
-
-// ---- blob layout (the header's) ---------------------------------------------------------------------------------------
-struct Mha {
-  const float *ln1w, *ln1b, *ln2w, *ln2b, *q, *k, *v, *li1w, *li1b, *ln3w, *ln3b, *li2w, *li2b, *li3w, *li3b;
-};
-
-__host__ __device__ inline int64_t mha_size(int c1, int c2, int H, int d, int ff) {
-  const int64_t hd = static_cast<int64_t>(H) * d;
-  return 2LL * c1 + 2LL * c2 + c1 * hd + hd * c2 + c2 * hd + hd * c1 + c1 + 2LL * c1 + static_cast<int64_t>(c1) * ff +
-         ff + static_cast<int64_t>(ff) * c1 + c1;
-}
-
-__device__ inline Mha mha_at(const float* p, int c1, int c2, int H, int d, int ff) {
-  const int hd = H * d;
-  Mha m;
-  m.ln1w = p; p += c1;
-  m.ln1b = p; p += c1;
-  m.ln2w = p; p += c2;
-  m.ln2b = p; p += c2;
-  m.q = p; p += c1 * hd;
-  m.k = p; p += hd * c2;
-  m.v = p; p += c2 * hd;
-  m.li1w = p; p += hd * c1;
-  m.li1b = p; p += c1;
-  m.ln3w = p; p += c1;
-  m.ln3b = p; p += c1;
-  m.li2w = p; p += c1 * ff;
-  m.li2b = p; p += ff;
-  m.li3w = p; p += ff * c1;
-  m.li3b = p;
-  return m;
-}
-
-struct Off {                   // float offsets into the blob
-  int64_t t_li1[3], t_li2[3];  // torso input projections
-  int64_t t_layer0, t_layer;   // first torso layer, stride
-  int64_t emb, pos, blk0, blk; // policy
-  int64_t out, v[4];           // policy logits, value MLP
-  int64_t total;
-};
-
-inline Off offsets(const tg_net_config& c) {
-  Off o{};
-  int64_t p = 0;
-  const int64_t S2 = static_cast<int64_t>(c.S) * c.S, cin = static_cast<int64_t>(c.S) * c.T + 1;
-  for (int g = 0; g < 3; ++g) { o.t_li1[g] = p; p += c.dim_s * S2 + S2; }
-  for (int g = 0; g < 3; ++g) { o.t_li2[g] = p; p += cin * c.c + c.c; }
-  o.t_layer0 = p;
-  o.t_layer = mha_size(c.c, c.c, c.torso_heads, c.torso_d, c.torso_ff);
-  p += o.t_layer * c.torso_layers;
-  o.emb = p; p += static_cast<int64_t>(c.n_logits + 1) * c.W;
-  o.pos = p; p += static_cast<int64_t>(c.n_steps) * c.W;
-  o.blk0 = p;
-  o.blk = 2LL * c.W + mha_size(c.W, c.W, c.heads, c.d, c.ff) + 2LL * c.W + mha_size(c.W, c.c, c.heads, c.d, c.ff);
-  p += o.blk * c.blocks;
-  o.out = p; p += static_cast<int64_t>(c.W) * c.n_logits + c.n_logits;
-  const int64_t nh = c.n_hidden;
-  o.v[0] = p; p += c.W * nh + nh;
-  o.v[1] = p; p += nh * nh + nh;
-  o.v[2] = p; p += nh * nh + nh;
-  o.v[3] = p; p += nh * c.n_quantile + c.n_quantile;
-  o.total = p;
-  return o;
-}
 
 // ---- LDS plans (floats) -----------------------------------------------------------------------------------------------
 struct TorsoPlan {
@@ -145,93 +80,6 @@ __host__ __device__ inline DecPlan dec_plan(const tg_net_config& c, int R) {
   p.MISC = p.V2 + (c.n_hidden > c.n_quantile ? c.n_hidden : c.n_quantile);
   p.total = p.MISC + 2 * R;  // pp[R], token[R]
   return p;
-}
-
-// ---- building blocks (all threads of the workgroup call them; each ends without a barrier) -------------------------
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
-
-// Y[r][o] = res2[r][o] + (res[r][o] + act(sum_i X[r][i] * Wt[i][o] + bias[o])) for r < R, o < O.
-template <int RB>
-__device__ inline void mm_rb(const float* X, int ldx, int R, int I, const float* __restrict__ Wt, int ldw, int O,
-                             const float* __restrict__ bias, int act, const float* res, const float* res2, int ldr,
-                             float* Y, int ldy) {
-  const int groups = (R + RB - 1) / RB;
-  for (int it = threadIdx.x; it < O * groups; it += NT) {
-    const int o = it % O, r0 = (it / O) * RB;
-    const float* xr[RB];
-#pragma unroll
-    for (int u = 0; u < RB; ++u) xr[u] = X + (r0 + u < R ? r0 + u : R - 1) * ldx;
-    float acc[RB];
-#pragma unroll
-    for (int u = 0; u < RB; ++u) acc[u] = 0.f;
-    const float* wp = Wt + o;
-#pragma unroll 8
-    for (int i = 0; i < I; ++i) {
-      const float wv = wp[static_cast<int64_t>(i) * ldw];
-#pragma unroll
-      for (int u = 0; u < RB; ++u) acc[u] = fmaf(xr[u][i], wv, acc[u]);
-    }
-    const float b = bias ? bias[o] : 0.f;
-#pragma unroll
-    for (int u = 0; u < RB; ++u) {
-      const int r = r0 + u;
-      if (r >= R) break;
-      float v = acc[u] + b;
-      if (act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-      else if (act == ACT_RELU) v = v > 0.f ? v : 0.f;
-      if (res) v = res[r * ldr + o] + v;
-      if (res2) v = res2[r * ldr + o] + v;
-      Y[r * ldy + o] = v;
-    }
-  }
-}
-
-__device__ inline void mm(const float* X, int ldx, int R, int I, const float* Wt, int ldw, int O, const float* bias,
-                          float* Y, int ldy, int act = ACT_NONE, const float* res = nullptr,
-                          const float* res2 = nullptr, int ldr = 0) {
-  const int work = R * O;
-  if (work >= 8 * NT) mm_rb<8>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
-  else if (work >= 4 * NT) mm_rb<4>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
-  else if (work >= 2 * NT) mm_rb<2>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
-  else mm_rb<1>(X, ldx, R, I, Wt, ldw, O, bias, act, res, res2, ldr, Y, ldy);
-}
-
-// LayerNorm (eps 1e-5, biased variance) of R rows of n <= 64 floats: 32 lanes per row, two passes.
-__device__ inline void layernorm(const float* X, int ldx, int R, int n, const float* __restrict__ w,
-                                 const float* __restrict__ b, float* Y, int ldy) {
-  const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
-  for (int r = team; r < R; r += NT / 32) {
-    const float* x = X + r * ldx;
-    const float x0 = lane < n ? x[lane] : 0.f, x1 = lane + 32 < n ? x[lane + 32] : 0.f;
-    float s = x0 + x1;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) s += __shfl_xor(s, m, 32);
-    const float mean = s / static_cast<float>(n);
-    const float d0 = lane < n ? x0 - mean : 0.f, d1 = lane + 32 < n ? x1 - mean : 0.f;
-    float v = d0 * d0 + d1 * d1;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
-    const float rstd = 1.f / sqrtf(v / static_cast<float>(n) + 1e-5f);
-    if (lane < n) Y[r * ldy + lane] = d0 * rstd * w[lane] + b[lane];
-    if (lane + 32 < n) Y[r * ldy + lane + 32] = d1 * rstd * w[lane + 32] + b[lane + 32];
-  }
-}
-
-// softmax in place over rows of n entries (one thread per row)
-__device__ inline void softmax_rows(float* A, int rows, int n, int ld) {
-  for (int r = threadIdx.x; r < rows; r += NT) {
-    float* a = A + r * ld;
-    float m = a[0];
-    for (int j = 1; j < n; ++j) m = fmaxf(m, a[j]);
-    float s = 0.f;
-    for (int j = 0; j < n; ++j) {
-      const float e = expf(a[j] - m);
-      a[j] = e;
-      s += e;
-    }
-    const float inv = 1.f / s;
-    for (int j = 0; j < n; ++j) a[j] *= inv;
-  }
 }
 
 // ---- torso --------------------------------------------------------------------------------------------------------

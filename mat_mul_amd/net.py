@@ -92,9 +92,10 @@ def _mha(sd: Mapping, p: str, H: int, out: list) -> None:
             g("li3.weight").T, g("li3.bias")]
 
 
-def pack_weights(sd: Mapping, cfg: Mapping[str, int]) -> np.ndarray:
+def pack_weights(sd: Mapping, cfg: Mapping[str, int], fold_pos: bool = True) -> np.ndarray:
     """The float32 weight blob of include/tensor_game_net.h.  The one folding (pos_enc + pos_enc_fix) is done in
-    float64 and rounded once."""
+    float64 and rounded once.  ``fold_pos=False`` packs the training parameter vector of include/tensor_game_train.h
+    instead, whose pos slot holds pos_enc alone."""
     g = lambda n: _np64(sd[n])  # noqa: E731
     parts: list = []
     for i in range(3):
@@ -103,7 +104,7 @@ def pack_weights(sd: Mapping, cfg: Mapping[str, int]) -> np.ndarray:
         parts += [g(f"torso.li2.{i}.weight").T, g(f"torso.li2.{i}.bias")]
     for l in range(cfg["torso_layers"]):
         _mha(sd, f"torso.blocks.{l}.mha.", cfg["torso_heads"], parts)
-    parts += [g(_P + "emb1.weight"), g(_P + "pos_enc") + g(_P + "pos_enc_fix")]
+    parts += [g(_P + "emb1.weight"), g(_P + "pos_enc") + g(_P + "pos_enc_fix") if fold_pos else g(_P + "pos_enc")]
     for b in range(cfg["blocks"]):
         p = f"{_P}blocks.{b}."
         parts += [g(p + "ln1.weight"), g(p + "ln1.bias")]

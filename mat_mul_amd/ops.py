@@ -22,6 +22,7 @@ __all__ = [
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
+    "net_train_check", "net_train_workspace_size", "net_loss_grad",
 ]
 
 
@@ -897,3 +898,66 @@ def net_logits(cfg, w, ee, g_action):
         call("tg_net_logits", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q),
              _stream(dev))
     return oo, zz0, q
+
+
+# ---- include/tensor_game_train.h ---------------------------------------------------------------------------------------
+def net_train_check(cfg) -> None:
+    """Raise TensorGameError (naming the bound) unless ``cfg`` is in the training family (tg_net_train_check)."""
+    call("tg_net_train_check", C.byref(cfg))
+
+
+def net_train_workspace_size(cfg, B: int) -> int:
+    """Bytes of workspace tg_net_loss_grad needs for B games."""
+    out = C.c_int64(0)
+    call("tg_net_train_workspace_size", C.byref(cfg), int(B), C.byref(out))
+    return int(out.value)
+
+
+def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad=None, losses=None,
+                  status=None, weight_pol: float = 1.0, weight_val: float = 1000.0, dropout_p: float = 0.0,
+                  seed: int = 0, call_idx: int = 0, keep_in=None, keep_out=None):
+    """AlphaTensor.fwd_train's losses and the gradient of weight_pol * l_pol + weight_val * l_val (tg_net_loss_grad).
+
+    theta float32 (the blob layout, pos slot = pos_enc), pos_fix float32 (n_steps, W), frames (B,T,S,S,S) float32 or
+    int8, scalars float32 (B,dim_s), g_action int8 (B,n_steps), g_value float32 (B,1), workspace uint8 of at least
+    net_train_workspace_size bytes.  grad (like theta) None means a loss-only call.  keep_in / keep_out: uint8
+    (B, blocks, 2, n_steps, W) or None.  Returns (losses float32 [2], status int32 [1]); no host sync."""
+    dev = _net_blob(cfg, theta)
+    B = frames.shape[0] if frames.dim() == 5 else -1
+    want = (B, cfg.T, cfg.S, cfg.S, cfg.S)
+    if frames.dtype not in (torch.float32, torch.int8) or tuple(frames.shape) != want or frames.device != dev:
+        raise TensorGameError("net_loss_grad", -1, f"frames must be float32 or int8 (B,T,S,S,S) = {want[1:]} per game "
+                              f"on {dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    if B < 1:
+        raise TensorGameError("net_loss_grad", -1, "B must be at least 1")
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise TensorGameError("net_loss_grad", -1, f"dropout_p={dropout_p} outside [0, 1)")
+    frames = frames.contiguous()
+    pos_fix = _flag(pos_fix, (cfg.n_steps, cfg.W), torch.float32, dev, "pos_fix")
+    scalars = _flag(scalars, (B, cfg.dim_s), torch.float32, dev, "scalars")
+    g_action = _flag(g_action, (B, cfg.n_steps), torch.int8, dev, "g_action")
+    g_value = _flag(g_value, (B, 1), torch.float32, dev, "g_value")
+    mask = (B, cfg.blocks, 2, cfg.n_steps, cfg.W)
+    keep_in = _flag(keep_in, mask, torch.uint8, dev, "keep_in")
+    keep_out = _flag(keep_out, mask, torch.uint8, dev, "keep_out")
+    if grad is not None:
+        grad = _flag(grad, tuple(theta.shape), torch.float32, dev, "grad")
+    if losses is None:
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+    losses = _flag(losses, (2,), torch.float32, dev, "losses")
+    status = _flag(status, (1,), torch.int32, dev, "status")
+    need = net_train_workspace_size(cfg, B)
+    _need_gpu(workspace, "workspace")
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
+            workspace.numel() < need or workspace.device != dev:
+        raise TensorGameError("net_loss_grad", -1, f"workspace must be contiguous uint8 of at least {need} bytes on "
+                              f"{dev}, got {workspace.dtype} {tuple(workspace.shape)} on {workspace.device}")
+    with torch.cuda.device(dev):
+        call("tg_net_loss_grad", C.byref(cfg), _ptr(theta), _ptr(pos_fix), _ptr(frames),
+             1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(g_action), _ptr(g_value), B,
+             float(weight_pol), float(weight_val), float(dropout_p), int(seed) & (2 ** 64 - 1),
+             int(call_idx) & (2 ** 64 - 1), _ptr(keep_in), _ptr(keep_out), _ptr(workspace), workspace.numel(),
+             _ptr(grad), _ptr(losses), _ptr(status), _stream(dev))
+    return losses, status
