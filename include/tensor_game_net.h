@@ -66,6 +66,14 @@ extern "C" {
 #define TG_NET_MAX_QUANTILE 16  /* n_quantile */
 #define TG_NET_MAX_SAMPLES 64   /* k = n_samples (TG_SEARCH_MAX_K) */
 
+/* One more state size outside S <= TG_NET_MAX_S: the 3x3 matmul tensor, S = 9 exactly, with n_steps up to
+ * TG_NET_WIDE_MAX_STEPS (= 3S).  Every other TG_NET_MAX_* bound applies, and so does the LDS plan, which grows with S:
+ * at S = 9 the torso holds 3 x 81 rows and the decoder's cross-attention J = 243 keys, so only small c, W and n_steps
+ * fit.  The training app's configuration at S = 9 (c 8, W 32, T 2, 8 torso layers, n_steps 27) takes 100 KiB (torso)
+ * and 127 KiB (decoder, R = 8). */
+#define TG_NET_WIDE_S 9
+#define TG_NET_WIDE_MAX_STEPS 27
+
 /* The dimensions of one network, all inferred from a state_dict (mat_mul_amd/net.py). */
 typedef struct tg_net_config {
   int32_t S, T, dim_s, c;                                     /* dim_3d, dim_t, dim_s, dim_c */

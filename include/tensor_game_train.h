@@ -58,8 +58,12 @@ extern "C" {
 /* 0 if cfg is inside the training family, TG_ERR_UNSUPPORTED naming the bound otherwise (TG_ERR_INVALID for a null
  * pointer or a dimension < 1).  The family is tg_net_check's, narrowed by LDS: the torso workgroup holds the three grids,
  * the pair's activations and one attention head's forward and backward buffers; the decoder workgroup holds the game's
- * ee and dL/dee, the inputs of every block, the mask and one attention block's buffers; each must fit in 160 KiB.  Host
- * only. */
+ * ee and dL/dee, the inputs of every block, the mask and one attention block's buffers; each must fit in 160 KiB.
+ * At S = TG_NET_WIDE_S the whole pair and the cross-attention's keys and values do not fit (263 and 272 KiB at the
+ * training app's configuration), so there the torso runs each pair's attention block over a chunk of its S independent
+ * sequences at a time (the fewest chunks that fit: 3 of 3 sequences, 116 KiB, at that configuration), and the decoder's
+ * cross-attention keeps no keys or values (scores (Wk_h^T q) . y_j, output Wv_h (sum_j a_j y_j), 148 KiB); a
+ * configuration fits when one sequence at a time does.  Host only. */
 int tg_net_train_check(const tg_net_config* cfg);
 
 /* *bytes = the workspace tg_net_loss_grad needs for B >= 1 games (grad or not):

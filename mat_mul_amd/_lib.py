@@ -132,6 +132,8 @@ NET_LIMITS = {"S": 5, "T": 8, "dim_s": 4, "c": 32, "torso_layers": 16, "torso_he
               "W": 64, "heads": 8, "d": 64, "ff": 256, "blocks": 4, "n_steps": 16, "n_logits": 8, "n_hidden": 512,
               "n_quantile": 16}
 TG_NET_MAX_SAMPLES = 64
+# the one state size outside NET_LIMITS["S"]: the 3x3 matmul tensor, with its own n_steps bound
+TG_NET_WIDE_S, TG_NET_WIDE_MAX_STEPS = 9, 27
 
 
 class NetConfig(C.Structure):

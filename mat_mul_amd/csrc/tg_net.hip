@@ -454,8 +454,18 @@ int check_cfg(const char* fn, const tg_net_config* c) {
                          "TG_NET_MAX_HEADS", "TG_NET_MAX_D", "TG_NET_MAX_TORSO_FF", "TG_NET_MAX_W", "TG_NET_MAX_HEADS",
                          "TG_NET_MAX_D", "TG_NET_MAX_FF", "TG_NET_MAX_BLOCKS", "TG_NET_MAX_STEPS", "TG_NET_MAX_LOGITS",
                          "TG_NET_MAX_HIDDEN", "TG_NET_MAX_QUANTILE"};
-  for (int i = 0; i < 17; ++i) {
+  for (int i = 0; i < 17; ++i)
     if (dims[i] < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, names[i], dims[i]);
+  // S <= TG_NET_MAX_S as for every bound, or exactly TG_NET_WIDE_S with n_steps <= TG_NET_WIDE_MAX_STEPS instead
+  const bool wide = c->S == TG_NET_WIDE_S;
+  if (c->S > TG_NET_MAX_S && !wide)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: dim_3d=%d above TG_NET_MAX_S=%d, and not exactly TG_NET_WIDE_S=%d",
+                            fn, c->S, TG_NET_MAX_S, TG_NET_WIDE_S);
+  if (wide && c->n_steps > TG_NET_WIDE_MAX_STEPS)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE_MAX_STEPS=%d (dim_3d=%d)", fn,
+                            c->n_steps, TG_NET_WIDE_MAX_STEPS, c->S);
+  for (int i = 1; i < 17; ++i) {
+    if (wide && i == 13) continue;  // n_steps: its bound at S = TG_NET_WIDE_S is above
     if (dims[i] > maxs[i])
       return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, names[i], dims[i], bound[i], maxs[i]);
   }

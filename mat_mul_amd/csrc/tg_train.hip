@@ -73,6 +73,31 @@ __host__ __device__ inline Scr scr_plan(const Geo& g) {
   return s;
 }
 
+// The same block without keys and values (the decoder's cross-attention at S = TG_NET_WIDE_S, 243 keys): as in
+// tg_net.hip's decoder, a head's scores are (Wk_h^T q_a) . yn_b and its output Wv_h (sum_b p_ab yn_b), so a head holds
+// c2-wide vectors per query (QK, YB and their gradients DQK, DYB) instead of M x d keys, values and their gradients.
+// XN .. DF sit where scr_plan puts them; the head's buffers start where scr_plan's do; DO reuses O and DQ reuses Q.
+struct ScrKV {
+  int Q, O, QK, YB, DYB, DQK, P, DS, total;
+};
+
+__host__ __device__ inline ScrKV scr_plan_kv(const Geo& g) {
+  const Scr s = scr_plan(g);
+  const int N = g.nseq * g.Lx, PS = g.nseq * g.Lx * g.Ly;
+  ScrKV k;
+  k.Q = s.Q;
+  k.O = k.Q + N * g.d;
+  k.QK = k.O + N * g.d;
+  k.YB = k.QK + N * g.c2;
+  k.DYB = k.YB + N * g.c2;
+  k.DQK = k.DYB + N * g.c2;
+  k.P = k.DQK + N * g.c2;
+  k.DS = k.P + PS;
+  const int heads_end = k.DS + PS, mlp_end = s.DF + N * g.ff;
+  k.total = heads_end > mlp_end ? heads_end : mlp_end;
+  return k;
+}
+
 // ---- building blocks (all threads call them; each ends without a barrier) -------------------------------------------
 // Y[r][i] = (Y[r][i] +) sum_o X[r][o] * Wt[i][o]   (X @ Wt^T, Wt rows contiguous)
 __device__ inline void mmT(const float* X, int ldx, int R, int O, const float* __restrict__ Wt, int ldw, int I, float* Y,
@@ -211,18 +236,72 @@ __device__ inline void head_fwd(const Geo& g, const Mha& w, int h, const float* 
   }
 }
 
+// One head's forward without keys and values (scr_plan_kv): Q (N x d), QK = Q Wk_h (N x c2), the attention P as in
+// head_fwd, YB = P YN (N x c2) and O = YB Wv_h (N x d).
+__device__ inline void head_fwd_kv(const Geo& g, const Mha& w, int h, const float* XN, const float* YN, float* sc) {
+  const ScrKV S = scr_plan_kv(g);
+  const int N = g.nseq * g.Lx, d = g.d, hd = g.H * d, c2 = g.c2, Lx = g.Lx, Ly = g.Ly;
+  float *Q = sc + S.Q, *QK = sc + S.QK, *YB = sc + S.YB, *P = sc + S.P, *O = sc + S.O;
+  net::mm(XN, g.c1, N, g.c1, w.q + h * d, hd, d, nullptr, Q, d);
+  __syncthreads();
+  net::mm(Q, d, N, d, w.k + h * d * c2, c2, c2, nullptr, QK, c2);  // k stored [hd][c2]: row e of head h is Wk_h[e]
+  __syncthreads();
+  const float sd = sqrtf(static_cast<float>(d));
+  for (int it = threadIdx.x; it < g.nseq * Lx * Ly; it += NT) {
+    const int b = it % Ly, a = (it / Ly) % Lx, s = it / (Lx * Ly);
+    if (g.causal && b > a) continue;
+    const float* qk = QK + (s * Lx + a) * c2;
+    const float* y = YN + (s * Ly + b) * c2;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int i = 0; i < c2; ++i) acc = fmaf(qk[i], y[i], acc);
+    P[it] = acc / sd;
+  }
+  __syncthreads();
+  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
+    float* p = P + row * Ly;
+    const int n = g.causal ? row % Lx + 1 : Ly;
+    float m = p[0];
+    for (int j = 1; j < n; ++j) m = fmaxf(m, p[j]);
+    float s = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const float e = expf(p[j] - m);
+      p[j] = e;
+      s += e;
+    }
+    const float inv = 1.f / s;
+    for (int j = 0; j < n; ++j) p[j] *= inv;
+    for (int j = n; j < Ly; ++j) p[j] = 0.f;
+  }
+  __syncthreads();
+  for (int it = threadIdx.x; it < N * c2; it += NT) {
+    const int i = it % c2, r = it / c2, s = r / Lx;
+    const float* pr = P + r * Ly;
+    const float* y = YN + s * Ly * c2 + i;
+    float acc = 0.f;
+    for (int b = 0; b < Ly; ++b) acc = fmaf(pr[b], y[b * c2], acc);
+    YB[it] = acc;
+  }
+  __syncthreads();
+  net::mm(YB, c2, N, c2, w.v + h * d, hd, d, nullptr, O, d);
+}
+
 // MultiHeadAttention.forward (model.py:44-67) up to li2: XN, YN, H1 = X + li1(heads), MN = ln3(H1), F = li2(MN) (before
-// the GELU).  With OUT, also OUT = H1 + li3(gelu(F)) (F then holds gelu(F)).  Ends with a barrier.
+// the GELU).  With OUT, also OUT = H1 + li3(gelu(F)) (F then holds gelu(F)).  KV: the heads without keys and values
+// (scr_plan_kv).  Ends with a barrier.
+template <bool KV = false>
 __device__ inline void mha_fwd(const Geo& g, const Mha& w, const float* X, const float* Y, float* OUT, float* sc) {
   const Scr S = scr_plan(g);
   const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, c1 = g.c1, d = g.d;
-  float *XN = sc + S.XN, *YN = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *F = sc + S.F, *O = sc + S.O;
+  float *XN = sc + S.XN, *YN = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *F = sc + S.F,
+        *O = sc + (KV ? scr_plan_kv(g).O : S.O);
   net::layernorm(X, c1, N, c1, w.ln1w, w.ln1b, XN, c1);
   net::layernorm(Y, g.c2, M, g.c2, w.ln2w, w.ln2b, YN, g.c2);
   for (int it = threadIdx.x; it < N * c1; it += NT) H1[it] = X[it] + w.li1b[it % c1];
   __syncthreads();
   for (int h = 0; h < g.H; ++h) {
-    head_fwd(g, w, h, XN, YN, sc);
+    if constexpr (KV) head_fwd_kv(g, w, h, XN, YN, sc);
+    else head_fwd(g, w, h, XN, YN, sc);
     __syncthreads();
     net::mm(O, d, N, d, w.li1w + h * d * c1, c1, c1, nullptr, H1, c1, net::ACT_NONE, H1, nullptr, c1);
     __syncthreads();
@@ -237,8 +316,74 @@ __device__ inline void mha_fwd(const Geo& g, const Mha& w, const float* X, const
   }
 }
 
+// The backward of head h without keys and values (scr_plan_kv), from DH1 = dL/dH1: recomputes the head's forward, adds
+// the gradients of li1's slice, Wq_h, Wk_h and Wv_h into gw, dL/dXN into DXN and dL/dYN into DYN.  Ends with a barrier.
+//   dO = DH1 li1_h^T;  dYB = dO Wv_h^T, dWv_h += YB^T dO;  dP_ab = dYB_a . yn_b;  dS = P (dP - rowsum(P dP)) / sqrt(d);
+//   dQK = dS YN, dWk_h += Q^T dQK, dQ = dQK Wk_h;  dYN_b += sum_a (P_ab dYB_a + dS_ab QK_a).
+__device__ inline void head_bwd_kv(const Geo& g, const Mha& w, const GMha& gw, int h, const float* XN, const float* YN,
+                                   const float* DH1, float* DXN, float* DYN, float* sc) {
+  const ScrKV S = scr_plan_kv(g);
+  const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, c1 = g.c1, c2 = g.c2, d = g.d, hd = g.H * d, Lx = g.Lx, Ly = g.Ly;
+  float *Q = sc + S.Q, *O = sc + S.O, *QK = sc + S.QK, *YB = sc + S.YB, *DYB = sc + S.DYB, *DQK = sc + S.DQK,
+        *P = sc + S.P, *DS = sc + S.DS;
+  float *DO = O, *DQ = Q;
+  head_fwd_kv(g, w, h, XN, YN, sc);
+  __syncthreads();
+  wgrad(O, d, DH1, c1, N, d, c1, gw.li1w + h * d * c1, c1, nullptr);
+  __syncthreads();
+  mmT(DH1, c1, N, c1, w.li1w + h * d * c1, c1, d, DO, d, false);
+  __syncthreads();
+  mmT(DO, d, N, d, w.v + h * d, hd, c2, DYB, c2, false);
+  wgrad(YB, c2, DO, d, N, c2, d, gw.v + h * d, hd, nullptr);
+  __syncthreads();
+  for (int it = threadIdx.x; it < g.nseq * Lx * Ly; it += NT) {  // dP, into DS
+    const int b = it % Ly, a = (it / Ly) % Lx, s = it / (Lx * Ly);
+    const float* dy = DYB + (s * Lx + a) * c2;
+    const float* y = YN + (s * Ly + b) * c2;
+    float acc = 0.f;
+    for (int i = 0; i < c2; ++i) acc = fmaf(dy[i], y[i], acc);
+    DS[it] = acc;
+  }
+  __syncthreads();
+  const float sd = sqrtf(static_cast<float>(d));
+  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
+    const float* p = P + row * Ly;
+    float* ds = DS + row * Ly;
+    float s = 0.f;
+    for (int b = 0; b < Ly; ++b) s = fmaf(p[b], ds[b], s);
+    for (int b = 0; b < Ly; ++b) ds[b] = p[b] * (ds[b] - s) / sd;
+  }
+  __syncthreads();
+  for (int it = threadIdx.x; it < N * c2; it += NT) {
+    const int i = it % c2, r = it / c2, s = r / Lx;
+    const float* ds = DS + r * Ly;
+    float acc = 0.f;
+    for (int b = 0; b < Ly; ++b) acc = fmaf(ds[b], YN[(s * Ly + b) * c2 + i], acc);
+    DQK[it] = acc;
+  }
+  for (int it = threadIdx.x; it < M * c2; it += NT) {
+    const int i = it % c2, rb = it / c2, s = rb / Ly, b = rb % Ly;
+    float acc = 0.f;
+    for (int a = 0; a < Lx; ++a) {
+      const int r = s * Lx + a;
+      acc = fmaf(P[r * Ly + b], DYB[r * c2 + i], acc);
+      acc = fmaf(DS[r * Ly + b], QK[r * c2 + i], acc);
+    }
+    DYN[it] += acc;
+  }
+  __syncthreads();
+  wgrad(Q, d, DQK, c2, N, d, c2, gw.k + h * d * c2, c2, nullptr);
+  __syncthreads();
+  mmT(DQK, c2, N, c2, w.k + h * d * c2, c2, d, DQ, d, false);
+  __syncthreads();
+  wgrad(XN, c1, DQ, d, N, c1, d, gw.q + h * d, hd, nullptr);
+  mmT(DQ, d, N, d, w.q + h * d, hd, c1, DXN, c1, true);
+  __syncthreads();
+}
+
 // The backward of OUT = MHA(X, Y) for dOut: dX += dOUT/dX^T dOut, dY += ..., weight gradients into gw (a partial slab).
-// dY may be dX (self-attention).  Recomputes the forward.  Ends with a barrier.
+// dY may be dX (self-attention).  Recomputes the forward.  KV: the heads without keys and values.  Ends with a barrier.
+template <bool KV = false>
 __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const float* X, const float* Y,
                                const float* dOut, float* dX, float* dY, float* sc) {
   const Scr S = scr_plan(g);
@@ -248,7 +393,7 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
         *DYN = sc + S.DYN, *ST = sc + S.ST, *F = sc + S.F, *DF = sc + S.DF;
   float *Q = sc + S.Q, *K = sc + S.K, *V = sc + S.V, *O = sc + S.O, *DO = sc + S.DO, *DQ = sc + S.DQ, *DK = sc + S.DK,
         *DV = sc + S.DV, *P = sc + S.P, *DS = sc + S.DS;
-  mha_fwd(g, w, X, Y, nullptr, sc);
+  mha_fwd<KV>(g, w, X, Y, nullptr, sc);
   // the MLP: dF = (dOut li3^T) * gelu'(F)
   for (int it = threadIdx.x; it < N * ff; it += NT) {
     const int j = it % ff, r = it / ff;
@@ -278,6 +423,10 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
   __syncthreads();
   const float sd = sqrtf(static_cast<float>(d));
   for (int h = 0; h < g.H; ++h) {
+    if constexpr (KV) {
+      head_bwd_kv(g, w, gw, h, XN, YN, DH1, DXN, DYN, sc);
+      continue;
+    }
     head_fwd(g, w, h, XN, YN, sc);
     __syncthreads();
     wgrad(O, d, DH1, c1, N, d, c1, gw.li1w + h * d * c1, c1, nullptr);
@@ -384,9 +533,10 @@ inline Ws ws_plan(const tg_net_config& c, int64_t B) {
   return w;
 }
 
-__host__ __device__ inline Geo torso_geo(const tg_net_config& c) {
-  return Geo{c.S, 2 * c.S, 2 * c.S, c.c, c.c, c.torso_heads, c.torso_d, c.torso_ff, 0};
+__host__ __device__ inline Geo torso_geo(const tg_net_config& c, int nseq) {
+  return Geo{nseq, 2 * c.S, 2 * c.S, c.c, c.c, c.torso_heads, c.torso_d, c.torso_ff, 0};
 }
+__host__ __device__ inline Geo torso_geo(const tg_net_config& c) { return torso_geo(c, c.S); }
 __host__ __device__ inline Geo self_geo(const tg_net_config& c) {
   return Geo{1, c.n_steps, c.n_steps, c.W, c.W, c.heads, c.d, c.ff, 1};
 }
@@ -398,7 +548,8 @@ struct TPlan {  // torso kernels (floats)
   int G, IN, X, DO, DX, SS, DP, SCR, total;
 };
 
-__host__ __device__ inline TPlan tplan(const tg_net_config& c) {
+// nseq: the sequences of a pair whose attention block runs at once (the scratch's size); c.S = the whole pair
+__host__ __device__ inline TPlan tplan(const tg_net_config& c, int nseq) {
   const int S2 = c.S * c.S, T2 = 2 * S2, cin = c.S * c.T + 1;
   TPlan p;
   p.G = 0;
@@ -409,9 +560,10 @@ __host__ __device__ inline TPlan tplan(const tg_net_config& c) {
   p.SS = p.DX + T2 * c.c;
   p.DP = p.SS + TG_NET_MAX_DIM_S;
   p.SCR = p.DP + 3 * S2;
-  p.total = p.SCR + scr_plan(torso_geo(c)).total;
+  p.total = p.SCR + scr_plan(torso_geo(c, nseq)).total;
   return p;
 }
+__host__ __device__ inline TPlan tplan(const tg_net_config& c) { return tplan(c, c.S); }
 
 struct DPlan {  // decoder kernel (floats)
   int EE, DEE, XS, X, DX, XB, MO, DXB, LG, VH, DZ, KEEP, TOK, SCR, total;
@@ -437,6 +589,27 @@ __host__ __device__ inline DPlan dplan(const tg_net_config& c) {
   p.SCR = p.TOK + 2 * N + 1;
   p.total = p.SCR + (s1.total > s2.total ? s1.total : s2.total);
   return p;
+}
+
+// the same with the cross-attention without keys and values (scr_plan_kv)
+__host__ __device__ inline DPlan dplan_kv(const tg_net_config& c) {
+  DPlan p = dplan(c);
+  const int s1 = scr_plan(self_geo(c)).total, s2 = scr_plan_kv(cross_geo(c)).total;
+  p.total = p.SCR + (s1 > s2 ? s1 : s2);
+  return p;
+}
+
+// S = TG_NET_WIDE_S takes the kernels below made for it: the torso's attention over a chunk of a pair's sequences at a
+// time, and the decoder's cross-attention without keys and values.  Every other S keeps the whole-pair kernels.
+__host__ __device__ inline bool wide(const tg_net_config& c) { return c.S == TG_NET_WIDE_S; }
+
+// Sequences per chunk of the wide torso: the fewest chunks whose plan fits, evened out; 0 if not even one sequence fits.
+inline int torso_chunk(const tg_net_config& c) {
+  int n = c.S;
+  while (n > 0 && tplan(c, n).total * sizeof(float) > static_cast<size_t>(kMaxDynamicLds)) --n;
+  if (n == 0) return 0;
+  const int chunks = (c.S + n - 1) / n;
+  return (c.S + chunks - 1) / chunks;
 }
 
 __device__ inline void game_range(const Args& a, int64_t& g0, int64_t& g1) {
@@ -479,13 +652,16 @@ __device__ inline int pair_row(int r, int S, int m1, int m2) {
 }
 
 // ---- kernel 1: the torso forward, saving each pair's input ----------------------------------------------------------
-__global__ void __launch_bounds__(NT) train_torso_fwd_kernel(Args a) {
+// CHUNKED (S = TG_NET_WIDE_S): a pair's S sequences are independent (layernorm and the MLP are row-wise, attention stays
+// inside a sequence), so its attention block runs over `chunk` sequences at a time with scratch for that many.
+template <bool CHUNKED>
+__device__ inline void torso_fwd(const Args& a, int chunk) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
   const int S = c.S, S2 = S * S, T2 = 2 * S2, C = c.c, cin = S * c.T + 1;
   const int64_t g = blockIdx.x;
   if (g >= a.B) return;
-  const TPlan L = tplan(c);
+  const TPlan L = CHUNKED ? tplan(c, chunk) : tplan(c);
   float *G = lds + L.G, *IN = lds + L.IN, *X = lds + L.X, *OUT = lds + L.DO, *SCR = lds + L.SCR;
   torso_inputs(a, g, IN, lds + L.SS);
   __syncthreads();
@@ -506,7 +682,14 @@ __global__ void __launch_bounds__(NT) train_torso_fwd_kernel(Args a) {
         save[it] = v;
       }
       __syncthreads();
-      mha_fwd(geo, mh, X, X, OUT, SCR);
+      if constexpr (CHUNKED) {
+        for (int s0 = 0; s0 < S; s0 += chunk) {
+          const int r0 = s0 * 2 * S * C;
+          mha_fwd(torso_geo(c, S - s0 < chunk ? S - s0 : chunk), mh, X + r0, X + r0, OUT + r0, SCR);
+        }
+      } else {
+        mha_fwd(geo, mh, X, X, OUT, SCR);
+      }
       for (int it = threadIdx.x; it < T2 * C; it += NT) G[pair_row(it / C, S, m1, m2) * C + it % C] = OUT[it];
       __syncthreads();
     }
@@ -518,13 +701,18 @@ __global__ void __launch_bounds__(NT) train_torso_fwd_kernel(Args a) {
   }
 }
 
+__global__ void __launch_bounds__(NT) train_torso_fwd_kernel(Args a) { torso_fwd<false>(a, 0); }
+__global__ void __launch_bounds__(NT) train_torso_fwd_chunk_kernel(Args a, int chunk) { torso_fwd<true>(a, chunk); }
+
 // ---- kernel 2: the decoder, the losses, the decoder's backward ------------------------------------------------------
-__global__ void __launch_bounds__(NT) train_decode_kernel(Args a) {
+// KV (S = TG_NET_WIDE_S): the cross-attention without keys and values (scr_plan_kv).
+template <bool KV>
+__device__ inline void decode(const Args& a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
   const int W = c.W, C = c.c, H = c.heads, d = c.d, ff = c.ff, J = 3 * c.S * c.S, N = c.n_steps, NL = c.n_logits;
   const int nh = c.n_hidden, nq = c.n_quantile, NB = c.blocks;
-  const DPlan L = dplan(c);
+  const DPlan L = KV ? dplan_kv(c) : dplan(c);
   float *EE = lds + L.EE, *DEE = lds + L.DEE, *XS = lds + L.XS, *X = lds + L.X, *DX = lds + L.DX, *XB = lds + L.XB,
         *MO = lds + L.MO, *DXB = lds + L.DXB, *LG = lds + L.LG, *DZ = lds + L.DZ, *SCR = lds + L.SCR;
   float *A1 = lds + L.VH, *A2 = A1 + nh, *A3 = A2 + nh, *DA = A3 + nh, *DB = DA + nh, *QV = DB + nh, *DQV = QV + nq,
@@ -603,7 +791,7 @@ __global__ void __launch_bounds__(NT) train_decode_kernel(Args a) {
       __syncthreads();
       net::layernorm(X, W, N, W, bp + blkm, bp + blkm + W, XB, W);
       __syncthreads();
-      mha_fwd(g2, a2, XB, EE, MO, SCR);
+      mha_fwd<KV>(g2, a2, XB, EE, MO, SCR);
       for (int it = threadIdx.x; it < N * W; it += NT) X[it] = XB[it] + (k2[it] ? a.scale : 0.f) * MO[it];
       __syncthreads();
     }
@@ -689,7 +877,7 @@ __global__ void __launch_bounds__(NT) train_decode_kernel(Args a) {
         DXB[it] = DX[it];
       }
       __syncthreads();
-      mha_bwd(g2, a2, ga2, XB, EE, MO, DXB, DEE, SCR);
+      mha_bwd<KV>(g2, a2, ga2, XB, EE, MO, DXB, DEE, SCR);
       for (int it = threadIdx.x; it < N * W; it += NT) DX[it] = 0.f;
       __syncthreads();
       ln_bwd(xmid, N, W, bp + blkm, DXB, DX, gp + blkm, gp + blkm + W, SCR);
@@ -718,12 +906,17 @@ __global__ void __launch_bounds__(NT) train_decode_kernel(Args a) {
   }
 }
 
+__global__ void __launch_bounds__(NT) train_decode_kernel(Args a) { decode<false>(a); }
+__global__ void __launch_bounds__(NT) train_decode_kv_kernel(Args a) { decode<true>(a); }
+
 // ---- kernel 3: the torso backward -----------------------------------------------------------------------------------
-__global__ void __launch_bounds__(NT) train_torso_bwd_kernel(Args a) {
+// CHUNKED: as torso_fwd; the chunks of a pair add their weight gradients to the slab one after another, in order.
+template <bool CHUNKED>
+__device__ inline void torso_bwd(const Args& a, int chunk) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
   const int S = c.S, S2 = S * S, T2 = 2 * S2, C = c.c, cin = S * c.T + 1;
-  const TPlan L = tplan(c);
+  const TPlan L = CHUNKED ? tplan(c, chunk) : tplan(c);
   float *DG = lds + L.G, *IN = lds + L.IN, *X = lds + L.X, *DO = lds + L.DO, *DXP = lds + L.DX, *SS = lds + L.SS,
         *DP = lds + L.DP, *SCR = lds + L.SCR;
   float* gs = a.slabs + static_cast<int64_t>(blockIdx.x) * a.off.total;
@@ -753,7 +946,15 @@ __global__ void __launch_bounds__(NT) train_torso_bwd_kernel(Args a) {
           DXP[it] = 0.f;
         }
         __syncthreads();
-        mha_bwd(geo, mh, gm, X, X, DO, DXP, DXP, SCR);
+        if constexpr (CHUNKED) {
+          for (int s0 = 0; s0 < S; s0 += chunk) {
+            const int r0 = s0 * 2 * S * C;
+            mha_bwd(torso_geo(c, S - s0 < chunk ? S - s0 : chunk), mh, gm, X + r0, X + r0, DO + r0, DXP + r0, DXP + r0,
+                    SCR);
+          }
+        } else {
+          mha_bwd(geo, mh, gm, X, X, DO, DXP, DXP, SCR);
+        }
         for (int it = threadIdx.x; it < T2 * C; it += NT) DG[pair_row(it / C, S, m1, m2) * C + it % C] = DXP[it];
         __syncthreads();
       }
@@ -779,6 +980,9 @@ __global__ void __launch_bounds__(NT) train_torso_bwd_kernel(Args a) {
     __syncthreads();
   }
 }
+
+__global__ void __launch_bounds__(NT) train_torso_bwd_kernel(Args a) { torso_bwd<false>(a, 0); }
+__global__ void __launch_bounds__(NT) train_torso_bwd_chunk_kernel(Args a, int chunk) { torso_bwd<true>(a, chunk); }
 
 // ---- kernel 4: the partial slabs, the losses, the status ------------------------------------------------------------
 __global__ void __launch_bounds__(NT) train_reduce_kernel(Args a, int grad_blocks) {
@@ -825,7 +1029,9 @@ namespace {
 
 int check_train_cfg(const char* fn, const tg_net_config* c) {
   if (int rc = tg_net_check(c)) return rc;
-  const size_t lt = tg::train::tplan(*c).total * sizeof(float), ld = tg::train::dplan(*c).total * sizeof(float);
+  const bool wide = tg::train::wide(*c);  // there the torso fits when one sequence at a time does
+  const size_t lt = (wide ? tg::train::tplan(*c, 1) : tg::train::tplan(*c)).total * sizeof(float),
+               ld = (wide ? tg::train::dplan_kv(*c) : tg::train::dplan(*c)).total * sizeof(float);
   if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(TG_ERR_UNSUPPORTED,
                             "%s: the training LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB per workgroup",
@@ -906,6 +1112,25 @@ int tg_net_loss_grad(const tg_net_config* cfg, const float* theta, const float* 
   a.losses = losses;
   a.status = status;
   const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int gb = grad ? static_cast<int>((a.off.total + tg::net::NT - 1) / tg::net::NT) : 0;
+  if (tg::train::wide(*cfg)) {
+    const int chunk = tg::train::torso_chunk(*cfg);
+    const size_t lt = tg::train::tplan(*cfg, chunk).total * sizeof(float),
+                 ld = tg::train::dplan_kv(*cfg).total * sizeof(float);
+    if (int rc = lds_opt_in<tg::train::train_torso_fwd_chunk_kernel>(fn, lt)) return rc;
+    if (int rc = lds_opt_in<tg::train::train_decode_kv_kernel>(fn, ld)) return rc;
+    if (int rc = lds_opt_in<tg::train::train_torso_bwd_chunk_kernel>(fn, lt)) return rc;
+    if (int rc = launch(fn, tg::train::train_torso_fwd_chunk_kernel, static_cast<unsigned>(B), tg::net::NT, lt, st, a,
+                        chunk))
+      return rc;
+    if (int rc = launch(fn, tg::train::train_decode_kv_kernel, static_cast<unsigned>(a.P), tg::net::NT, ld, st, a))
+      return rc;
+    if (grad)
+      if (int rc = launch(fn, tg::train::train_torso_bwd_chunk_kernel, static_cast<unsigned>(a.P), tg::net::NT, lt, st,
+                          a, chunk))
+        return rc;
+    return launch(fn, tg::train::train_reduce_kernel, static_cast<unsigned>(gb + 1), tg::net::NT, 0, st, a, gb);
+  }
   const size_t lt = tg::train::tplan(*cfg).total * sizeof(float), ld = tg::train::dplan(*cfg).total * sizeof(float);
   if (int rc = lds_opt_in<tg::train::train_torso_fwd_kernel>(fn, lt)) return rc;
   if (int rc = lds_opt_in<tg::train::train_decode_kernel>(fn, ld)) return rc;
@@ -915,7 +1140,6 @@ int tg_net_loss_grad(const tg_net_config* cfg, const float* theta, const float* 
   if (grad)
     if (int rc = launch(fn, tg::train::train_torso_bwd_kernel, static_cast<unsigned>(a.P), tg::net::NT, lt, st, a))
       return rc;
-  const int gb = grad ? static_cast<int>((a.off.total + tg::net::NT - 1) / tg::net::NT) : 0;
   return launch(fn, tg::train::train_reduce_kernel, static_cast<unsigned>(gb + 1), tg::net::NT, 0, st, a, gb);
 }
 

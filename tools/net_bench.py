@@ -1,7 +1,7 @@
 """The fused network (include/tensor_game_net.h) against the float32 restatement run eagerly, at the training app's
 configuration (tests/net_ref.CONFIGS["a"]: S 4, T 2, c 8, W 32, 8 + 2 layers, n_steps 12), k = 8.
 
-    python tools/net_bench.py OUT_DIR [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
+    python tools/net_bench.py OUT_DIR [--config a] [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
 
 One process, one GPU.  Per B in {256, 1024, 4096}: FusedAlphaTensor.fwd_infer and the eager Ref.fwd_infer (the
 reference's op structure: the whole prefix rerun at every token step, torch's Categorical) alternate call by call;
@@ -9,6 +9,8 @@ HIP events around each call after warm-up; median, p10 and p90 in microseconds. 
 fused algorithm (the decoder with its cache).  Then one self-play figure: microseconds per simulation of
 search.actor_prediction with net.policy at S = 4, B = 4096.  --fused-only runs the fused calls alone (for a kernel-trace
 run); --kernel-stats merges a rocprofv3 --stats CSV into an existing OUT_DIR/r08_net.json.  Writes OUT_DIR/r08_net.json.
+--config picks another configuration of net_ref.CONFIGS or tests/net_s9_ref.CONFIGS (a9, b9: S = 9); the file is then
+OUT_DIR/r08_net_<config>.json and the self-play figure is skipped.
 """
 from __future__ import annotations
 
@@ -29,6 +31,9 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 from mat_mul_amd import FusedAlphaTensor, search  # noqa: E402
 from net_ref import CONFIGS, Ref, dims, make_inputs, make_weights  # noqa: E402
+from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
+
+CONFIGS = {**CONFIGS, **CONFIGS_S9}
 
 DEV = "cuda:0"
 FP32_PEAK = 157.3e12  # MI355X vector FP32, FLOP/s (FMA = 2)
@@ -76,10 +81,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--kernel-stats")
+    ap.add_argument("--config", default="a", choices=sorted(CONFIGS))
     args = ap.parse_args()
     out = Path(args.out_dir)
     out.mkdir(parents=True, exist_ok=True)
-    path = out / "r08_net.json"
+    path = out / ("r08_net.json" if args.config == "a" else f"r08_net_{args.config}.json")
     if args.kernel_stats:
         res = json.loads(path.read_text())
         with open(args.kernel_stats) as f:
@@ -88,7 +94,7 @@ def main():
         path.write_text(json.dumps(res, indent=1))
         print(json.dumps(rows))
         return
-    cfg = CONFIGS["a"]
+    cfg = CONFIGS[args.config]
     m = dims(cfg)
     k = cfg["n_samples"]
     sd = make_weights(cfg, 11)
@@ -120,7 +126,7 @@ def main():
             row["eager_over_fused"] = statistics.median(te) / statistics.median(tf)
         res["sizes"].append(row)
         print(json.dumps(row), flush=True)
-    if not args.fused_only:
+    if not args.fused_only and args.config == "a":
         B, S, T = 4096, 4, cfg["dim_t"]
         start = torch.from_numpy(np.random.default_rng(0).integers(-1, 2, size=(B, T, S, S, S)).astype(np.int8)).to(DEV)
         n_sim, max_actions = 16, 4

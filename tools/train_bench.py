@@ -2,13 +2,14 @@
 (tests/train_ref.TrainRef: forward plus autograd backward), at the training app's configuration (net_ref.CONFIGS["a"]),
 p = 0.5 dropout.
 
-    python tools/train_bench.py OUT_DIR [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
+    python tools/train_bench.py OUT_DIR [--config a] [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
 
 One process, one GPU.  Per B in {256, 1024, 4096}: FusedTrainer.loss_and_grad, the AdamW step on its parameter vector
 (torch.optim.AdamW, foreach) plus the inference blob refresh, and the eager forward + backward, each timed with HIP
 events around the call after warm-up; median, p10 and p90 in microseconds.  --fused-only runs the fused calls alone (for
 a kernel-trace run); --kernel-stats merges a rocprofv3 --stats CSV into an existing OUT_DIR/r09_train.json.
-Writes OUT_DIR/r09_train.json.
+Writes OUT_DIR/r09_train.json.  --config picks another configuration of net_ref.CONFIGS or tests/net_s9_ref.CONFIGS
+(a9, b9: S = 9); the file is then OUT_DIR/r09_train_<config>.json.
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 from mat_mul_amd import FusedTrainer  # noqa: E402
 from net_ref import CONFIGS, make_weights  # noqa: E402
+from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
 from train_ref import TrainRef, keep_mask, make_batch, multipliers  # noqa: E402
 
 DEV = "cuda:0"
@@ -72,19 +74,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--kernel-stats")
+    ap.add_argument("--config", default="a", choices=sorted({**CONFIGS, **CONFIGS_S9}))
     args = ap.parse_args()
-    out = Path(args.out) / "r09_train.json"
+    out = Path(args.out) / ("r09_train.json" if args.config == "a" else f"r09_train_{args.config}.json")
     if args.kernel_stats:
         res = json.loads(out.read_text())
         res["kernel_stats"] = kernel_stats(args.kernel_stats)
         out.write_text(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res["kernel_stats"], indent=1))
         return
-    cfg = CONFIGS["a"]
+    cfg = {**CONFIGS, **CONFIGS_S9}[args.config]
     sd = make_weights(cfg, 1)
     tr = FusedTrainer.from_state_dict(sd, dropout_p=P_DROP, device=DEV)
     opt = torch.optim.AdamW([tr.params], lr=1e-4)
-    res = {"config": "a", "dropout_p": P_DROP, "torch": torch.__version__,
+    res = {"config": args.config, "dropout_p": P_DROP, "torch": torch.__version__,
            "device": torch.cuda.get_device_name(0), "rows": []}
     for B in (256, 1024, 4096):
         batch = tuple(torch.from_numpy(x).to(DEV) for x in make_batch(cfg, B, B))
