@@ -28,18 +28,27 @@ D_HEAD, MLP_W, N_QUANTILE = 32, 4, 8  # the reference's MultiHeadAttention / Val
 P = "policy_head.predict_action_logits."
 
 
+FIELDS = ("S", "T", "dim_s", "c", "torso_layers", "torso_heads", "torso_d", "torso_ff", "W", "heads", "d", "ff",
+          "blocks", "n_steps", "n_logits", "n_hidden", "n_quantile")  # tg_net_config's, in its order
+
+
 def dims(cfg):
-    """The fused configuration (include/tensor_game_net.h field names) of a reference configuration."""
+    """The fused configuration (include/tensor_game_net.h field names) of a configuration: reference constructor kwargs
+    (``d``, ``w`` and ``n_quantile`` optional: the first two reach the torso's attention only, as in the reference; the
+    policy keeps D_HEAD and MLP_W), or the fused dims themselves (every field of FIELDS)."""
+    if "S" in cfg:
+        return {k: int(cfg[k]) for k in FIELDS}
     W = cfg["n_feats"] * cfg["n_heads"]
     return dict(S=cfg["dim_3d"], T=cfg["dim_t"], dim_s=cfg["dim_s"], c=cfg["dim_c"],
-                torso_layers=cfg.get("n_layers", 8), torso_heads=cfg["n_heads"], torso_d=D_HEAD,
-                torso_ff=MLP_W * cfg["dim_c"], W=W, heads=cfg["n_heads"], d=D_HEAD, ff=MLP_W * W,
+                torso_layers=cfg.get("n_layers", 8), torso_heads=cfg["n_heads"], torso_d=cfg.get("d", D_HEAD),
+                torso_ff=cfg.get("w", MLP_W) * cfg["dim_c"], W=W, heads=cfg["n_heads"], d=D_HEAD, ff=MLP_W * W,
                 blocks=cfg.get("n_layers", 2), n_steps=cfg["n_steps"], n_logits=cfg["n_logits"],
-                n_hidden=cfg["n_hidden"], n_quantile=N_QUANTILE)
+                n_hidden=cfg["n_hidden"], n_quantile=cfg.get("n_quantile", N_QUANTILE))
 
 
 def make_weights(cfg, seed):
-    """state_dict (name -> float32 numpy array) of a reference AlphaTensor with configuration ``cfg``."""
+    """state_dict (name -> float32 numpy array) of a reference AlphaTensor with configuration ``cfg`` (either form of
+    ``dims``)."""
     rng = np.random.default_rng(seed)
     m = dims(cfg)
     sd = {}
@@ -54,17 +63,17 @@ def make_weights(cfg, seed):
         sd[name + ".weight"] = 1.0 + rng.uniform(-0.2, 0.2, n)
         sd[name + ".bias"] = rng.uniform(-0.2, 0.2, n)
 
-    def mha(p, c1, c2, H):
+    def mha(p, c1, c2, H, d, ff):
         ln(p + "ln1", c1)
         ln(p + "ln2", c2)
         for h in range(H):
-            lin(f"{p}heads.{h}.query", c1, D_HEAD, bias=False)
-            lin(f"{p}heads.{h}.key", c2, D_HEAD, bias=False)
-            lin(f"{p}heads.{h}.value", c2, D_HEAD, bias=False)
-        lin(p + "li1", H * D_HEAD, c1)
+            lin(f"{p}heads.{h}.query", c1, d, bias=False)
+            lin(f"{p}heads.{h}.key", c2, d, bias=False)
+            lin(f"{p}heads.{h}.value", c2, d, bias=False)
+        lin(p + "li1", H * d, c1)
         ln(p + "ln3", c1)
-        lin(p + "li2", c1, c1 * MLP_W)
-        lin(p + "li3", c1 * MLP_W, c1)
+        lin(p + "li2", c1, ff)
+        lin(p + "li3", ff, c1)
 
     S, T, c, W = m["S"], m["T"], m["c"], m["W"]
     for i in range(3):
@@ -72,38 +81,39 @@ def make_weights(cfg, seed):
     for i in range(3):
         lin(f"torso.li2.{i}", S * T + 1, c)
     for l in range(m["torso_layers"]):
-        mha(f"torso.blocks.{l}.mha.", c, c, m["torso_heads"])
+        mha(f"torso.blocks.{l}.mha.", c, c, m["torso_heads"], m["torso_d"], m["torso_ff"])
     sd[P + "emb1.weight"] = rng.normal(0.0, 1.0, (m["n_logits"] + 1, W))
     sd[P + "pos_enc"] = rng.uniform(0.0, 1.0, (m["n_steps"], W))
     sd[P + "pos_enc_fix"] = rng.uniform(-1.0, 1.0, (m["n_steps"], W))
     for b in range(m["blocks"]):
         p = f"{P}blocks.{b}."
         ln(p + "ln1", W)
-        mha(p + "att1.", W, W, m["heads"])
+        mha(p + "att1.", W, W, m["heads"], m["d"], m["ff"])
         ln(p + "ln2", W)
-        mha(p + "att2.", W, c, m["heads"])
+        mha(p + "att2.", W, c, m["heads"], m["d"], m["ff"])
     lin(P + "li1", W, m["n_logits"])
     nh = m["n_hidden"]
     lin("value_head.mlp.0", W, nh)
     lin("value_head.mlp.2", nh, nh)
     lin("value_head.mlp.4", nh, nh)
-    lin("value_head.mlp.6", nh, N_QUANTILE)
+    lin("value_head.mlp.6", nh, m["n_quantile"])
     return {k: v.astype(np.float32) for k, v in sd.items()}
 
 
 def make_inputs(cfg, n, seed):
     """n states with entries in {-2..2} (int8 (n,T,S,S,S)) and their scalars float32 (n,dim_s)."""
     rng = np.random.default_rng(seed)
-    S, T = cfg["dim_3d"], cfg["dim_t"]
+    m = dims(cfg)
+    S, T = m["S"], m["T"]
     xx = rng.integers(-2, 3, size=(n, T, S, S, S)).astype(np.int8)
-    ss = rng.integers(0, 12, size=(n, cfg["dim_s"])).astype(np.float32)
+    ss = rng.integers(0, 12, size=(n, m["dim_s"])).astype(np.float32)
     return xx, ss
 
 
 # ---- float64 restatement ---------------------------------------------------------------------------------------------
 class Ref:
-    """The eval-mode forward in float64 torch on ``device``, from a state_dict (numpy or torch values).  ``dtype``
-    float32 gives the eager stand-in of tools/net_bench.py."""
+    """The eval-mode forward in float64 torch on ``device``, from a state_dict (numpy or torch values) and its
+    configuration in either form of ``dims``.  ``dtype`` float32 gives the eager stand-in of tools/net_bench.py."""
 
     def __init__(self, sd, cfg, device="cpu", dtype=torch.float64):
         self.w = {k: torch.as_tensor(np.asarray(v), dtype=dtype, device=device) for k, v in sd.items()}

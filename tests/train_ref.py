@@ -14,8 +14,8 @@ from oracle import tensor_game as O
 
 
 class TrainRef(Ref):
-    """The train-mode loss of a reference AlphaTensor, written from the network's math.  ``w`` holds leaf tensors that
-    require grad (every state_dict entry but the buffer pos_enc_fix)."""
+    """The train-mode loss of a reference AlphaTensor, written from the network's math (``cfg`` in either form of
+    net_ref.dims).  ``w`` holds leaf tensors that require grad (every state_dict entry but the buffer pos_enc_fix)."""
 
     def __init__(self, sd, cfg, device="cpu", dtype=torch.float64):
         super().__init__(sd, cfg, device, dtype)
@@ -50,11 +50,13 @@ class TrainRef(Ref):
         l_pol = torch.nn.functional.cross_entropy(oo.reshape(-1, self.m["n_logits"]), g.reshape(-1), reduction="sum")
         q = self.value(x[:, 0])
         n = q.shape[-1]
-        tau = (torch.arange(n, dtype=self.dtype, device=self.device) + 0.5) / n
+        # the quantile levels and their weights in float32, as the reference's quantile_loss forms them (exact when n
+        # is a power of two)
+        tau = (torch.arange(n, dtype=torch.float32, device=self.device) + 0.5) / n
         dd = gv - q
         ad = dd.abs()
         hh = torch.where(ad < 1.0, 0.5 * dd * dd, ad - 0.5)
-        kk = (tau - (dd > 0).to(self.dtype)).abs()
+        kk = (tau - (dd > 0).float()).abs().to(self.dtype)
         return l_pol, (hh * kk).mean()
 
     def loss_grad(self, xx, ss, g_action, g_value, masks=None, weight_pol=1.0, weight_val=1000.0):
@@ -70,7 +72,7 @@ class TrainRef(Ref):
 def keep_mask(seed, call, B, cfg, p):
     """uint8 (B, blocks, 2, n_steps, W) of the header's keep rule: element (r, blk, which, t, i) is kept iff
     (w >> 8) * 2^-24 >= p, w = word i % 4 of philox4x32_10((r, call, blk*2 + which, t*ceil(W/4) + i//4), seed)."""
-    m = dims(cfg) if "n_feats" in cfg else cfg
+    m = dims(cfg)
     NB, N, W = m["blocks"], m["n_steps"], m["W"]
     nw4 = (W + 3) // 4
     ctr = np.zeros((B, NB * 2, N, nw4, 4), np.uint32)
@@ -92,12 +94,13 @@ def multipliers(keep, p):
 
 def make_batch(cfg, B, seed):
     """int8 states (B,T,S,S,S) in {-2..2}, float32 scalars (B,dim_s), int8 actions (B,n_steps) in [0, n_logits) and
-    float32 rewards (B,1) in [-12, 0]."""
+    float32 rewards (B,1) in [-12, 0], for ``cfg`` in either form of net_ref.dims."""
     rng = np.random.default_rng(seed)
-    S, T = cfg["dim_3d"], cfg["dim_t"]
+    m = dims(cfg)
+    S, T = m["S"], m["T"]
     xx = rng.integers(-2, 3, size=(B, T, S, S, S)).astype(np.int8)
-    ss = rng.integers(0, 12, size=(B, cfg["dim_s"])).astype(np.float32)
-    aa = rng.integers(0, cfg["n_logits"], size=(B, cfg["n_steps"])).astype(np.int8)
+    ss = rng.integers(0, 12, size=(B, m["dim_s"])).astype(np.float32)
+    aa = rng.integers(0, m["n_logits"], size=(B, m["n_steps"])).astype(np.int8)
     rr = -rng.integers(0, 13, size=(B, 1)).astype(np.float32)
     return xx, ss, aa, rr
 
