@@ -74,6 +74,18 @@ extern "C" {
 #define TG_NET_WIDE_S 9
 #define TG_NET_WIDE_MAX_STEPS 27
 
+/* And a second one: the 4x4 matmul tensor, S = 16 exactly, with n_steps up to TG_NET_WIDE2_MAX_STEPS (= 3S); inference
+ * only (tg_net_train_check refuses it).  A whole game's torso does not fit there (344 KiB at the training app's
+ * configuration), and does not have to: the first grid index is a batch index through every attention block of the
+ * torso, so tg_net_torso runs one workgroup per (game, slice i) on the 3S rows (i, m, j) of the three grids.  The torso
+ * term of the LDS check is that slice plan (3S x c grids, four 2S x c buffers, one head's q/k/v or the MLP's hidden
+ * rows or the 3S input rows, one head's 2S x 2S scores); the decoder term is the same plan as at every size, with
+ * J = 768 keys in the cross-attention.  The training app's configuration at S = 16 (c 8, W 32, T 2, 8 torso layers,
+ * n_steps 48) takes 21.5 KiB per slice and 158 KiB in the decoder (R = 4 samples per workgroup; 76 KiB at R = 1).  With
+ * J > 256 keys the decoder's cross-attention softmax runs a 32-lane team per row, its partial sums in a fixed order. */
+#define TG_NET_WIDE2_S 16
+#define TG_NET_WIDE2_MAX_STEPS 48
+
 /* The dimensions of one network, all inferred from a state_dict (mat_mul_amd/net.py). */
 typedef struct tg_net_config {
   int32_t S, T, dim_s, c;                                     /* dim_3d, dim_t, dim_s, dim_c */
@@ -91,7 +103,8 @@ int tg_net_weights_size(const tg_net_config* cfg, int64_t* floats);
 
 /* Torso.forward (model.py:97-123) for B games in ONE launch: frames (B,T,S,S,S) float32 (frames_is_i8 = 0) or int8
  * (frames_is_i8 = 1, converted exactly), scalars float32 (B,dim_s) -> ee float32 (B,3S^2,c) in the reference's order
- * (row i*3S + m*S + j = grid m, row (i, j)).  One workgroup per game; the three grids stay in LDS. */
+ * (row i*3S + m*S + j = grid m, row (i, j)).  One workgroup per game, the three grids in LDS; at S = TG_NET_WIDE2_S one
+ * workgroup per (game, i), which computes rows i*3S .. i*3S + 3S - 1. */
 int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8, const float* scalars,
                  float* ee, int64_t B, tg_stream_t stream);
 

@@ -132,8 +132,10 @@ NET_LIMITS = {"S": 5, "T": 8, "dim_s": 4, "c": 32, "torso_layers": 16, "torso_he
               "W": 64, "heads": 8, "d": 64, "ff": 256, "blocks": 4, "n_steps": 16, "n_logits": 8, "n_hidden": 512,
               "n_quantile": 16}
 TG_NET_MAX_SAMPLES = 64
-# the one state size outside NET_LIMITS["S"]: the 3x3 matmul tensor, with its own n_steps bound
+# the first state size outside NET_LIMITS["S"]: the 3x3 matmul tensor, with its own n_steps bound
 TG_NET_WIDE_S, TG_NET_WIDE_MAX_STEPS = 9, 27
+# and the second: the 4x4 matmul tensor, inference only (the torso runs by slices there)
+TG_NET_WIDE2_S, TG_NET_WIDE2_MAX_STEPS = 16, 48
 
 
 class NetConfig(C.Structure):

@@ -1,11 +1,15 @@
 // Fused eval-mode inference of the AlphaTensor network (include/tensor_game_net.h).  gfx950 only; part of
 // libtensorgame.so.
 //
-// Two kernels, both plain fp32 with every activation in LDS and the weights read from global memory (they are shared by
+// Three kernels, all plain fp32 with every activation in LDS and the weights read from global memory (they are shared by
 // every workgroup and stay in L2):
 //   - net_torso_kernel: one workgroup per game.  The three S x S x c grids stay in LDS for all layers; each attention
 //     pair (m1, m2) is S independent sequences of 2S tokens, processed head by head (q, k, v of one head, scores,
 //     softmax, a @ v, then its slice of li1 added into the residual), then the MLP.
+//   - net_torso_slice_kernel (S = TG_NET_WIDE2_S): one workgroup per (game, i).  The first grid index is a batch index
+//     from the first torso layer to the last (a pair concatenates rows (i, .) of two grids and nothing transposes a
+//     grid), so the 3S rows (i, m, j) go through every layer without reading another slice.  The same steps as
+//     net_torso_kernel on one sequence of 2S tokens, the same arithmetic per row.
 //   - net_decode_kernel: one workgroup per (game, group of R samples of that game); with teacher forcing one row per
 //     game.  Decodes position by position with a per-(row, block) cache of the self-attention's normalised key/value
 //     input (W floats per position): with it, a head's scores are (Wk_h^T q_h) . y_j and its output is
@@ -13,6 +17,8 @@
 //     the game, normalised once per block at the start.  Under the causal mask this equals the reference's rerun of
 //     the whole prefix.  The sampling rule runs per row at the end of each step; the value head runs in the workgroup
 //     that holds sample 0, on the position-0 output.
+//     At S = TG_NET_WIDE2_S (J = 768 keys) the cross-attention's softmax runs a 32-lane team per row
+//     (net_decode_kernel<true>); every other size keeps one thread per row and its token-order sums.
 // Every matrix product goes through mm(): thread = (output column, group of RB rows), the weight element read once per
 // RB rows, the rows read from LDS as broadcasts.
 #include <hip/hip_runtime.h>
@@ -47,6 +53,24 @@ __host__ __device__ inline TorsoPlan torso_plan(const tg_net_config& c) {
   p.QKV = p.Y + T2 * c.c;
   p.SC = p.QKV + qkv;
   p.total = p.SC + c.S * 4 * S2;
+  return p;
+}
+
+// one slice i of a game: the rows (i, m, j) of the three grids, one pair = one sequence of 2S tokens
+__host__ __device__ inline TorsoPlan slice_plan(const tg_net_config& c) {
+  const int L = 2 * c.S, cin = c.S * c.T + 1;
+  int qkv = 3 * L * c.torso_d;
+  if (L * c.torso_ff > qkv) qkv = L * c.torso_ff;
+  if (3 * c.S * cin > qkv) qkv = 3 * c.S * cin;
+  TorsoPlan p;
+  p.G = 0;
+  p.X = p.G + 3 * c.S * c.c;
+  p.XN = p.X + L * c.c;
+  p.YN = p.XN + L * c.c;
+  p.Y = p.YN + L * c.c;
+  p.QKV = p.Y + L * c.c;
+  p.SC = p.QKV + qkv;
+  p.total = p.SC + L * L;
   return p;
 }
 
@@ -212,7 +236,152 @@ __global__ void __launch_bounds__(NT) net_torso_kernel(TorsoArgs a) {
   }
 }
 
+// One workgroup per (game g, slice i): blockIdx.x = g*S + i.  G holds the slice's rows [m][j][ch]; a pair (m1, m2) is the
+// sequence of tokens u < 2S: grid m1 row j = u for u < S, grid m2 row j = u - S otherwise.
+__global__ void __launch_bounds__(NT) net_torso_slice_kernel(TorsoArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const tg_net_config& c = a.c;
+  const int S = c.S, S2 = S * S, L = 2 * S, C = c.c, cin = S * c.T + 1;
+  const int64_t g = blockIdx.x / S;
+  const int i = static_cast<int>(blockIdx.x % S);
+  if (g >= a.B) return;
+  const TorsoPlan P = slice_plan(c);
+  float *G = lds + P.G, *X = lds + P.X, *XN = lds + P.XN, *YN = lds + P.YN, *Y = lds + P.Y, *QKV = lds + P.QKV,
+        *SC = lds + P.SC;
+  // input rows: IN[m][j][ch], ch = c3*T + t < S*T from the frames, ch = S*T the scalar projection at (i, j)
+  float* IN = QKV;
+  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
+  for (int it = threadIdx.x; it < 3 * S * cin; it += NT) {
+    const int ch = it % cin, j = (it / cin) % S, m = it / (cin * S);
+    float v;
+    if (ch == cin - 1) {
+      const float* Wt = a.w + a.off.t_li1[m];
+      const int tok = i * S + j;
+      float s = 0.f;
+      for (int q = 0; q < c.dim_s; ++q) s = fmaf(a.scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
+      v = s + Wt[c.dim_s * S2 + tok];
+    } else {
+      const int c3 = ch / c.T, t = ch % c.T;
+      int a0, a1, a2;
+      if (m == 0) { a0 = i; a1 = j; a2 = c3; }
+      else if (m == 1) { a0 = j; a1 = c3; a2 = i; }
+      else { a0 = c3; a1 = i; a2 = j; }
+      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
+      v = a.frames_i8 ? static_cast<float>(static_cast<const int8_t*>(a.frames)[idx])
+                      : static_cast<const float*>(a.frames)[idx];
+    }
+    IN[it] = v;
+  }
+  __syncthreads();
+  for (int m = 0; m < 3; ++m) {
+    const float* Wt = a.w + a.off.t_li2[m];
+    mm(IN + m * S * cin, cin, S, cin, Wt, C, C, Wt + cin * C, G + m * S * C, C);
+  }
+  __syncthreads();
+  const int H = c.torso_heads, d = c.torso_d, hd = H * d, ff = c.torso_ff;
+  const float sd = sqrtf(static_cast<float>(d));
+  float *Q = QKV, *K = QKV + L * d, *V = QKV + 2 * L * d;
+  for (int l = 0; l < c.torso_layers; ++l) {
+    const Mha mh = mha_at(a.w + a.off.t_layer0 + l * a.off.t_layer, C, C, H, d, ff);
+    for (int pr = 0; pr < 3; ++pr) {
+      const float* G1 = G + pr * S * C;
+      const float* G2 = G + (pr == 2 ? 0 : pr + 1) * S * C;
+      for (int it = threadIdx.x; it < L * C; it += NT) {
+        const float v = it < S * C ? G1[it] : G2[it - S * C];
+        X[it] = v;
+        Y[it] = v;
+      }
+      __syncthreads();
+      layernorm(X, C, L, C, mh.ln1w, mh.ln1b, XN, C);
+      layernorm(X, C, L, C, mh.ln2w, mh.ln2b, YN, C);
+      __syncthreads();
+      for (int h = 0; h < H; ++h) {
+        mm(XN, C, L, C, mh.q + h * d, hd, d, nullptr, Q, d);
+        // keys: K[r][e] = sum_i YN[r][i] * k[h*d+e][i]  (k stored [hd][c])
+        for (int it = threadIdx.x; it < L * d; it += NT) {
+          const int e = it % d, r = it / d;
+          const float* kr = mh.k + (h * d + e) * C;
+          float s = 0.f;
+#pragma unroll 8
+          for (int n = 0; n < C; ++n) s = fmaf(YN[r * C + n], kr[n], s);
+          K[it] = s;
+        }
+        mm(YN, C, L, C, mh.v + h * d, hd, d, nullptr, V, d);
+        __syncthreads();
+        // scores: SC[a][b] = Q[a] . K[b] / sqrt(d)
+        for (int it = threadIdx.x; it < L * L; it += NT) {
+          const float* q = Q + (it / L) * d;
+          const float* k = K + (it % L) * d;
+          float s = 0.f;
+#pragma unroll 8
+          for (int e = 0; e < d; ++e) s = fmaf(q[e], k[e], s);
+          SC[it] = s / sd;
+        }
+        __syncthreads();
+        softmax_rows(SC, L, L, L);
+        __syncthreads();
+        // O (into Q) = A @ V
+        for (int it = threadIdx.x; it < L * d; it += NT) {
+          const int e = it % d;
+          const float* ar = SC + (it / d) * L;
+          float s = 0.f;
+          for (int bb = 0; bb < L; ++bb) s = fmaf(ar[bb], V[bb * d + e], s);
+          Q[it] = s;
+        }
+        __syncthreads();
+        // Y += O_h @ li1[h*d .. h*d+d-1][:] (+ the bias with head 0)
+        mm(Q, d, L, d, mh.li1w + h * d * C, C, C, h == 0 ? mh.li1b : nullptr, Y, C, ACT_NONE, Y, nullptr, C);
+        __syncthreads();
+      }
+      layernorm(Y, C, L, C, mh.ln3w, mh.ln3b, XN, C);
+      __syncthreads();
+      mm(XN, C, L, C, mh.li2w, ff, ff, mh.li2b, QKV, ff, ACT_GELU);
+      __syncthreads();
+      mm(QKV, ff, L, ff, mh.li3w, C, C, mh.li3b, X, C, ACT_NONE, Y, nullptr, C);
+      __syncthreads();
+      float* W1 = G + pr * S * C;
+      float* W2 = G + (pr == 2 ? 0 : pr + 1) * S * C;
+      for (int it = threadIdx.x; it < L * C; it += NT) {
+        if (it < S * C) W1[it] = X[it];
+        else W2[it - S * C] = X[it];
+      }
+      __syncthreads();
+    }
+  }
+  // ee rows i*3S + m*S + j = G[m][j]: one contiguous run of 3S*c floats
+  float* out = a.ee + (g * S + i) * 3 * S * C;
+  for (int it = threadIdx.x; it < 3 * S * C; it += NT) out[it] = G[it];
+}
+
 // ---- decoder ------------------------------------------------------------------------------------------------------
+// softmax in place over rows of n entries, a team of 32 lanes per row: for the cross-attention's J = 768 keys at
+// S = TG_NET_WIDE2_S, where one thread per row (softmax_rows) leaves R * heads threads at work for 3 x 768 steps.  Lane l
+// takes entries l, l + 32, ...: its partial sum runs in that order and the 32 partial sums meet in a fixed butterfly, so a
+// row's result depends on neither R nor the launch shape.  Rows of at most kTeamSoftmaxFrom entries (J <= 243 at every
+// other supported size, and the self-attention's n_steps) keep softmax_rows and its token-order sum.
+constexpr int kTeamSoftmaxFrom = 256;
+
+__device__ inline void softmax_rows_team(float* A, int rows, int n, int ld) {
+  const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
+  for (int r = team; r < rows; r += NT / 32) {
+    float* a = A + r * ld;
+    float m = -INFINITY;
+    for (int j = lane; j < n; j += 32) m = fmaxf(m, a[j]);
+#pragma unroll
+    for (int x = 16; x >= 1; x >>= 1) m = fmaxf(m, __shfl_xor(m, x, 32));
+    float s = 0.f;
+    for (int j = lane; j < n; j += 32) {
+      const float e = expf(a[j] - m);
+      a[j] = e;
+      s += e;
+    }
+#pragma unroll
+    for (int x = 16; x >= 1; x >>= 1) s += __shfl_xor(s, x, 32);
+    const float inv = 1.f / s;
+    for (int j = lane; j < n; j += 32) a[j] *= inv;
+  }
+}
+
 struct DecArgs {
   tg_net_config c;
   Off off;
@@ -231,6 +400,9 @@ struct DecArgs {
   float* zz0;               // teacher: (B,W)
 };
 
+// kTeam: the cross-attention's softmax by teams (the host takes it for J > kTeamSoftmaxFrom); the other instantiation is
+// the kernel of every other size, whose registers the team code then does not touch.
+template <bool kTeam>
 __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
@@ -332,7 +504,8 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
         SC[rh * nsc + j] = s / sd;
       }
       __syncthreads();
-      softmax_rows(SC, R * H, J, nsc);
+      if (kTeam) softmax_rows_team(SC, R * H, J, nsc);
+      else softmax_rows(SC, R * H, J, nsc);
       __syncthreads();
       for (int it = threadIdx.x; it < R * H * C; it += NT) {
         const int i = it % C, rh = it / C;
@@ -456,20 +629,26 @@ int check_cfg(const char* fn, const tg_net_config* c) {
                          "TG_NET_MAX_HIDDEN", "TG_NET_MAX_QUANTILE"};
   for (int i = 0; i < 17; ++i)
     if (dims[i] < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, names[i], dims[i]);
-  // S <= TG_NET_MAX_S as for every bound, or exactly TG_NET_WIDE_S with n_steps <= TG_NET_WIDE_MAX_STEPS instead
-  const bool wide = c->S == TG_NET_WIDE_S;
+  // S <= TG_NET_MAX_S as for every bound, or exactly TG_NET_WIDE_S or TG_NET_WIDE2_S with their own n_steps bounds instead
+  const bool wide1 = c->S == TG_NET_WIDE_S, wide2 = c->S == TG_NET_WIDE2_S, wide = wide1 || wide2;
   if (c->S > TG_NET_MAX_S && !wide)
-    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: dim_3d=%d above TG_NET_MAX_S=%d, and not exactly TG_NET_WIDE_S=%d",
-                            fn, c->S, TG_NET_MAX_S, TG_NET_WIDE_S);
-  if (wide && c->n_steps > TG_NET_WIDE_MAX_STEPS)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED,
+                            "%s: dim_3d=%d above TG_NET_MAX_S=%d, and not exactly TG_NET_WIDE_S=%d or TG_NET_WIDE2_S=%d",
+                            fn, c->S, TG_NET_MAX_S, TG_NET_WIDE_S, TG_NET_WIDE2_S);
+  if (wide1 && c->n_steps > TG_NET_WIDE_MAX_STEPS)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE_MAX_STEPS=%d (dim_3d=%d)", fn,
                             c->n_steps, TG_NET_WIDE_MAX_STEPS, c->S);
+  if (wide2 && c->n_steps > TG_NET_WIDE2_MAX_STEPS)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE2_MAX_STEPS=%d (dim_3d=%d)", fn,
+                            c->n_steps, TG_NET_WIDE2_MAX_STEPS, c->S);
   for (int i = 1; i < 17; ++i) {
-    if (wide && i == 13) continue;  // n_steps: its bound at S = TG_NET_WIDE_S is above
+    if (wide && i == 13) continue;  // n_steps: its bound at a wide S is above
     if (dims[i] > maxs[i])
       return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, names[i], dims[i], bound[i], maxs[i]);
   }
-  const size_t lt = tg::net::torso_plan(*c).total * sizeof(float), ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
+  // at S = TG_NET_WIDE2_S the torso runs by slices (net_torso_slice_kernel) and its term is the slice plan
+  const size_t lt = (wide2 ? tg::net::slice_plan(*c) : tg::net::torso_plan(*c)).total * sizeof(float),
+               ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
   if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: the LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB", fn,
                             lt, ld);
@@ -494,8 +673,13 @@ int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
     return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn,
                             (long long)a.B, a.chunks);
   const size_t lds = tg::net::dec_plan(a.c, R).total * sizeof(float);
-  if (int rc = lds_opt_in<tg::net::net_decode_kernel>(fn, lds)) return rc;
-  return launch(fn, tg::net::net_decode_kernel, static_cast<unsigned>(a.B * a.chunks), tg::net::NT, lds, st, a);
+  const unsigned grid = static_cast<unsigned>(a.B * a.chunks);
+  if (3 * a.c.S * a.c.S > tg::net::kTeamSoftmaxFrom) {
+    if (int rc = lds_opt_in<tg::net::net_decode_kernel<true>>(fn, lds)) return rc;
+    return launch(fn, tg::net::net_decode_kernel<true>, grid, tg::net::NT, lds, st, a);
+  }
+  if (int rc = lds_opt_in<tg::net::net_decode_kernel<false>>(fn, lds)) return rc;
+  return launch(fn, tg::net::net_decode_kernel<false>, grid, tg::net::NT, lds, st, a);
 }
 
 }  // namespace
@@ -524,6 +708,16 @@ int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, i
   if (!aligned(frames, frames_is_i8 ? 1 : 4) || !aligned(scalars, 4) || !aligned(ee, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
   tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B};
+  // by slices at S = TG_NET_WIDE2_S; in the A/B library also where TG_NET_TORSO_SLICES is set (any size, for comparison)
+  if (cfg->S == TG_NET_WIDE2_S || TG_SWITCH("TG_NET_TORSO_SLICES")) {
+    if (B * cfg->S > INT32_MAX)
+      return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn, (long long)B,
+                              cfg->S);
+    const size_t lds = tg::net::slice_plan(*cfg).total * sizeof(float);
+    if (int rc = lds_opt_in<tg::net::net_torso_slice_kernel>(fn, lds)) return rc;
+    return launch(fn, tg::net::net_torso_slice_kernel, static_cast<unsigned>(B * cfg->S), tg::net::NT, lds,
+                  static_cast<hipStream_t>(stream), a);
+  }
   const size_t lds = tg::net::torso_plan(*cfg).total * sizeof(float);
   if (int rc = lds_opt_in<tg::net::net_torso_kernel>(fn, lds)) return rc;
   return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);

@@ -1029,6 +1029,10 @@ namespace {
 
 int check_train_cfg(const char* fn, const tg_net_config* c) {
   if (int rc = tg_net_check(c)) return rc;
+  if (c->S == TG_NET_WIDE2_S)  // inference only: the decoder's backward keeps a whole game's ee and dL/dee in one workgroup
+    return tg_internal_fail(TG_ERR_UNSUPPORTED,
+                            "%s: training at dim_3d=%d (TG_NET_WIDE2_S) is not built; inference and self-play only", fn,
+                            c->S);
   const bool wide = tg::train::wide(*c);  // there the torso fits when one sequence at a time does
   const size_t lt = (wide ? tg::train::tplan(*c, 1) : tg::train::tplan(*c)).total * sizeof(float),
                ld = (wide ? tg::train::dplan_kv(*c) : tg::train::dplan(*c)).total * sizeof(float);

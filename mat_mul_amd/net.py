@@ -10,6 +10,10 @@ head) -- from one packed float32 weight blob.
     oo, zz0 = net.logits(xx, ss, g_action)                  # teacher-forced, PolicyHead.fwd_train's forward
     states, policy, rewards, lengths = search.actor_prediction(net.policy(seed=0), start, 8, n_sim=16, ...)
 
+Supported: dim_3d <= 5, or exactly 9 (3x3 matmul) or 16 (4x4 matmul, n_steps <= 48, inference only: the torso then
+runs one workgroup per (game, slice) instead of one per game), inside the TG_NET_MAX_* bounds and the LDS plans of the
+header; ``check_config`` names the bound otherwise.
+
 The draws follow the header's sampling rule (Philox keyed by seed, counter (game, call, sample, step block)), not
 torch's generator: the distribution is the reference's, the individual draws are not.  There is no CPU path.
 """
@@ -151,7 +155,8 @@ class FusedAlphaTensor:
 
     # ---- forward pieces -------------------------------------------------------------------------------------------
     def torso(self, xx: torch.Tensor, ss: torch.Tensor) -> torch.Tensor:
-        """Torso.forward: xx (B,T,S,S,S) float32 or int8, ss float32 (B,dim_s) -> ee float32 (B,3S^2,c)."""
+        """Torso.forward: xx (B,T,S,S,S) float32 or int8, ss float32 (B,dim_s) -> ee float32 (B,3S^2,c).  One launch at
+        every supported S (by slices at S = 16)."""
         return ops.net_torso(self.c, self.w, xx, ss.to(torch.float32))
 
     def sample(self, ee: torch.Tensor, rows: Optional[torch.Tensor] = None, seed: int = 0, call: Optional[int] = None,

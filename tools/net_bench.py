@@ -9,14 +9,18 @@ HIP events around each call after warm-up; median, p10 and p90 in microseconds. 
 fused algorithm (the decoder with its cache).  Then one self-play figure: microseconds per simulation of
 search.actor_prediction with net.policy at S = 4, B = 4096.  --fused-only runs the fused calls alone (for a kernel-trace
 run); --kernel-stats merges a rocprofv3 --stats CSV into an existing OUT_DIR/r08_net.json.  Writes OUT_DIR/r08_net.json.
---config picks another configuration of net_ref.CONFIGS or tests/net_s9_ref.CONFIGS (a9, b9: S = 9); the file is then
-OUT_DIR/r08_net_<config>.json and the self-play figure is skipped.
+--config picks another configuration of net_ref.CONFIGS, tests/net_s9_ref.CONFIGS (a9, b9: S = 9) or
+tests/net_s16_ref.CONFIGS (a16, b16: S = 16); the file is then OUT_DIR/r08_net_<config>.json.  At S = 9 the self-play
+figure is skipped; at S = 16 the sizes are B = 16, 256 and 1024 and the self-play figure is at B = 256, n_sim = 4.
+--torso-only times tg_net_torso alone at B = 16 and 256 and writes OUT_DIR/r08_torso_<config>[_slices].json; with
+TG_LIB_VARIANT=ab, TG_NET_TORSO_SLICES=1 forces net_torso_slice_kernel at any size (the A/B library's switch).
 """
 from __future__ import annotations
 
 import argparse
 import csv
 import json
+import os
 import statistics
 import sys
 import time
@@ -32,8 +36,9 @@ sys.path.insert(0, str(ROOT / "tests"))
 from mat_mul_amd import FusedAlphaTensor, search  # noqa: E402
 from net_ref import CONFIGS, Ref, dims, make_inputs, make_weights  # noqa: E402
 from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
+from net_s16_ref import CONFIGS as CONFIGS_S16  # noqa: E402
 
-CONFIGS = {**CONFIGS, **CONFIGS_S9}
+CONFIGS = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}
 
 DEV = "cuda:0"
 FP32_PEAK = 157.3e12  # MI355X vector FP32, FLOP/s (FMA = 2)
@@ -80,6 +85,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--torso-only", action="store_true")
     ap.add_argument("--kernel-stats")
     ap.add_argument("--config", default="a", choices=sorted(CONFIGS))
     args = ap.parse_args()
@@ -101,7 +107,26 @@ def main():
     net = FusedAlphaTensor.from_state_dict(sd, k, device=DEV)
     ref = Ref(sd, cfg, device=DEV, dtype=torch.float32)
     res = {"config": m, "k": k, "fp32_peak_flops": FP32_PEAK, "sizes": []}
-    for B in (256, 1024, 4096):
+    if args.torso_only:
+        slices = os.environ.get("TG_LIB_VARIANT") == "ab" and "TG_NET_TORSO_SLICES" in os.environ
+        res = {"config": m, "kernel": "net_torso_slice_kernel" if slices or m["S"] == 16 else "net_torso_kernel",
+               "sizes": []}
+        for B in (16, 256):
+            xx, ss = make_inputs(cfg, B, B)
+            xx, ss = torch.from_numpy(xx).to(DEV).float(), torch.from_numpy(ss).to(DEV)
+            for _ in range(args.warmup):
+                net.torso(xx, ss)
+            torch.cuda.synchronize()
+            row = {"B": B, "torso": stats([timed(lambda: net.torso(xx, ss)) for _ in range(args.reps)])}
+            res["sizes"].append(row)
+            print(json.dumps(row), flush=True)
+        res["command"] = " ".join(sys.argv)
+        path = out / f"r08_torso_{args.config}{'_slices' if slices else ''}.json"
+        path.write_text(json.dumps(res, indent=1))
+        print(f"wrote {path}")
+        return
+    wide16 = m["S"] == 16
+    for B in ((16, 256, 1024) if wide16 else (256, 1024, 4096)):
         xx, ss = make_inputs(cfg, B, B)
         xx = torch.from_numpy(xx).to(DEV).float()
         ss = torch.from_numpy(ss).to(DEV)
@@ -126,10 +151,10 @@ def main():
             row["eager_over_fused"] = statistics.median(te) / statistics.median(tf)
         res["sizes"].append(row)
         print(json.dumps(row), flush=True)
-    if not args.fused_only and args.config == "a":
-        B, S, T = 4096, 4, cfg["dim_t"]
+    if not args.fused_only and (args.config == "a" or wide16):
+        B, S, T = (256, 16, cfg["dim_t"]) if wide16 else (4096, 4, cfg["dim_t"])
         start = torch.from_numpy(np.random.default_rng(0).integers(-1, 2, size=(B, T, S, S, S)).astype(np.int8)).to(DEV)
-        n_sim, max_actions = 16, 4
+        n_sim, max_actions = (4, 2) if wide16 else (16, 4)
         pol = net.policy(seed=3)
         first = [0]
 
@@ -146,7 +171,7 @@ def main():
         wall = time.perf_counter() - t0
         res["self_play"] = {"B": B, "S": S, "k": k, "n_sim": n_sim, "max_actions": max_actions,
                             "simulations": first[0], "us_per_simulation": wall * 1e6 / max(1, first[0]),
-                            "search_only_us_per_simulation_r06": 122}
+                            **({} if wide16 else {"search_only_us_per_simulation_r06": 122})}
         print(json.dumps(res["self_play"]), flush=True)
     res["device"] = torch.cuda.get_device_name(0)
     res["command"] = " ".join(sys.argv)
