@@ -15,9 +15,9 @@ import importlib
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
-           "FusedAlphaTensor", "net", "FusedTrainer", "train"]
+           "FusedAlphaTensor", "net", "FusedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -29,6 +29,8 @@ _ATTRS = {
     "TensorGameData": "replay",
     "FusedAlphaTensor": "net",
     "FusedTrainer": "train",
+    "sample_rollouts": "rollout",
+    "RolloutResult": "rollout",
 }
 
 

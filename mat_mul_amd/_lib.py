@@ -124,6 +124,11 @@ TRAIN_SIGNATURES = {
     "tg_net_loss_grad": [_p, _p, _p, _p, _i, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_float, _u64, _u64, _p, _p, _p,
                          _i64, _p, _p, _p, _p],
 }
+# name -> argtypes; every symbol include/tensor_game_rollout.h declares
+ROLLOUT_SIGNATURES = {
+    "tg_rollout_advance": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
+    "tg_rollout_check": [_i64, _i, _i, _i, _i, _i, _i, _i],
+}
 TG_NET_TRAIN_PARTIALS = 256
 TG_TRAIN_STATUS_BAD_TOKEN = 1
 
@@ -173,7 +178,7 @@ def _load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
-                           **NET_SIGNATURES, **TRAIN_SIGNATURES}.items():
+                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -201,3 +201,18 @@ class FusedAlphaTensor:
             return tokens, None, q
 
         return policy
+
+    def rollout_policy(self, seed: int = 0):
+        """A ``rollout.RolloutPolicy``: ONE action per row (torso on the int8 frames, then ``sample`` with k = 1), drawn
+        with the random stream keyed by the global row index -- so the samples of one start state draw differently --
+        and ``call`` = the step, so two rollouts of the same seed play the same games.  Two launches, capturable."""
+        if self.n_steps != 3 * self.config["S"]:
+            raise TensorGameError("rollout_policy", -1, f"n_steps={self.n_steps} is not 3*dim_3d: the sampled tokens "
+                                  "are not one action")
+
+        @torch.no_grad()
+        def policy(frames, scalars, rows, step):
+            tokens, _, _ = self.sample(self.torso(frames, scalars), rows, seed, call=step, k=1)
+            return tokens.view(frames.shape[0], self.n_steps)
+
+        return policy

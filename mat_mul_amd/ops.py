@@ -23,6 +23,7 @@ __all__ = [
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
+    "rollout_check", "rollout_records", "rollout_advance",
 ]
 
 
@@ -961,3 +962,62 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
              int(call_idx) & (2 ** 64 - 1), _ptr(keep_in), _ptr(keep_out), _ptr(workspace), workspace.numel(),
              _ptr(grad), _ptr(losses), _ptr(status), _stream(dev))
     return losses, status
+
+
+# ---- sampled policy rollouts (include/tensor_game_rollout.h) --------------------------------------------------------
+def rollout_check(B: int, n: int, S: int, T: int, dim_s: int = 0, step: int = 0, max_actions: int = 0,
+                  with_actions: bool = False) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_rollout_advance takes these sizes.  Host only."""
+    call("tg_rollout_check", int(B), int(n), int(S), int(T), int(dim_s), int(step), int(max_actions),
+         1 if with_actions else 0)
+
+
+def rollout_records(G: int, S: int, device):
+    """Fresh group records of a rollout: int32 (G,) each -- best_nnz = S^3 (the reference's lowest_rank starts there,
+    training.py:329), hits = 0, solved_step = solved_sample = -1."""
+    kw = dict(dtype=torch.int32, device=device)
+    return (torch.full((G,), S ** 3, **kw), torch.zeros((G,), **kw), torch.full((G,), -1, **kw),
+            torch.full((G,), -1, **kw))
+
+
+def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nnz=None, overflow=None, actions=None,
+                    shift: int = 1):
+    """One step of a sampled rollout in one launch (tg_rollout_advance): == reference training.py:253-268 (the new
+    head, the history shift, scalars + 1, rank_ubs and the best sample per group) + the running statistics of
+    :343-346.  frames int8 (B,T,S,S,S), stepped IN PLACE (newest first: the next ``net_torso`` input); tokens int8
+    (B,3S); rows are group-major, row g*n + s = sample s of group g; ``records`` = (best_nnz, hits, solved_step,
+    solved_sample), int32 (B/n,) each (``rollout_records``), updated; scalars float32 (B,dim_s) += 1; overflow uint8
+    (B,) is set where an entry left int8; actions int8 (B,max_actions,3S) receives the tokens at index ``step``.
+    Returns nnz int32 (B,), the non-zero count of every new head."""
+    _need_gpu(frames, "frames")
+    if frames.dtype != torch.int8 or frames.dim() != 5 or not (frames.shape[2] == frames.shape[3] == frames.shape[4]):
+        raise TensorGameError("rollout_advance", -1, f"frames must be int8 (B,T,S,S,S), got {frames.dtype} "
+                              f"{tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise TensorGameError("rollout_advance", -1, "frames must be contiguous (they are stepped in place)")
+    B, T, S = frames.shape[0], frames.shape[1], frames.shape[2]
+    dev = frames.device
+    tokens = _tokens(tokens, (B,), S, dev, "tokens")
+    dim_s = 0
+    if scalars is not None:
+        dim_s = scalars.shape[1] if scalars.dim() == 2 else -1
+        scalars = _flag(scalars, (B, dim_s), torch.float32, dev, "scalars")
+    max_actions = 0
+    if actions is not None:
+        max_actions = actions.shape[1] if actions.dim() == 3 else -1
+        actions = _flag(actions, (B, max_actions, 3 * S), torch.int8, dev, "actions")
+    rollout_check(B, n, S, T, dim_s, step, max_actions, actions is not None)
+    if nnz is None:
+        nnz = torch.empty((B,), dtype=torch.int32, device=dev)
+    nnz = _flag(nnz, (B,), torch.int32, dev, "nnz")
+    overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
+    if len(records) != 4:
+        raise TensorGameError("rollout_advance", -1, "records must be (best_nnz, hits, solved_step, solved_sample)")
+    rec = [_flag(r, (B // n,), torch.int32, dev, name)
+           for r, name in zip(records, ("best_nnz", "hits", "solved_step", "solved_sample"))]
+    if any(r is None for r in rec):
+        raise TensorGameError("rollout_advance", -1, "records must be four int32 tensors (ops.rollout_records)")
+    with torch.cuda.device(dev):
+        call("tg_rollout_advance", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow), *map(_ptr, rec),
+             _ptr(actions), B, int(n), S, T, dim_s, int(step), max_actions, int(shift), _stream(dev))
+    return nnz

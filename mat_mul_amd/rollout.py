@@ -1,0 +1,155 @@
+"""Sampled policy rollouts: the solution search of the reference's SyntheticDemoTrainingApp (training.py:325-352).
+
+Every start state is copied ``n_samples`` times, the network samples ONE action per copy, the copies are stepped
+(``_take_action``, training.py:249-268), and this repeats ``max_actions`` times while the lowest non-zero count and the
+steps at which a copy reached the zero tensor are tracked.  Here a step is the policy's launches plus ONE more
+(``tg_rollout_advance``, include/tensor_game_rollout.h): the int8 frames are stepped in place and are the next torso
+input as they stand, the statistics stay on the device, and the played tokens are recorded, so a solved group can be
+turned back into the factorisation that was found.  Nothing in the loop synchronises with the host.
+
+    res = sample_rollouts(net.rollout_policy(seed=0), states, scalars, n_samples=8, max_actions=7)
+    res.num_solved.item(), res.lowest_rank.item()       # the first host syncs
+    groups, tokens, lengths = res.solutions()             # action lists that replay the start states to zero
+
+Two deliberate differences from training.py.  Its ``fwd_infer(..., n_samples=1)`` call (:252) does not run as written
+(fwd_infer takes no such argument); the policy here draws one action per row.  Its ``repeat(n_samples, ...)`` (:332)
+followed by ``view(-1, n_samples, ...)`` (:259) groups copies of DIFFERENT states; here a group is the n samples of one
+state (rows are group-major: row g*n + s is sample s of state g).  ``shift`` defaults to 1, the live path's
+vocabulary; the reference hard-codes ``- 2`` (:253, the Strassen vocabulary): pass ``shift=2`` for that.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Optional, Tuple
+
+import torch
+
+from . import ops
+from ._lib import TensorGameError
+
+__all__ = ["sample_rollouts", "RolloutResult", "model_policy", "RolloutPolicy"]
+
+# (frames int8 (B,T,S,S,S), scalars float32 (B,dim_s), rows int64 (B,), step) -> tokens int8 (B,3S)
+RolloutPolicy = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, int], torch.Tensor]
+
+
+@dataclass
+class RolloutResult:
+    """What ``sample_rollouts`` leaves on the device.  Per group (int32 (G,)): ``best_nnz`` the lowest non-zero count
+    any sample reached at any step, ``hits`` the number of steps at which some sample was at zero, ``solved_step`` the
+    first such step (-1: never) and ``solved_sample`` the lowest sample index at zero at that step.  ``frames`` int8
+    (B,T,S,S,S) and ``scalars`` are the final rows, ``nnz`` int32 (B,) the last step's counts, ``overflow`` uint8 (B,)
+    is set where an entry ever left int8, ``actions`` int8 (B,max_actions,3S) the played tokens (None unless
+    recorded).  ``lowest_rank`` (the reference's lowest_rank, :343), ``num_hits`` (its num_solutions_found, :346) and
+    ``num_solved`` (groups with a solution) are 0-d device tensors."""
+
+    n_samples: int
+    max_actions: int
+    shift: int
+    best_nnz: torch.Tensor
+    hits: torch.Tensor
+    solved_step: torch.Tensor
+    solved_sample: torch.Tensor
+    frames: torch.Tensor
+    scalars: torch.Tensor
+    nnz: torch.Tensor
+    overflow: torch.Tensor
+    actions: Optional[torch.Tensor]
+    lowest_rank: torch.Tensor
+    num_hits: torch.Tensor
+    num_solved: torch.Tensor
+    graph: Optional[torch.cuda.CUDAGraph] = None  # the captured loop (graph=True): kept alive with its results
+
+    def solutions(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """For every solved group, gathered on the device: (groups int64 (M,), tokens int8 (M,max_actions,3S),
+        lengths int64 (M,)).  tokens[m, :lengths[m]] are the winning sample's actions 0 .. solved_step, which replay
+        start state groups[m] to zero; the rows beyond the length are zero."""
+        if self.actions is None:
+            raise TensorGameError("solutions", -1, "the rollout did not record its actions (record_actions=False)")
+        groups = torch.nonzero(self.solved_step >= 0).flatten()
+        rows = groups * self.n_samples + self.solved_sample[groups].to(torch.int64)
+        lengths = self.solved_step[groups].to(torch.int64) + 1
+        tokens = self.actions[rows]
+        keep = torch.arange(self.max_actions, device=tokens.device)[None, :] < lengths[:, None]
+        return groups, tokens * keep[:, :, None].to(torch.int8), lengths
+
+
+def model_policy(model) -> RolloutPolicy:
+    """Wrap an ``AlphaTensor``-like torch model (``fwd_infer(states, scalars) -> (tokens (B,k,3S), probs, q)``,
+    model.py:347-356): the first of its samples is the row's action.  Not capturable (``ops.as_tokens`` checks the
+    token range on the host)."""
+
+    @torch.no_grad()
+    def policy(frames, scalars, rows, step):
+        aa = model.fwd_infer(frames.float(), scalars)[0]
+        B = frames.shape[0]
+        return ops.as_tokens(aa.reshape(B, -1, aa.shape[-1])[:, 0], frames.device)
+
+    return policy
+
+
+def sample_rollouts(policy: RolloutPolicy, states: torch.Tensor, scalars: torch.Tensor, n_samples: int,
+                    max_actions: int, shift: int = 1, record_actions: bool = True, graph: bool = False
+                    ) -> RolloutResult:
+    """Roll every start state out ``n_samples`` times for ``max_actions`` steps of ``policy -> advance``.
+
+    states int8 (G,T,S,S,S) (newest frame first), scalars float32 (G,dim_s); neither is modified.  ``policy`` sees the
+    B = G*n_samples rows (group-major) and their global row indices, so that the samples of one state draw
+    differently.  ``graph=True`` captures the whole loop once (a linear chain of launches) and replays it: only for
+    policies that can be captured (``FusedAlphaTensor.rollout_policy`` can); the results equal the eager loop bit for
+    bit."""
+    if not states.is_cuda:
+        raise TensorGameError("sample_rollouts", -1, f"states must live on a ROCm device (got {states.device}); there "
+                              "is no CPU path")
+    if states.dtype != torch.int8 or states.dim() != 5 or not (states.shape[2] == states.shape[3] == states.shape[4]):
+        raise TensorGameError("sample_rollouts", -1, f"states must be int8 (G,T,S,S,S), got {states.dtype} "
+                              f"{tuple(states.shape)}")
+    G, T, S = states.shape[0], states.shape[1], states.shape[2]
+    dev = states.device
+    if scalars.dim() != 2 or scalars.shape[0] != G or scalars.dtype != torch.float32 or scalars.device != dev:
+        raise TensorGameError("sample_rollouts", -1, f"scalars must be float32 ({G},dim_s) on {dev}, got "
+                              f"{scalars.dtype} {tuple(scalars.shape)} on {scalars.device}")
+    n, K = int(n_samples), int(max_actions)
+    if K < 1:
+        raise TensorGameError("sample_rollouts", -1, f"max_actions={max_actions} < 1")
+    B = G * max(n, 0)
+    ops.rollout_check(B, n, S, T, scalars.shape[1], 0, K, record_actions)
+    frames = states.repeat_interleave(n, dim=0).contiguous()
+    scal = scalars.repeat_interleave(n, dim=0).contiguous()
+    rows = torch.arange(B, device=dev, dtype=torch.int64)
+    records = ops.rollout_records(G, S, dev)
+    nnz = torch.zeros((B,), dtype=torch.int32, device=dev)
+    overflow = torch.zeros((B,), dtype=torch.uint8, device=dev)
+    actions = torch.zeros((B, K, 3 * S), dtype=torch.int8, device=dev) if record_actions else None
+
+    def one(step: int) -> None:
+        tokens = policy(frames, scal, rows, step)
+        ops.rollout_advance(frames, tokens, n, step, records, scalars=scal, nnz=nnz, overflow=overflow,
+                            actions=actions, shift=shift)
+
+    g = None
+    if graph and B:
+        # one warm-up step outside the capture (lazy initialisation of the policy's launches), then undone
+        keep = (frames.clone(), scal.clone())
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            one(0)
+            frames.copy_(keep[0])
+            scal.copy_(keep[1])
+            for r, fresh in zip(records, ops.rollout_records(G, S, dev)):
+                r.copy_(fresh)
+            overflow.zero_()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for step in range(K):
+                one(step)
+        g.replay()
+    elif B:
+        for step in range(K):
+            one(step)
+    best_nnz, hits, solved_step, solved_sample = records
+    return RolloutResult(n, K, int(shift), best_nnz, hits, solved_step, solved_sample, frames, scal, nnz, overflow,
+                         actions, best_nnz.min() if G else torch.tensor(S ** 3, dtype=torch.int32, device=dev),
+                         hits.sum(), (solved_step >= 0).sum(), g)
