@@ -8,8 +8,8 @@
 //     softmax, a @ v, then its slice of li1 added into the residual), then the MLP.
 //   - net_torso_slice_kernel (S = TG_NET_WIDE2_S): one workgroup per (game, i).  The first grid index is a batch index
 //     from the first torso layer to the last (a pair concatenates rows (i, .) of two grids and nothing transposes a
-//     grid), so the 3S rows (i, m, j) go through every layer without reading another slice.  The same steps as
-//     net_torso_kernel on one sequence of 2S tokens, the same arithmetic per row.
+//     grid), so the 3S rows (i, m, j) go through every layer without reading another slice.
+//     Both are one body (torso<SLICE>) over nseq sequences of 2S tokens, nseq = S or 1: the same arithmetic per row.
 //   - net_decode_kernel: one workgroup per (game, group of R samples of that game); with teacher forcing one row per
 //     game.  Decodes position by position with a per-(row, block) cache of the self-attention's normalised key/value
 //     input (W floats per position): with it, a head's scores are (Wk_h^T q_h) . y_j and its output is
@@ -39,38 +39,22 @@ struct TorsoPlan {
   int G, X, XN, YN, Y, QKV, SC, total;
 };
 
-__host__ __device__ inline TorsoPlan torso_plan(const tg_net_config& c) {
-  const int S2 = c.S * c.S, T2 = 2 * S2, cin = c.S * c.T + 1;
-  int qkv = 3 * T2 * c.torso_d;
-  if (T2 * c.torso_ff > qkv) qkv = T2 * c.torso_ff;
-  if (3 * S2 * cin > qkv) qkv = 3 * S2 * cin;
+// nseq sequences of 2S tokens at once: the whole game (nseq = S) or one slice i of it, the rows (i, m, j) of the three
+// grids (nseq = 1)
+__host__ __device__ inline TorsoPlan torso_plan(const tg_net_config& c, int nseq) {
+  const int N = nseq * 2 * c.S, cin = c.S * c.T + 1;
+  int qkv = 3 * N * c.torso_d;
+  if (N * c.torso_ff > qkv) qkv = N * c.torso_ff;
+  if (3 * nseq * c.S * cin > qkv) qkv = 3 * nseq * c.S * cin;
   TorsoPlan p;
   p.G = 0;
-  p.X = p.G + 3 * S2 * c.c;
-  p.XN = p.X + T2 * c.c;
-  p.YN = p.XN + T2 * c.c;
-  p.Y = p.YN + T2 * c.c;
-  p.QKV = p.Y + T2 * c.c;
+  p.X = p.G + 3 * nseq * c.S * c.c;
+  p.XN = p.X + N * c.c;
+  p.YN = p.XN + N * c.c;
+  p.Y = p.YN + N * c.c;
+  p.QKV = p.Y + N * c.c;
   p.SC = p.QKV + qkv;
-  p.total = p.SC + c.S * 4 * S2;
-  return p;
-}
-
-// one slice i of a game: the rows (i, m, j) of the three grids, one pair = one sequence of 2S tokens
-__host__ __device__ inline TorsoPlan slice_plan(const tg_net_config& c) {
-  const int L = 2 * c.S, cin = c.S * c.T + 1;
-  int qkv = 3 * L * c.torso_d;
-  if (L * c.torso_ff > qkv) qkv = L * c.torso_ff;
-  if (3 * c.S * cin > qkv) qkv = 3 * c.S * cin;
-  TorsoPlan p;
-  p.G = 0;
-  p.X = p.G + 3 * c.S * c.c;
-  p.XN = p.X + L * c.c;
-  p.YN = p.XN + L * c.c;
-  p.Y = p.YN + L * c.c;
-  p.QKV = p.Y + L * c.c;
-  p.SC = p.QKV + qkv;
-  p.total = p.SC + L * L;
+  p.total = p.SC + N * 2 * c.S;
   return p;
 }
 
@@ -118,66 +102,50 @@ struct TorsoArgs {
   int64_t B;
 };
 
-__global__ void __launch_bounds__(NT) net_torso_kernel(TorsoArgs a) {
+// The torso of game g over nseq of its S slices: G holds their rows [m][s][j][ch]; a pair (m1, m2) is nseq independent
+// sequences of 2S tokens (net::pair_row).  SLICE: one slice per workgroup, blockIdx.x = g*S + i; otherwise the whole
+// game.  A compile-time constant, so that with one sequence the row mappings fold away (ee is then one contiguous run).
+// Training's mha_fwd (tg_train.hip) is this block once more and stays apart: it starts from H1 = X + li1's bias where
+// this adds the bias with head 0 (res + (acc + b)), so a merged body would change one side's result bits.
+template <bool SLICE>
+__device__ inline void torso(const TorsoArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
-  const int S = c.S, S2 = S * S, T2 = 2 * S2, C = c.c, cin = S * c.T + 1;
-  const int64_t g = blockIdx.x;
+  const int S = c.S, nseq = SLICE ? 1 : S, L = 2 * S, N = nseq * L, C = c.c, cin = S * c.T + 1;
+  const int64_t g = SLICE ? blockIdx.x / S : blockIdx.x;
+  const int i0 = SLICE ? static_cast<int>(blockIdx.x % S) : 0;
   if (g >= a.B) return;
-  const TorsoPlan P = torso_plan(c);
+  const TorsoPlan P = torso_plan(c, nseq);
   float *G = lds + P.G, *X = lds + P.X, *XN = lds + P.XN, *YN = lds + P.YN, *Y = lds + P.Y, *QKV = lds + P.QKV,
         *SC = lds + P.SC;
-  // input grids: IN[m][i*S+j][ch], ch = c3*T + t < S*T from the frames, ch = S*T the scalar projection
   float* IN = QKV;
-  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
-  for (int it = threadIdx.x; it < 3 * S2 * cin; it += NT) {
-    const int ch = it % cin, tok = (it / cin) % S2, m = it / (cin * S2);
-    float v;
-    if (ch == cin - 1) {
-      const float* Wt = a.w + a.off.t_li1[m];
-      float s = 0.f;
-      for (int q = 0; q < c.dim_s; ++q) s = fmaf(a.scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
-      v = s + Wt[c.dim_s * S2 + tok];
-    } else {
-      const int p = tok / S, q = tok % S, c3 = ch / c.T, t = ch % c.T;
-      int a0, a1, a2;
-      if (m == 0) { a0 = p; a1 = q; a2 = c3; }
-      else if (m == 1) { a0 = q; a1 = c3; a2 = p; }
-      else { a0 = c3; a1 = p; a2 = q; }
-      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
-      v = a.frames_i8 ? static_cast<float>(static_cast<const int8_t*>(a.frames)[idx])
-                      : static_cast<const float*>(a.frames)[idx];
-    }
-    IN[it] = v;
-  }
+  torso_inputs(c, a.off, a.w, a.frames, a.frames_i8, a.scalars, g, nseq, i0, IN);
   __syncthreads();
   for (int m = 0; m < 3; ++m) {
     const float* Wt = a.w + a.off.t_li2[m];
-    mm(IN + m * S2 * cin, cin, S2, cin, Wt, C, C, Wt + cin * C, G + m * S2 * C, C);
+    mm(IN + m * nseq * S * cin, cin, nseq * S, cin, Wt, C, C, Wt + cin * C, G + m * nseq * S * C, C);
   }
   __syncthreads();
   const int H = c.torso_heads, d = c.torso_d, hd = H * d, ff = c.torso_ff;
   const float sd = sqrtf(static_cast<float>(d));
-  float *Q = QKV, *K = QKV + T2 * d, *V = QKV + 2 * T2 * d;
+  float *Q = QKV, *K = QKV + N * d, *V = QKV + 2 * N * d;
   for (int l = 0; l < c.torso_layers; ++l) {
     const Mha mh = mha_at(a.w + a.off.t_layer0 + l * a.off.t_layer, C, C, H, d, ff);
     for (int pr = 0; pr < 3; ++pr) {
       const int m1 = pr, m2 = pr == 2 ? 0 : pr + 1;
-      // token r = i*2S + u: grid m1 row (i, u) for u < S, grid m2 row (i, u - S) otherwise
-      for (int it = threadIdx.x; it < T2 * C; it += NT) {
-        const int ch = it % C, r = it / C, i = r / (2 * S), u = r % (2 * S);
-        const float v = u < S ? G[(m1 * S2 + i * S + u) * C + ch] : G[(m2 * S2 + i * S + u - S) * C + ch];
+      for (int it = threadIdx.x; it < N * C; it += NT) {
+        const float v = G[pair_row(it / C, S, nseq, m1, m2) * C + it % C];
         X[it] = v;
         Y[it] = v;
       }
       __syncthreads();
-      layernorm(X, C, T2, C, mh.ln1w, mh.ln1b, XN, C);
-      layernorm(X, C, T2, C, mh.ln2w, mh.ln2b, YN, C);
+      layernorm(X, C, N, C, mh.ln1w, mh.ln1b, XN, C);
+      layernorm(X, C, N, C, mh.ln2w, mh.ln2b, YN, C);
       __syncthreads();
       for (int h = 0; h < H; ++h) {
-        mm(XN, C, T2, C, mh.q + h * d, hd, d, nullptr, Q, d);
+        mm(XN, C, N, C, mh.q + h * d, hd, d, nullptr, Q, d);
         // keys: K[r][e] = sum_i YN[r][i] * k[h*d+e][i]  (k stored [hd][c])
-        for (int it = threadIdx.x; it < T2 * d; it += NT) {
+        for (int it = threadIdx.x; it < N * d; it += NT) {
           const int e = it % d, r = it / d;
           const float* kr = mh.k + (h * d + e) * C;
           float s = 0.f;
@@ -185,173 +153,51 @@ __global__ void __launch_bounds__(NT) net_torso_kernel(TorsoArgs a) {
           for (int i = 0; i < C; ++i) s = fmaf(YN[r * C + i], kr[i], s);
           K[it] = s;
         }
-        mm(YN, C, T2, C, mh.v + h * d, hd, d, nullptr, V, d);
+        mm(YN, C, N, C, mh.v + h * d, hd, d, nullptr, V, d);
         __syncthreads();
-        // scores of sequence i: SC[i][a][b] = Q[i,a] . K[i,b] / sqrt(d)
-        const int L2 = 2 * S;
-        for (int it = threadIdx.x; it < S * L2 * L2; it += NT) {
-          const int bb = it % L2, aa = (it / L2) % L2, i = it / (L2 * L2);
-          const float* q = Q + (i * L2 + aa) * d;
-          const float* k = K + (i * L2 + bb) * d;
+        // scores within a sequence: SC[r][b] = Q[r] . K[seq(r)*L + b] / sqrt(d)
+        for (int it = threadIdx.x; it < N * L; it += NT) {
+          const int bb = it % L, r = it / L;
+          const float* q = Q + r * d;
+          const float* k = K + (seq_of(r, L, nseq) * L + bb) * d;
           float s = 0.f;
 #pragma unroll 8
           for (int e = 0; e < d; ++e) s = fmaf(q[e], k[e], s);
           SC[it] = s / sd;
         }
         __syncthreads();
-        softmax_rows(SC, S * L2, L2, L2);
+        softmax_rows(SC, N, L, L);
         __syncthreads();
         // O (into Q) = A @ V per sequence
-        for (int it = threadIdx.x; it < T2 * d; it += NT) {
-          const int e = it % d, r = it / d, i = r / L2, aa = r % L2;
-          const float* ar = SC + (i * L2 + aa) * L2;
+        for (int it = threadIdx.x; it < N * d; it += NT) {
+          const int e = it % d, r = it / d;
+          const float* ar = SC + r * L;
+          const float* v = V + seq_of(r, L, nseq) * L * d + e;
           float s = 0.f;
-          for (int bb = 0; bb < L2; ++bb) s = fmaf(ar[bb], V[(i * L2 + bb) * d + e], s);
+          for (int bb = 0; bb < L; ++bb) s = fmaf(ar[bb], v[bb * d], s);
           Q[it] = s;
         }
         __syncthreads();
         // Y += O_h @ li1[h*d .. h*d+d-1][:] (+ the bias with head 0)
-        mm(Q, d, T2, d, mh.li1w + h * d * C, C, C, h == 0 ? mh.li1b : nullptr, Y, C, ACT_NONE, Y, nullptr, C);
+        mm(Q, d, N, d, mh.li1w + h * d * C, C, C, h == 0 ? mh.li1b : nullptr, Y, C, ACT_NONE, Y, nullptr, C);
         __syncthreads();
       }
-      layernorm(Y, C, T2, C, mh.ln3w, mh.ln3b, XN, C);
+      layernorm(Y, C, N, C, mh.ln3w, mh.ln3b, XN, C);
       __syncthreads();
-      mm(XN, C, T2, C, mh.li2w, ff, ff, mh.li2b, QKV, ff, ACT_GELU);
+      mm(XN, C, N, C, mh.li2w, ff, ff, mh.li2b, QKV, ff, ACT_GELU);
       __syncthreads();
-      mm(QKV, ff, T2, ff, mh.li3w, C, C, mh.li3b, X, C, ACT_NONE, Y, nullptr, C);
+      mm(QKV, ff, N, ff, mh.li3w, C, C, mh.li3b, X, C, ACT_NONE, Y, nullptr, C);
       __syncthreads();
-      for (int it = threadIdx.x; it < T2 * C; it += NT) {
-        const int ch = it % C, r = it / C, i = r / (2 * S), u = r % (2 * S);
-        if (u < S) G[(m1 * S2 + i * S + u) * C + ch] = X[it];
-        else G[(m2 * S2 + i * S + u - S) * C + ch] = X[it];
-      }
+      for (int it = threadIdx.x; it < N * C; it += NT) G[pair_row(it / C, S, nseq, m1, m2) * C + it % C] = X[it];
       __syncthreads();
     }
   }
-  // ee row i*3S + m*S + j = grid m row (i, j)
-  float* out = a.ee + g * 3 * S2 * C;
-  for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) {
-    const int ch = it % C, row = it / C, i = row / (3 * S), m = (row / S) % 3, j = row % S;
-    out[it] = G[(m * S2 + i * S + j) * C + ch];
-  }
+  float* out = a.ee + (g * S + i0) * 3 * S * C;
+  for (int it = threadIdx.x; it < 3 * nseq * S * C; it += NT) out[it] = G[ee_row(it / C, S, nseq) * C + it % C];
 }
 
-// One workgroup per (game g, slice i): blockIdx.x = g*S + i.  G holds the slice's rows [m][j][ch]; a pair (m1, m2) is the
-// sequence of tokens u < 2S: grid m1 row j = u for u < S, grid m2 row j = u - S otherwise.
-__global__ void __launch_bounds__(NT) net_torso_slice_kernel(TorsoArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const tg_net_config& c = a.c;
-  const int S = c.S, S2 = S * S, L = 2 * S, C = c.c, cin = S * c.T + 1;
-  const int64_t g = blockIdx.x / S;
-  const int i = static_cast<int>(blockIdx.x % S);
-  if (g >= a.B) return;
-  const TorsoPlan P = slice_plan(c);
-  float *G = lds + P.G, *X = lds + P.X, *XN = lds + P.XN, *YN = lds + P.YN, *Y = lds + P.Y, *QKV = lds + P.QKV,
-        *SC = lds + P.SC;
-  // input rows: IN[m][j][ch], ch = c3*T + t < S*T from the frames, ch = S*T the scalar projection at (i, j)
-  float* IN = QKV;
-  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
-  for (int it = threadIdx.x; it < 3 * S * cin; it += NT) {
-    const int ch = it % cin, j = (it / cin) % S, m = it / (cin * S);
-    float v;
-    if (ch == cin - 1) {
-      const float* Wt = a.w + a.off.t_li1[m];
-      const int tok = i * S + j;
-      float s = 0.f;
-      for (int q = 0; q < c.dim_s; ++q) s = fmaf(a.scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
-      v = s + Wt[c.dim_s * S2 + tok];
-    } else {
-      const int c3 = ch / c.T, t = ch % c.T;
-      int a0, a1, a2;
-      if (m == 0) { a0 = i; a1 = j; a2 = c3; }
-      else if (m == 1) { a0 = j; a1 = c3; a2 = i; }
-      else { a0 = c3; a1 = i; a2 = j; }
-      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
-      v = a.frames_i8 ? static_cast<float>(static_cast<const int8_t*>(a.frames)[idx])
-                      : static_cast<const float*>(a.frames)[idx];
-    }
-    IN[it] = v;
-  }
-  __syncthreads();
-  for (int m = 0; m < 3; ++m) {
-    const float* Wt = a.w + a.off.t_li2[m];
-    mm(IN + m * S * cin, cin, S, cin, Wt, C, C, Wt + cin * C, G + m * S * C, C);
-  }
-  __syncthreads();
-  const int H = c.torso_heads, d = c.torso_d, hd = H * d, ff = c.torso_ff;
-  const float sd = sqrtf(static_cast<float>(d));
-  float *Q = QKV, *K = QKV + L * d, *V = QKV + 2 * L * d;
-  for (int l = 0; l < c.torso_layers; ++l) {
-    const Mha mh = mha_at(a.w + a.off.t_layer0 + l * a.off.t_layer, C, C, H, d, ff);
-    for (int pr = 0; pr < 3; ++pr) {
-      const float* G1 = G + pr * S * C;
-      const float* G2 = G + (pr == 2 ? 0 : pr + 1) * S * C;
-      for (int it = threadIdx.x; it < L * C; it += NT) {
-        const float v = it < S * C ? G1[it] : G2[it - S * C];
-        X[it] = v;
-        Y[it] = v;
-      }
-      __syncthreads();
-      layernorm(X, C, L, C, mh.ln1w, mh.ln1b, XN, C);
-      layernorm(X, C, L, C, mh.ln2w, mh.ln2b, YN, C);
-      __syncthreads();
-      for (int h = 0; h < H; ++h) {
-        mm(XN, C, L, C, mh.q + h * d, hd, d, nullptr, Q, d);
-        // keys: K[r][e] = sum_i YN[r][i] * k[h*d+e][i]  (k stored [hd][c])
-        for (int it = threadIdx.x; it < L * d; it += NT) {
-          const int e = it % d, r = it / d;
-          const float* kr = mh.k + (h * d + e) * C;
-          float s = 0.f;
-#pragma unroll 8
-          for (int n = 0; n < C; ++n) s = fmaf(YN[r * C + n], kr[n], s);
-          K[it] = s;
-        }
-        mm(YN, C, L, C, mh.v + h * d, hd, d, nullptr, V, d);
-        __syncthreads();
-        // scores: SC[a][b] = Q[a] . K[b] / sqrt(d)
-        for (int it = threadIdx.x; it < L * L; it += NT) {
-          const float* q = Q + (it / L) * d;
-          const float* k = K + (it % L) * d;
-          float s = 0.f;
-#pragma unroll 8
-          for (int e = 0; e < d; ++e) s = fmaf(q[e], k[e], s);
-          SC[it] = s / sd;
-        }
-        __syncthreads();
-        softmax_rows(SC, L, L, L);
-        __syncthreads();
-        // O (into Q) = A @ V
-        for (int it = threadIdx.x; it < L * d; it += NT) {
-          const int e = it % d;
-          const float* ar = SC + (it / d) * L;
-          float s = 0.f;
-          for (int bb = 0; bb < L; ++bb) s = fmaf(ar[bb], V[bb * d + e], s);
-          Q[it] = s;
-        }
-        __syncthreads();
-        // Y += O_h @ li1[h*d .. h*d+d-1][:] (+ the bias with head 0)
-        mm(Q, d, L, d, mh.li1w + h * d * C, C, C, h == 0 ? mh.li1b : nullptr, Y, C, ACT_NONE, Y, nullptr, C);
-        __syncthreads();
-      }
-      layernorm(Y, C, L, C, mh.ln3w, mh.ln3b, XN, C);
-      __syncthreads();
-      mm(XN, C, L, C, mh.li2w, ff, ff, mh.li2b, QKV, ff, ACT_GELU);
-      __syncthreads();
-      mm(QKV, ff, L, ff, mh.li3w, C, C, mh.li3b, X, C, ACT_NONE, Y, nullptr, C);
-      __syncthreads();
-      float* W1 = G + pr * S * C;
-      float* W2 = G + (pr == 2 ? 0 : pr + 1) * S * C;
-      for (int it = threadIdx.x; it < L * C; it += NT) {
-        if (it < S * C) W1[it] = X[it];
-        else W2[it - S * C] = X[it];
-      }
-      __syncthreads();
-    }
-  }
-  // ee rows i*3S + m*S + j = G[m][j]: one contiguous run of 3S*c floats
-  float* out = a.ee + (g * S + i) * 3 * S * C;
-  for (int it = threadIdx.x; it < 3 * S * C; it += NT) out[it] = G[it];
-}
+__global__ void __launch_bounds__(NT) net_torso_kernel(TorsoArgs a) { torso<false>(a); }
+__global__ void __launch_bounds__(NT) net_torso_slice_kernel(TorsoArgs a) { torso<true>(a); }
 
 // ---- decoder ------------------------------------------------------------------------------------------------------
 // softmax in place over rows of n entries, a team of 32 lanes per row: for the cross-attention's J = 768 keys at
@@ -380,6 +226,20 @@ __device__ inline void softmax_rows_team(float* A, int rows, int n, int ld) {
     const float inv = 1.f / s;
     for (int j = lane; j < n; j += 32) a[j] *= inv;
   }
+}
+
+// The tail of an attention block, from the heads' output O and the block's input XB (R rows):
+// H1 = XB + li1(O); X = XB + (H1 + li3(gelu(li2(ln3(H1))))).  Ends with a barrier.
+__device__ inline void att_tail(const Mha& m, int R, int W, int hd, int ff, const float* O, const float* XB, float* H1,
+                                float* M, float* F, float* X) {
+  mm(O, hd, R, hd, m.li1w, W, W, m.li1b, H1, W, ACT_NONE, XB, nullptr, W);
+  __syncthreads();
+  layernorm(H1, W, R, W, m.ln3w, m.ln3b, M, W);
+  __syncthreads();
+  mm(M, W, R, W, m.li2w, ff, ff, m.li2b, F, ff, ACT_GELU);
+  __syncthreads();
+  mm(F, ff, R, ff, m.li3w, W, W, m.li3b, X, W, ACT_NONE, H1, XB, W);
+  __syncthreads();
 }
 
 struct DecArgs {
@@ -477,14 +337,7 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
       __syncthreads();
       for (int h = 0; h < H; ++h) mm(YB + h * wq, H * wq, R, W, a1.v + h * d, hd, d, nullptr, O + h * d, hd);
       __syncthreads();
-      mm(O, hd, R, hd, a1.li1w, W, W, a1.li1b, H1, W, ACT_NONE, XB, nullptr, W);
-      __syncthreads();
-      layernorm(H1, W, R, W, a1.ln3w, a1.ln3b, M, W);
-      __syncthreads();
-      mm(M, W, R, W, a1.li2w, ff, ff, a1.li2b, F, ff, ACT_GELU);
-      __syncthreads();
-      mm(F, ff, R, ff, a1.li3w, W, W, a1.li3b, X, W, ACT_NONE, H1, XB, W);
-      __syncthreads();
+      att_tail(a1, R, W, hd, ff, O, XB, H1, M, F, X);
       // ---- cross-attention: xb = ln2(x); x = xb + att2(xb, ee)
       layernorm(X, W, R, W, bln2, bln2 + W, XB, W);
       __syncthreads();
@@ -517,14 +370,7 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
       __syncthreads();
       for (int h = 0; h < H; ++h) mm(YB + h * wq, H * wq, R, C, a2.v + h * d, hd, d, nullptr, O + h * d, hd);
       __syncthreads();
-      mm(O, hd, R, hd, a2.li1w, W, W, a2.li1b, H1, W, ACT_NONE, XB, nullptr, W);
-      __syncthreads();
-      layernorm(H1, W, R, W, a2.ln3w, a2.ln3b, M, W);
-      __syncthreads();
-      mm(M, W, R, W, a2.li2w, ff, ff, a2.li2b, F, ff, ACT_GELU);
-      __syncthreads();
-      mm(F, ff, R, ff, a2.li3w, W, W, a2.li3b, X, W, ACT_NONE, H1, XB, W);
-      __syncthreads();
+      att_tail(a2, R, W, hd, ff, O, XB, H1, M, F, X);
     }
     if (t == 0)
       for (int it = threadIdx.x; it < R * W; it += NT) Z0[it] = X[it];
@@ -615,20 +461,19 @@ namespace {
 
 int check_cfg(const char* fn, const tg_net_config* c) {
   if (!c) return tg_internal_fail(TG_ERR_INVALID, "%s: null config", fn);
-  const int32_t dims[] = {c->S, c->T, c->dim_s, c->c, c->torso_layers, c->torso_heads, c->torso_d, c->torso_ff, c->W,
-                          c->heads, c->d, c->ff, c->blocks, c->n_steps, c->n_logits, c->n_hidden, c->n_quantile};
-  const char* names[] = {"dim_3d", "dim_t", "dim_s", "dim_c", "torso_layers", "torso_heads", "torso_d", "torso_ff",
-                         "W", "heads", "d", "ff", "blocks", "n_steps", "n_logits", "n_hidden", "n_quantile"};
-  const int32_t maxs[] = {TG_NET_MAX_S, TG_NET_MAX_T, TG_NET_MAX_DIM_S, TG_NET_MAX_C, TG_NET_MAX_LAYERS,
-                          TG_NET_MAX_HEADS, TG_NET_MAX_D, TG_NET_MAX_TORSO_FF, TG_NET_MAX_W, TG_NET_MAX_HEADS,
-                          TG_NET_MAX_D, TG_NET_MAX_FF, TG_NET_MAX_BLOCKS, TG_NET_MAX_STEPS, TG_NET_MAX_LOGITS,
-                          TG_NET_MAX_HIDDEN, TG_NET_MAX_QUANTILE};
-  const char* bound[] = {"TG_NET_MAX_S", "TG_NET_MAX_T", "TG_NET_MAX_DIM_S", "TG_NET_MAX_C", "TG_NET_MAX_LAYERS",
-                         "TG_NET_MAX_HEADS", "TG_NET_MAX_D", "TG_NET_MAX_TORSO_FF", "TG_NET_MAX_W", "TG_NET_MAX_HEADS",
-                         "TG_NET_MAX_D", "TG_NET_MAX_FF", "TG_NET_MAX_BLOCKS", "TG_NET_MAX_STEPS", "TG_NET_MAX_LOGITS",
-                         "TG_NET_MAX_HIDDEN", "TG_NET_MAX_QUANTILE"};
-  for (int i = 0; i < 17; ++i)
-    if (dims[i] < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, names[i], dims[i]);
+#define TG_LIM(v, name, M) {c->v, name, M, #M}
+  const struct { int32_t v; const char* name; int32_t max; const char* bound; } t[] = {
+      TG_LIM(S, "dim_3d", TG_NET_MAX_S), TG_LIM(T, "dim_t", TG_NET_MAX_T), TG_LIM(dim_s, "dim_s", TG_NET_MAX_DIM_S),
+      TG_LIM(c, "dim_c", TG_NET_MAX_C), TG_LIM(torso_layers, "torso_layers", TG_NET_MAX_LAYERS),
+      TG_LIM(torso_heads, "torso_heads", TG_NET_MAX_HEADS), TG_LIM(torso_d, "torso_d", TG_NET_MAX_D),
+      TG_LIM(torso_ff, "torso_ff", TG_NET_MAX_TORSO_FF), TG_LIM(W, "W", TG_NET_MAX_W),
+      TG_LIM(heads, "heads", TG_NET_MAX_HEADS), TG_LIM(d, "d", TG_NET_MAX_D), TG_LIM(ff, "ff", TG_NET_MAX_FF),
+      TG_LIM(blocks, "blocks", TG_NET_MAX_BLOCKS), TG_LIM(n_steps, "n_steps", TG_NET_MAX_STEPS),
+      TG_LIM(n_logits, "n_logits", TG_NET_MAX_LOGITS), TG_LIM(n_hidden, "n_hidden", TG_NET_MAX_HIDDEN),
+      TG_LIM(n_quantile, "n_quantile", TG_NET_MAX_QUANTILE)};
+#undef TG_LIM
+  for (const auto& e : t)
+    if (e.v < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, e.name, e.v);
   // S <= TG_NET_MAX_S as for every bound, or exactly TG_NET_WIDE_S or TG_NET_WIDE2_S with their own n_steps bounds instead
   const bool wide1 = c->S == TG_NET_WIDE_S, wide2 = c->S == TG_NET_WIDE2_S, wide = wide1 || wide2;
   if (c->S > TG_NET_MAX_S && !wide)
@@ -643,11 +488,11 @@ int check_cfg(const char* fn, const tg_net_config* c) {
                             c->n_steps, TG_NET_WIDE2_MAX_STEPS, c->S);
   for (int i = 1; i < 17; ++i) {
     if (wide && i == 13) continue;  // n_steps: its bound at a wide S is above
-    if (dims[i] > maxs[i])
-      return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, names[i], dims[i], bound[i], maxs[i]);
+    if (t[i].v > t[i].max)
+      return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, t[i].name, t[i].v, t[i].bound, t[i].max);
   }
-  // at S = TG_NET_WIDE2_S the torso runs by slices (net_torso_slice_kernel) and its term is the slice plan
-  const size_t lt = (wide2 ? tg::net::slice_plan(*c) : tg::net::torso_plan(*c)).total * sizeof(float),
+  // at S = TG_NET_WIDE2_S the torso runs by slices (net_torso_slice_kernel) and its term is one slice's plan
+  const size_t lt = tg::net::torso_plan(*c, wide2 ? 1 : c->S).total * sizeof(float),
                ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
   if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: the LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB", fn,
@@ -661,6 +506,19 @@ int check_common(const char* fn, const tg_net_config* c, const float* w, int64_t
   if (!w) return tg_internal_fail(TG_ERR_INVALID, "%s: null weights", fn);
   if (!aligned(w, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: weights not 4-byte aligned", fn);
   return TG_OK;
+}
+
+// the fields every decode takes; the caller adds its mode's inputs and outputs
+tg::net::DecArgs dec_args(const tg_net_config* cfg, const float* w, const float* ee, int64_t B, int k, int teacher) {
+  tg::net::DecArgs a{};
+  a.c = *cfg;
+  a.off = tg::net::offsets(*cfg);
+  a.w = w;
+  a.ee = ee;
+  a.B = B;
+  a.k = k;
+  a.teacher = teacher;
+  return a;
 }
 
 int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
@@ -713,12 +571,12 @@ int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, i
     if (B * cfg->S > INT32_MAX)
       return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn, (long long)B,
                               cfg->S);
-    const size_t lds = tg::net::slice_plan(*cfg).total * sizeof(float);
+    const size_t lds = tg::net::torso_plan(*cfg, 1).total * sizeof(float);
     if (int rc = lds_opt_in<tg::net::net_torso_slice_kernel>(fn, lds)) return rc;
     return launch(fn, tg::net::net_torso_slice_kernel, static_cast<unsigned>(B * cfg->S), tg::net::NT, lds,
                   static_cast<hipStream_t>(stream), a);
   }
-  const size_t lds = tg::net::torso_plan(*cfg).total * sizeof(float);
+  const size_t lds = tg::net::torso_plan(*cfg, cfg->S).total * sizeof(float);
   if (int rc = lds_opt_in<tg::net::net_torso_kernel>(fn, lds)) return rc;
   return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);
 }
@@ -735,14 +593,7 @@ int tg_net_sample(const tg_net_config* cfg, const float* w, const float* ee, con
   if (!ee || (!rows && !uniforms)) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee, or null rows without uniforms", fn);
   if (!aligned(ee, 4) || !aligned(rows, 8) || !aligned(uniforms, 4) || !aligned(probs, 4) || !aligned(q, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: ee, rows, uniforms, probs or q not aligned to their elements", fn);
-  tg::net::DecArgs a{};
-  a.c = *cfg;
-  a.off = tg::net::offsets(*cfg);
-  a.w = w;
-  a.ee = ee;
-  a.B = B;
-  a.k = k;
-  a.teacher = 0;
+  tg::net::DecArgs a = dec_args(cfg, w, ee, B, k, 0);
   a.rows = rows;
   a.seed_lo = static_cast<uint32_t>(seed);
   a.seed_hi = static_cast<uint32_t>(seed >> 32);
@@ -763,14 +614,7 @@ int tg_net_logits(const tg_net_config* cfg, const float* w, const float* ee, con
   if (!ee || !g_action) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee or g_action", fn);
   if (!aligned(ee, 4) || !aligned(g_action, 8) || !aligned(oo, 4) || !aligned(zz0, 4) || !aligned(q, 4))
     return tg_internal_fail(TG_ERR_INVALID, "%s: ee, g_action, oo, zz0 or q not aligned to their elements", fn);
-  tg::net::DecArgs a{};
-  a.c = *cfg;
-  a.off = tg::net::offsets(*cfg);
-  a.w = w;
-  a.ee = ee;
-  a.B = B;
-  a.k = 1;
-  a.teacher = 1;
+  tg::net::DecArgs a = dec_args(cfg, w, ee, B, 1, 1);
   a.q = q;
   a.g_action = g_action;
   a.oo = oo;

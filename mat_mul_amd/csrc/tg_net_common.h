@@ -1,5 +1,5 @@
-// Shared by tg_net.hip (inference) and tg_train.hip (training): the weight blob's layout of include/tensor_game_net.h
-// and the workgroup-level fp32 building blocks that work on activations in LDS.
+// Shared by tg_net.hip (inference) and tg_train.hip (training): the weight blob's layout of include/tensor_game_net.h,
+// the workgroup-level fp32 building blocks that work on activations in LDS, and the torso's input rows and row orders.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -165,6 +165,56 @@ __device__ inline void softmax_rows(float* A, int rows, int n, int ld) {
     }
     const float inv = 1.f / s;
     for (int j = 0; j < n; ++j) a[j] *= inv;
+  }
+}
+
+// ---- the torso's rows (inference's torso, training's torso_fwd and torso_bwd) ---------------------------------------
+// A workgroup holds nseq slices i0 <= i < i0 + nseq of a game's three grids as G[m][s][j] (s = i - i0, a row of c
+// channels each): nseq = S with i0 = 0 is the whole game, nseq = 1 one slice.  With nseq a constant 1 the mappings below
+// fold to the identity on a slice's rows.
+
+// the sequence s of token r, in rows of L tokens per sequence
+__device__ inline int seq_of(int r, int L, int nseq) { return nseq == 1 ? 0 : r / L; }
+
+// pair (m1, m2): token r = s*2S + u is grid m1 row (s, u) for u < S, grid m2 row (s, u - S) otherwise
+__device__ inline int pair_row(int r, int S, int nseq, int m1, int m2) {
+  const int s = seq_of(r, 2 * S, nseq), u = r - s * 2 * S;
+  return u < S ? (m1 * nseq + s) * S + u : (m2 * nseq + s) * S + u - S;
+}
+
+// ee row s*3S + m*S + j (counted from slice i0's first) is grid m row (s, j)
+__device__ inline int ee_row(int row, int S, int nseq) {
+  if (nseq == 1) return row;
+  const int s = row / (3 * S), m = (row / S) % 3, j = row % S;
+  return (m * nseq + s) * S + j;
+}
+
+// The torso's input rows of game g: IN[m][s][j][ch], ch = c3*T + t < S*T from the frames (int8 or float32, grid m
+// through its permutation of the three indices), ch = S*T the scalar projection at (i, j).
+__device__ inline void torso_inputs(const tg_net_config& c, const Off& off, const float* w, const void* frames,
+                                    int frames_i8, const float* scalars, int64_t g, int nseq, int i0, float* IN) {
+  const int S = c.S, S2 = S * S, cin = S * c.T + 1;
+  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
+  for (int it = threadIdx.x; it < 3 * nseq * S * cin; it += NT) {
+    const int ch = it % cin, j = (it / cin) % S, i = i0 + (it / (cin * S)) % nseq, m = it / (cin * S * nseq);
+    float v;
+    if (ch == cin - 1) {
+      const float* Wt = w + off.t_li1[m];
+      const int tok = i * S + j;
+      float s = 0.f;
+      for (int q = 0; q < c.dim_s; ++q) s = fmaf(scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
+      v = s + Wt[c.dim_s * S2 + tok];
+    } else {
+      const int c3 = ch / c.T, t = ch % c.T;
+      int a0, a1, a2;
+      if (m == 0) { a0 = i; a1 = j; a2 = c3; }
+      else if (m == 1) { a0 = j; a1 = c3; a2 = i; }
+      else { a0 = c3; a1 = i; a2 = j; }
+      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
+      v = frames_i8 ? static_cast<float>(static_cast<const int8_t*>(frames)[idx])
+                    : static_cast<const float*>(frames)[idx];
+    }
+    IN[it] = v;
   }
 }
 

@@ -188,6 +188,40 @@ __device__ inline void ln_bwd(const float* X, int R, int n, const float* __restr
   }
 }
 
+// softmax in place over the rows of the scores P (nseq x Lx x Ly), one thread per row; when causal, row a takes its
+// first a + 1 entries and the rest become 0
+__device__ inline void softmax_masked(const Geo& g, float* P) {
+  const int Lx = g.Lx, Ly = g.Ly;
+  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
+    float* p = P + row * Ly;
+    const int n = g.causal ? row % Lx + 1 : Ly;
+    float m = p[0];
+    for (int j = 1; j < n; ++j) m = fmaxf(m, p[j]);
+    float s = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const float e = expf(p[j] - m);
+      p[j] = e;
+      s += e;
+    }
+    const float inv = 1.f / s;
+    for (int j = 0; j < n; ++j) p[j] *= inv;
+    for (int j = n; j < Ly; ++j) p[j] = 0.f;
+  }
+}
+
+// dS = P (dP - rowsum(P dP)) / sqrt(d) in place over the rows of DS = dP, one thread per row
+__device__ inline void softmax_bwd(const Geo& g, const float* P, float* DS) {
+  const int Ly = g.Ly;
+  const float sd = sqrtf(static_cast<float>(g.d));
+  for (int row = threadIdx.x; row < g.nseq * g.Lx; row += NT) {
+    const float* p = P + row * Ly;
+    float* ds = DS + row * Ly;
+    float s = 0.f;
+    for (int b = 0; b < Ly; ++b) s = fmaf(p[b], ds[b], s);
+    for (int b = 0; b < Ly; ++b) ds[b] = p[b] * (ds[b] - s) / sd;
+  }
+}
+
 // One head's forward: Q (N x d), K, V (M x d), the attention P (nseq x Lx x Ly, 0 above the diagonal when causal) and
 // O = P V (N x d).
 __device__ inline void head_fwd(const Geo& g, const Mha& w, int h, const float* XN, const float* YN, float* sc) {
@@ -210,21 +244,7 @@ __device__ inline void head_fwd(const Geo& g, const Mha& w, int h, const float* 
     P[it] = acc / sd;
   }
   __syncthreads();
-  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
-    float* p = P + row * Ly;
-    const int n = g.causal ? row % Lx + 1 : Ly;
-    float m = p[0];
-    for (int j = 1; j < n; ++j) m = fmaxf(m, p[j]);
-    float s = 0.f;
-    for (int j = 0; j < n; ++j) {
-      const float e = expf(p[j] - m);
-      p[j] = e;
-      s += e;
-    }
-    const float inv = 1.f / s;
-    for (int j = 0; j < n; ++j) p[j] *= inv;
-    for (int j = n; j < Ly; ++j) p[j] = 0.f;
-  }
+  softmax_masked(g, P);
   __syncthreads();
   for (int it = threadIdx.x; it < N * d; it += NT) {
     const int e = it % d, r = it / d, s = r / Lx;
@@ -258,21 +278,7 @@ __device__ inline void head_fwd_kv(const Geo& g, const Mha& w, int h, const floa
     P[it] = acc / sd;
   }
   __syncthreads();
-  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
-    float* p = P + row * Ly;
-    const int n = g.causal ? row % Lx + 1 : Ly;
-    float m = p[0];
-    for (int j = 1; j < n; ++j) m = fmaxf(m, p[j]);
-    float s = 0.f;
-    for (int j = 0; j < n; ++j) {
-      const float e = expf(p[j] - m);
-      p[j] = e;
-      s += e;
-    }
-    const float inv = 1.f / s;
-    for (int j = 0; j < n; ++j) p[j] *= inv;
-    for (int j = n; j < Ly; ++j) p[j] = 0.f;
-  }
+  softmax_masked(g, P);
   __syncthreads();
   for (int it = threadIdx.x; it < N * c2; it += NT) {
     const int i = it % c2, r = it / c2, s = r / Lx;
@@ -345,14 +351,7 @@ __device__ inline void head_bwd_kv(const Geo& g, const Mha& w, const GMha& gw, i
     DS[it] = acc;
   }
   __syncthreads();
-  const float sd = sqrtf(static_cast<float>(d));
-  for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
-    const float* p = P + row * Ly;
-    float* ds = DS + row * Ly;
-    float s = 0.f;
-    for (int b = 0; b < Ly; ++b) s = fmaf(p[b], ds[b], s);
-    for (int b = 0; b < Ly; ++b) ds[b] = p[b] * (ds[b] - s) / sd;
-  }
+  softmax_bwd(g, P, DS);
   __syncthreads();
   for (int it = threadIdx.x; it < N * c2; it += NT) {
     const int i = it % c2, r = it / c2, s = r / Lx;
@@ -421,7 +420,6 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
   for (int it = threadIdx.x; it < M * c2; it += NT) DYN[it] = 0.f;
   bgrad(DH1, c1, N, c1, gw.li1b);
   __syncthreads();
-  const float sd = sqrtf(static_cast<float>(d));
   for (int h = 0; h < g.H; ++h) {
     if constexpr (KV) {
       head_bwd_kv(g, w, gw, h, XN, YN, DH1, DXN, DYN, sc);
@@ -448,14 +446,7 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
       DV[it] = acc;
     }
     __syncthreads();
-    // dS = P * (dP - sum_b P dP) / sqrt(d)
-    for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
-      const float* p = P + row * Ly;
-      float* ds = DS + row * Ly;
-      float s = 0.f;
-      for (int b = 0; b < Ly; ++b) s = fmaf(p[b], ds[b], s);
-      for (int b = 0; b < Ly; ++b) ds[b] = p[b] * (ds[b] - s) / sd;
-    }
+    softmax_bwd(g, P, DS);
     __syncthreads();
     // dQ = dS K, dK = dS^T Q
     for (int it = threadIdx.x; it < N * d; it += NT) {
@@ -617,40 +608,6 @@ __device__ inline void game_range(const Args& a, int64_t& g0, int64_t& g1) {
   g1 = a.B * (blockIdx.x + 1) / a.P;
 }
 
-// IN[m][tok][ch] of the torso input projection for game g (tg_net.hip's net_torso_kernel), scalars into SS
-__device__ inline void torso_inputs(const Args& a, int64_t g, float* IN, float* SS) {
-  const tg_net_config& c = a.c;
-  const int S = c.S, S2 = S * S, cin = S * c.T + 1;
-  const int64_t fstride = static_cast<int64_t>(c.T) * S2 * S;
-  for (int it = threadIdx.x; it < 3 * S2 * cin; it += NT) {
-    const int ch = it % cin, tok = (it / cin) % S2, m = it / (cin * S2);
-    float v;
-    if (ch == cin - 1) {
-      const float* Wt = a.w + a.off.t_li1[m];
-      float s = 0.f;
-      for (int q = 0; q < c.dim_s; ++q) s = fmaf(a.scalars[g * c.dim_s + q], Wt[q * S2 + tok], s);
-      v = s + Wt[c.dim_s * S2 + tok];
-    } else {
-      const int p = tok / S, q = tok % S, c3 = ch / c.T, t = ch % c.T;
-      int a0, a1, a2;
-      if (m == 0) { a0 = p; a1 = q; a2 = c3; }
-      else if (m == 1) { a0 = q; a1 = c3; a2 = p; }
-      else { a0 = c3; a1 = p; a2 = q; }
-      const int64_t idx = g * fstride + ((static_cast<int64_t>(t) * S + a0) * S + a1) * S + a2;
-      v = a.frames_i8 ? static_cast<float>(static_cast<const int8_t*>(a.frames)[idx])
-                      : static_cast<const float*>(a.frames)[idx];
-    }
-    IN[it] = v;
-  }
-  for (int q = threadIdx.x; q < c.dim_s; q += NT) SS[q] = a.scalars[g * c.dim_s + q];
-}
-
-// pair rows: token r = i*2S + u is grid m1 row (i, u) for u < S, grid m2 row (i, u - S) otherwise
-__device__ inline int pair_row(int r, int S, int m1, int m2) {
-  const int i = r / (2 * S), u = r % (2 * S);
-  return u < S ? m1 * S * S + i * S + u : m2 * S * S + i * S + u - S;
-}
-
 // ---- kernel 1: the torso forward, saving each pair's input ----------------------------------------------------------
 // CHUNKED (S = TG_NET_WIDE_S): a pair's S sequences are independent (layernorm and the MLP are row-wise, attention stays
 // inside a sequence), so its attention block runs over `chunk` sequences at a time with scratch for that many.
@@ -663,7 +620,7 @@ __device__ inline void torso_fwd(const Args& a, int chunk) {
   if (g >= a.B) return;
   const TPlan L = CHUNKED ? tplan(c, chunk) : tplan(c);
   float *G = lds + L.G, *IN = lds + L.IN, *X = lds + L.X, *OUT = lds + L.DO, *SCR = lds + L.SCR;
-  torso_inputs(a, g, IN, lds + L.SS);
+  net::torso_inputs(c, a.off, a.w, a.frames, a.frames_i8, a.scalars, g, S, 0, IN);
   __syncthreads();
   for (int m = 0; m < 3; ++m) {
     const float* Wt = a.w + a.off.t_li2[m];
@@ -677,7 +634,7 @@ __device__ inline void torso_fwd(const Args& a, int chunk) {
       const int m1 = pr, m2 = pr == 2 ? 0 : pr + 1;
       float* save = a.act + ((g * c.torso_layers + l) * 3 + pr) * T2 * C;
       for (int it = threadIdx.x; it < T2 * C; it += NT) {
-        const float v = G[pair_row(it / C, S, m1, m2) * C + it % C];
+        const float v = G[net::pair_row(it / C, S, S, m1, m2) * C + it % C];
         X[it] = v;
         save[it] = v;
       }
@@ -690,15 +647,12 @@ __device__ inline void torso_fwd(const Args& a, int chunk) {
       } else {
         mha_fwd(geo, mh, X, X, OUT, SCR);
       }
-      for (int it = threadIdx.x; it < T2 * C; it += NT) G[pair_row(it / C, S, m1, m2) * C + it % C] = OUT[it];
+      for (int it = threadIdx.x; it < T2 * C; it += NT) G[net::pair_row(it / C, S, S, m1, m2) * C + it % C] = OUT[it];
       __syncthreads();
     }
   }
   float* out = a.ee + g * 3 * S2 * C;
-  for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) {
-    const int ch = it % C, row = it / C, i = row / (3 * S), m = (row / S) % 3, j = row % S;
-    out[it] = G[(m * S2 + i * S + j) * C + ch];
-  }
+  for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) out[it] = G[net::ee_row(it / C, S, S) * C + it % C];
 }
 
 __global__ void __launch_bounds__(NT) train_torso_fwd_kernel(Args a) { torso_fwd<false>(a, 0); }
@@ -927,11 +881,9 @@ __device__ inline void torso_bwd(const Args& a, int chunk) {
   game_range(a, ga, gz);
   for (int64_t g = ga; g < gz; ++g) {
     const float* dee = a.dee + g * 3 * S2 * C;
-    for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) {
-      const int ch = it % C, row = it / C, i = row / (3 * S), m = (row / S) % 3, j = row % S;
-      DG[(m * S2 + i * S + j) * C + ch] = dee[it];
-    }
-    torso_inputs(a, g, IN, SS);
+    for (int it = threadIdx.x; it < 3 * S2 * C; it += NT) DG[net::ee_row(it / C, S, S) * C + it % C] = dee[it];
+    net::torso_inputs(c, a.off, a.w, a.frames, a.frames_i8, a.scalars, g, S, 0, IN);
+    for (int q = threadIdx.x; q < c.dim_s; q += NT) SS[q] = a.scalars[g * c.dim_s + q];
     __syncthreads();
     for (int l = c.torso_layers - 1; l >= 0; --l) {
       const int64_t lo = a.off.t_layer0 + l * a.off.t_layer;
@@ -942,7 +894,7 @@ __device__ inline void torso_bwd(const Args& a, int chunk) {
         const float* save = a.act + ((g * c.torso_layers + l) * 3 + pr) * T2 * C;
         for (int it = threadIdx.x; it < T2 * C; it += NT) {
           X[it] = save[it];
-          DO[it] = DG[pair_row(it / C, S, m1, m2) * C + it % C];
+          DO[it] = DG[net::pair_row(it / C, S, S, m1, m2) * C + it % C];
           DXP[it] = 0.f;
         }
         __syncthreads();
@@ -955,7 +907,7 @@ __device__ inline void torso_bwd(const Args& a, int chunk) {
         } else {
           mha_bwd(geo, mh, gm, X, X, DO, DXP, DXP, SCR);
         }
-        for (int it = threadIdx.x; it < T2 * C; it += NT) DG[pair_row(it / C, S, m1, m2) * C + it % C] = DXP[it];
+        for (int it = threadIdx.x; it < T2 * C; it += NT) DG[net::pair_row(it / C, S, S, m1, m2) * C + it % C] = DXP[it];
         __syncthreads();
       }
     }
@@ -1043,6 +995,22 @@ int check_train_cfg(const char* fn, const tg_net_config* c) {
   return TG_OK;
 }
 
+// The four launches of one call: the torso forward, the decoder, the torso backward when a gradient is wanted, the
+// reduction.  lt, ld: the LDS bytes of the torso kernels and of the decoder; chunk: the chunked torso kernels' argument.
+template <auto FWD, auto DEC, auto BWD, class... Chunk>
+int launch_all(const char* fn, const tg::train::Args& a, size_t lt, size_t ld, hipStream_t st, Chunk... chunk) {
+  const unsigned NT = tg::net::NT, P = static_cast<unsigned>(a.P);
+  const int gb = a.grad ? static_cast<int>((a.off.total + NT - 1) / NT) : 0;
+  if (int rc = lds_opt_in<FWD>(fn, lt)) return rc;
+  if (int rc = lds_opt_in<DEC>(fn, ld)) return rc;
+  if (int rc = lds_opt_in<BWD>(fn, lt)) return rc;
+  if (int rc = launch(fn, FWD, static_cast<unsigned>(a.B), NT, lt, st, a, chunk...)) return rc;
+  if (int rc = launch(fn, DEC, P, NT, ld, st, a)) return rc;
+  if (a.grad)
+    if (int rc = launch(fn, BWD, P, NT, lt, st, a, chunk...)) return rc;
+  return launch(fn, tg::train::train_reduce_kernel, static_cast<unsigned>(gb + 1), NT, 0, st, a, gb);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1116,35 +1084,14 @@ int tg_net_loss_grad(const tg_net_config* cfg, const float* theta, const float* 
   a.losses = losses;
   a.status = status;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int gb = grad ? static_cast<int>((a.off.total + tg::net::NT - 1) / tg::net::NT) : 0;
-  if (tg::train::wide(*cfg)) {
-    const int chunk = tg::train::torso_chunk(*cfg);
-    const size_t lt = tg::train::tplan(*cfg, chunk).total * sizeof(float),
-                 ld = tg::train::dplan_kv(*cfg).total * sizeof(float);
-    if (int rc = lds_opt_in<tg::train::train_torso_fwd_chunk_kernel>(fn, lt)) return rc;
-    if (int rc = lds_opt_in<tg::train::train_decode_kv_kernel>(fn, ld)) return rc;
-    if (int rc = lds_opt_in<tg::train::train_torso_bwd_chunk_kernel>(fn, lt)) return rc;
-    if (int rc = launch(fn, tg::train::train_torso_fwd_chunk_kernel, static_cast<unsigned>(B), tg::net::NT, lt, st, a,
-                        chunk))
-      return rc;
-    if (int rc = launch(fn, tg::train::train_decode_kv_kernel, static_cast<unsigned>(a.P), tg::net::NT, ld, st, a))
-      return rc;
-    if (grad)
-      if (int rc = launch(fn, tg::train::train_torso_bwd_chunk_kernel, static_cast<unsigned>(a.P), tg::net::NT, lt, st,
-                          a, chunk))
-        return rc;
-    return launch(fn, tg::train::train_reduce_kernel, static_cast<unsigned>(gb + 1), tg::net::NT, 0, st, a, gb);
+  using namespace tg::train;
+  if (wide(*cfg)) {
+    const int chunk = torso_chunk(*cfg);
+    return launch_all<train_torso_fwd_chunk_kernel, train_decode_kv_kernel, train_torso_bwd_chunk_kernel>(
+        fn, a, tplan(*cfg, chunk).total * sizeof(float), dplan_kv(*cfg).total * sizeof(float), st, chunk);
   }
-  const size_t lt = tg::train::tplan(*cfg).total * sizeof(float), ld = tg::train::dplan(*cfg).total * sizeof(float);
-  if (int rc = lds_opt_in<tg::train::train_torso_fwd_kernel>(fn, lt)) return rc;
-  if (int rc = lds_opt_in<tg::train::train_decode_kernel>(fn, ld)) return rc;
-  if (int rc = lds_opt_in<tg::train::train_torso_bwd_kernel>(fn, lt)) return rc;
-  if (int rc = launch(fn, tg::train::train_torso_fwd_kernel, static_cast<unsigned>(B), tg::net::NT, lt, st, a)) return rc;
-  if (int rc = launch(fn, tg::train::train_decode_kernel, static_cast<unsigned>(a.P), tg::net::NT, ld, st, a)) return rc;
-  if (grad)
-    if (int rc = launch(fn, tg::train::train_torso_bwd_kernel, static_cast<unsigned>(a.P), tg::net::NT, lt, st, a))
-      return rc;
-  return launch(fn, tg::train::train_reduce_kernel, static_cast<unsigned>(gb + 1), tg::net::NT, 0, st, a, gb);
+  return launch_all<train_torso_fwd_kernel, train_decode_kernel, train_torso_bwd_kernel>(
+      fn, a, tplan(*cfg).total * sizeof(float), dplan(*cfg).total * sizeof(float), st);
 }
 
 }  // extern "C"
