@@ -1,4 +1,4 @@
-// tg_genfused.h -- the synthetic-demonstration generator in ONE kernel (included by tg_kernels.hip after tg_mfma.h).
+// tg_genfused.h -- the synthetic-demonstration generator in ONE kernel (included inside namespace tg by tg_kernels.hip after tg_mfma.h).
 //
 // create_synthetic_demo (utils.py:203-233) / _create_synthetic_demos (datasets.py:124-142) for S = 9, 16, 25:
 //   Philox -> factor bytes in registers -> [change of basis: one int8 MFMA per (mode, 32 actions)] -> the transposed

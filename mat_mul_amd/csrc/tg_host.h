@@ -18,7 +18,7 @@ int tg_internal_fail(int code, const char* fmt, ...);  // records tg_last_error(
 // the key pass of tg_expand_keyed_i8 (tg_aux.hip)
 extern "C" int tg_internal_hash(const int8_t* state, uint64_t* hash_out, int64_t B, int S, int64_t stride, hipStream_t st);
 namespace tg { struct Dist; }
-// the generator in one kernel (tg_genfused.h, launched from tg_kernels.hip), called by tg_gen_demos_i8 (tg_gen.hip):
+// the generator in one kernel (tg_genfused.h, launched from the host side of tg_kernels.hip), called by tg_gen_demos_i8 (tg_gen.hip):
 // 1 = launched, 0 = not applicable (the caller takes the token kernel + tg_gen_from_factors_i8), < 0 = error
 int tg_internal_gen_fused(int8_t* target, int8_t* actions, uint8_t* overflow, const int8_t* basis, int64_t B, int S,
                           int R, const tg::Dist& D, int shift, uint64_t seed, uint64_t gid0, int64_t stride,

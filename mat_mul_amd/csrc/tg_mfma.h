@@ -1,4 +1,4 @@
-// tg_mfma.h -- accumulation over many rank-1 terms on the matrix cores (included by tg_kernels.hip):
+// tg_mfma.h -- accumulation over many rank-1 terms on the matrix cores (included inside namespace tg by tg_kernels.hip after tg_apply.h):
 // genf_mfma_kernel (tg_gen_from_factors_i8, the generator) and many_mfma_kernel (tg_step_many_i8, below).
 //
 // target[i][j][l] = sum_r u_r[i] v_r[j] w_r[l]   (reference utils.py:218-232, datasets.py:127-141)

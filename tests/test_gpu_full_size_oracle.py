@@ -46,10 +46,10 @@ SIZES = {
     "step_s4_token_wait": (4, (384 * MiB, INF), "states"),               # token awaited first (kS4TokenWaitBytes ..)
     "step_s16_lines": (16, (96 * MiB, 320 * MiB), "states"),             # whole-line stores (96 MiB .. kNtLoadsFromBytes)
     "step_s16_nt_loads": (16, (320 * MiB, 1280 * MiB), "states"),        # [kNtLoadsFromBytes, kNtLoadsToBytes)
-    "step_s16_lds_pad": (16, (1280 * MiB, INF), "states"),               # s16_lds_pad: occupancy held down
+    "step_s16_lds_pad": (16, (1280 * MiB, INF), "states"),               # kS16LdsPad: occupancy held down
     "step_s25_lines": (25, (96 * MiB, 320 * MiB), "states"),
     "step_s25_nt_loads": (25, (320 * MiB, 1280 * MiB), "states"),
-    "step_s25_lds_pad": (25, (1280 * MiB, INF), "states"),               # s25_lds_pad, plain stores again
+    "step_s25_lds_pad": (25, (1280 * MiB, INF), "states"),               # kS25LdsPad, plain stores again
     "step_s9_streaming": (9, (96 * MiB, INF), "states"),                 # s9_step_kernel beyond the L2s and the cache
     # tg_step_tracked_i8
     "tracked_s16_crossover": (16, (12000, INF), "games"),                # TensorGameEnv.TRACKED_FROM[16]

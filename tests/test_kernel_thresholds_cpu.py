@@ -32,15 +32,14 @@ PINS = [
     ("tg_kernels.hip", r"constexpr int64_t kLanesFrom = (\d+);", 57344, "stream_s4_rounds (the lane kernel's layout)"),
     ("tg_kernels.hip", r"constexpr int64_t kTrackedSparse25 = (\d+);", 2048, "tracked_s25_sparse"),
     # the S=4 step: non-temporal loads from 96 MiB, the alternating sweep above 16 MiB
-    ("tg_kernels.hip", r"const bool nt = \(bytes >= \((\d+)ll << 20\)", 96, "step_s4_plain_reversed, step_s4_nt_loads"),
-    ("tg_kernels.hip", r"bytes > \((\d+)ll << 20\) \? a\.sweep : 0", 16, "step_s4_plain_one_way, step_s4_plain_reversed"),
+    ("tg_kernels.hip", r"constexpr int64_t kS4NtLoadsFromBytes = (\d+)ll << 20;", 96, "step_s4_plain_reversed, step_s4_nt_loads"),
+    ("tg_kernels.hip", r"constexpr int64_t kS4SweepAboveBytes = (\d+)ll << 20;", 16, "step_s4_plain_one_way, step_s4_plain_reversed"),
     # S=16 / S=25 whole-line stores from 96 MiB
-    ("tg_kernels.hip", r"else if \(\(B \* a\.in_stride >= \((\d+)ll << 20\) \|\| TG_SWITCH\(\"TG_S16_LINES\"\)\)\)", 96,
-     "step_s16_lines"),
-    ("tg_kernels.hip", r"\(\(bytes25 >= \((\d+)ll << 20\) && bytes25 < kNtLoadsToBytes\)", 96, "step_s25_lines"),
+    ("tg_kernels.hip", r"constexpr int64_t kLinesFromBytes = (\d+)ll << 20;", 96, "step_s16_lines"),
+    ("tg_kernels.hip", r"constexpr int64_t kLinesFromBytes = (\d+)ll << 20;", 96, "step_s25_lines"),
     # copy: by the bytes of both buffers, and the byte path's grid
-    ("tg_kernels.hip", r"else if \(both > \((\d+)ll << 20\) \|\| TG_SWITCH\(\"TG_COPY_NT2\"\)\)", 640, "copy_s16_nt1, copy_s16_nt2"),
-    ("tg_kernels.hip", r"else if \(both > \((\d+)ll << 20\) \|\| TG_SWITCH\(\"TG_COPY_NT1\"\)\)", 256, "copy_s16_nt1"),
+    ("tg_kernels.hip", r"kCopyNtStoresAboveBytes = (\d+)ll << 20;", 640, "copy_s16_nt1, copy_s16_nt2"),
+    ("tg_kernels.hip", r"constexpr int64_t kCopyNtLoadsAboveBytes = (\d+)ll << 20,", 256, "copy_s16_nt1"),
     ("tg_kernels.hip", r"copy_bytes_kernel, grid_for\(B, (\d+)\)", 65536, "copy_bytes_grid_cap"),
     # grid caps
     ("tg_kernels.hip", r"done_kernel, grid_for\(blocks, (\d+)\)", 8192, "done_s4_grid_cap, done_s16_grid_cap"),

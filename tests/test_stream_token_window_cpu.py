@@ -7,7 +7,7 @@ token byte the step reads is covered."""
 import re
 from pathlib import Path
 
-SRC = (Path(__file__).resolve().parent.parent / "mat_mul_amd" / "csrc" / "tg_kernels.hip").read_text()
+SRC = (Path(__file__).resolve().parent.parent / "mat_mul_amd" / "csrc" / "tg_stream.h").read_text()
 
 
 def kernel_body():

@@ -2,7 +2,7 @@
 """Audit of the resident steppers' hand-issued loads (tg_step_stream_i8): an inline-asm load's VGPR destination counts as
 written at the end of the statement as far as hipcc knows, so the compiler may read, copy or spill it before the data has
 arrived.  The kernels tie those registers to their counted wait ("+v"), which pins ORDER, not register allocation: this
-script compiles tg_kernels.hip to assembly and checks, for every s4 / s16 stream kernel, that no instruction between an
+script compiles tg_kernels.hip (which includes tg_stream.h, their home) to assembly and checks, for every s4 / s16 stream kernel, that no instruction between an
 `sc1` load and the next arrival wait (vmcnt <= 2; <= 13 in the double-buffered lane kernel) touches the load's destination, and that the kernels use no scratch.
 (s25_stream_kernel receives its tokens by LDS-DMA: no VGPR destination; it is checked for having no VGPR sc1 loads
 outside the compiler-visible polls, which are followed by vmcnt(0).)
