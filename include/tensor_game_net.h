@@ -118,6 +118,20 @@ int tg_net_sample(const tg_net_config* cfg, const float* w, const float* ee, con
                   uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
                   tg_stream_t stream);
 
+/* tg_net_torso and tg_net_sample on the rows a device-side mask selects.  flags uint8 (B): row g is ACTIVE when
+ * (flags[g] & need) == need; flags = NULL means every row (need is then ignored) and equals the plain entry bit for bit.
+ * Every workgroup of an inactive row returns at once: the row's inputs are not read and its ee, tokens_i8, probs and q
+ * are NOT WRITTEN (they keep what they held).  An active row's results are those of the plain entry, bit for bit: a
+ * row's result depends on nothing but that row.  The mask is read when the kernel runs, so a captured graph follows the
+ * current contents of flags.  need outside 1 .. 255 with flags given is TG_ERR_INVALID; every other check is the plain
+ * entry's, in its order.  The self-play driver passes the search's flags (tensor_game_search.h) with
+ * need = TG_SEARCH_EXPAND | TG_SEARCH_PENDING, and need = TG_SEARCH_RETRY for a retry. */
+int tg_net_torso_masked(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8,
+                        const float* scalars, float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream);
+int tg_net_sample_masked(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B, int k,
+                         uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
+                         const uint8_t* flags, int need, tg_stream_t stream);
+
 /* The forward of PolicyHead.fwd_train (model.py:219-232) and the ValueHead on its zz[:, 0], in ONE launch: ee float32
  * (B,3S^2,c), g_action int64 (B,n_steps) (tokens in [0, n_logits); the input is START then g_action shifted by one)
  * -> oo float32 (B,n_steps,n_logits), zz0 float32 (B,W), q float32 (B,n_quantile) (the raw quantiles).  Any output may

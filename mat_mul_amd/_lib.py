@@ -114,6 +114,8 @@ NET_SIGNATURES = {
     "tg_net_weights_size": [_p, _p],
     "tg_net_torso": [_p, _p, _p, _i, _p, _p, _i64, _p],
     "tg_net_sample": [_p, _p, _p, _p, _i64, _i, _u64, _u64, _p, _p, _p, _p, _p],
+    "tg_net_torso_masked": [_p, _p, _p, _i, _p, _p, _i64, _p, _i, _p],
+    "tg_net_sample_masked": [_p, _p, _p, _p, _i64, _i, _u64, _u64, _p, _p, _p, _p, _p, _i, _p],
     "tg_net_logits": [_p, _p, _p, _p, _i64, _p, _p, _p, _p],
 }
 

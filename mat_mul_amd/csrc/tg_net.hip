@@ -19,6 +19,9 @@
 //     that holds sample 0, on the position-0 output.
 //     At S = TG_NET_WIDE2_S (J = 768 keys) the cross-attention's softmax runs a 32-lane team per row
 //     (net_decode_kernel<true>); every other size keeps one thread per row and its token-order sums.
+// Row mask (tg_net_torso_masked, tg_net_sample_masked): every workgroup of a game whose flags byte lacks one of the `need`
+// bits (net::active) returns before its first barrier and before any load of the game's inputs, and writes nothing.  The
+// test is uniform over the workgroup, and over the S slice workgroups / the `chunks` decoder workgroups of a game.
 // Every matrix product goes through mm(): thread = (output column, group of RB rows), the weight element read once per
 // RB rows, the rows read from LDS as broadcasts.
 #include <hip/hip_runtime.h>
@@ -100,6 +103,8 @@ struct TorsoArgs {
   const float* scalars;
   float* ee;
   int64_t B;
+  const uint8_t* flags;  // (B) or NULL: the row mask (net::active)
+  uint8_t need;
 };
 
 // The torso of game g over nseq of its S slices: G holds their rows [m][s][j][ch]; a pair (m1, m2) is nseq independent
@@ -114,7 +119,7 @@ __device__ inline void torso(const TorsoArgs& a) {
   const int S = c.S, nseq = SLICE ? 1 : S, L = 2 * S, N = nseq * L, C = c.c, cin = S * c.T + 1;
   const int64_t g = SLICE ? blockIdx.x / S : blockIdx.x;
   const int i0 = SLICE ? static_cast<int>(blockIdx.x % S) : 0;
-  if (g >= a.B) return;
+  if (g >= a.B || !active(a.flags, a.need, g)) return;
   const TorsoPlan P = torso_plan(c, nseq);
   float *G = lds + P.G, *X = lds + P.X, *XN = lds + P.XN, *YN = lds + P.YN, *Y = lds + P.Y, *QKV = lds + P.QKV,
         *SC = lds + P.SC;
@@ -258,6 +263,8 @@ struct DecArgs {
   const int64_t* g_action;  // teacher: (B,n_steps)
   float* oo;                // teacher: (B,n_steps,n_logits)
   float* zz0;               // teacher: (B,W)
+  const uint8_t* flags;     // sampling: (B) or NULL, the row mask (net::active)
+  uint8_t need;
 };
 
 // kTeam: the cross-attention's softmax by teams (the host takes it for J > kTeamSoftmaxFrom); the other instantiation is
@@ -267,7 +274,7 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
   const int64_t g = blockIdx.x / a.chunks;
-  if (g >= a.B) return;
+  if (g >= a.B || !active(a.flags, a.need, g)) return;
   const int s0 = static_cast<int>(blockIdx.x % a.chunks) * a.R;
   const int R = a.k - s0 < a.R ? a.k - s0 : a.R;  // rows of this workgroup: samples s0 .. s0+R-1
   const int W = c.W, C = c.c, H = c.heads, d = c.d, hd = H * d, ff = c.ff, J = 3 * c.S * c.S, NS = c.n_steps;
@@ -540,6 +547,68 @@ int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
   return launch(fn, tg::net::net_decode_kernel<false>, grid, tg::net::NT, lds, st, a);
 }
 
+// the row mask of the *_masked entries: NULL flags = every row (need is then ignored)
+int check_mask(const char* fn, const uint8_t* flags, int need) {
+  if (flags && (need < 1 || need > 255))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: need=%d with flags given (the bits a row's flags must hold, 1 .. 255)", fn,
+                            need);
+  return TG_OK;
+}
+
+// tg_net_torso and tg_net_torso_masked
+int torso_entry(const char* fn, const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8,
+                const float* scalars, float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream) {
+  if (int rc = check_common(fn, cfg, w, B)) return rc;
+  if (frames_is_i8 != 0 && frames_is_i8 != 1)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_is_i8=%d (0 float32, 1 int8)", fn, frames_is_i8);
+  if (int rc = check_mask(fn, flags, need)) return rc;
+  if (B == 0) return TG_OK;
+  if (!frames || !scalars || !ee) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames, scalars or ee", fn);
+  if (!aligned(frames, frames_is_i8 ? 1 : 4) || !aligned(scalars, 4) || !aligned(ee, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
+  tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B, flags,
+                       static_cast<uint8_t>(flags ? need : 0)};
+  // by slices at S = TG_NET_WIDE2_S; in the A/B library also where TG_NET_TORSO_SLICES is set (any size, for comparison)
+  if (cfg->S == TG_NET_WIDE2_S || TG_SWITCH("TG_NET_TORSO_SLICES")) {
+    if (B * cfg->S > INT32_MAX)
+      return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn, (long long)B,
+                              cfg->S);
+    const size_t lds = tg::net::torso_plan(*cfg, 1).total * sizeof(float);
+    if (int rc = lds_opt_in<tg::net::net_torso_slice_kernel>(fn, lds)) return rc;
+    return launch(fn, tg::net::net_torso_slice_kernel, static_cast<unsigned>(B * cfg->S), tg::net::NT, lds,
+                  static_cast<hipStream_t>(stream), a);
+  }
+  const size_t lds = tg::net::torso_plan(*cfg, cfg->S).total * sizeof(float);
+  if (int rc = lds_opt_in<tg::net::net_torso_kernel>(fn, lds)) return rc;
+  return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);
+}
+
+// tg_net_sample and tg_net_sample_masked
+int sample_entry(const char* fn, const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B,
+                 int k, uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
+                 const uint8_t* flags, int need, tg_stream_t stream) {
+  if (int rc = check_common(fn, cfg, w, B)) return rc;
+  if (k < 1 || k > TG_NET_MAX_SAMPLES)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: k=%d outside [1, TG_NET_MAX_SAMPLES=%d]", fn, k, TG_NET_MAX_SAMPLES);
+  if (int rc = check_mask(fn, flags, need)) return rc;
+  if (B == 0) return TG_OK;
+  if (!ee || (!rows && !uniforms)) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee, or null rows without uniforms", fn);
+  if (!aligned(ee, 4) || !aligned(rows, 8) || !aligned(uniforms, 4) || !aligned(probs, 4) || !aligned(q, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, rows, uniforms, probs or q not aligned to their elements", fn);
+  tg::net::DecArgs a = dec_args(cfg, w, ee, B, k, 0);
+  a.rows = rows;
+  a.seed_lo = static_cast<uint32_t>(seed);
+  a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.call_lo = static_cast<uint32_t>(call);
+  a.uniforms = uniforms;
+  a.tokens = tokens_i8;
+  a.probs = probs;
+  a.q = q;
+  a.flags = flags;
+  a.need = static_cast<uint8_t>(flags ? need : 0);
+  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -557,52 +626,27 @@ int tg_net_weights_size(const tg_net_config* cfg, int64_t* floats) {
 // Torso.forward, model.py:97-123
 int tg_net_torso(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8, const float* scalars,
                  float* ee, int64_t B, tg_stream_t stream) {
-  const char* fn = "tg_net_torso";
-  if (int rc = check_common(fn, cfg, w, B)) return rc;
-  if (frames_is_i8 != 0 && frames_is_i8 != 1)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: frames_is_i8=%d (0 float32, 1 int8)", fn, frames_is_i8);
-  if (B == 0) return TG_OK;
-  if (!frames || !scalars || !ee) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames, scalars or ee", fn);
-  if (!aligned(frames, frames_is_i8 ? 1 : 4) || !aligned(scalars, 4) || !aligned(ee, 4))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
-  tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B};
-  // by slices at S = TG_NET_WIDE2_S; in the A/B library also where TG_NET_TORSO_SLICES is set (any size, for comparison)
-  if (cfg->S == TG_NET_WIDE2_S || TG_SWITCH("TG_NET_TORSO_SLICES")) {
-    if (B * cfg->S > INT32_MAX)
-      return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn, (long long)B,
-                              cfg->S);
-    const size_t lds = tg::net::torso_plan(*cfg, 1).total * sizeof(float);
-    if (int rc = lds_opt_in<tg::net::net_torso_slice_kernel>(fn, lds)) return rc;
-    return launch(fn, tg::net::net_torso_slice_kernel, static_cast<unsigned>(B * cfg->S), tg::net::NT, lds,
-                  static_cast<hipStream_t>(stream), a);
-  }
-  const size_t lds = tg::net::torso_plan(*cfg, cfg->S).total * sizeof(float);
-  if (int rc = lds_opt_in<tg::net::net_torso_kernel>(fn, lds)) return rc;
-  return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);
+  return torso_entry("tg_net_torso", cfg, w, frames, frames_is_i8, scalars, ee, B, nullptr, 0, stream);
+}
+
+int tg_net_torso_masked(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8,
+                        const float* scalars, float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream) {
+  return torso_entry("tg_net_torso_masked", cfg, w, frames, frames_is_i8, scalars, ee, B, flags, need, stream);
 }
 
 // PolicyHead.fwd_infer + ValueHead + value_risk_mgmt, model.py:234-261, 266-280, 322-324 (AlphaTensor.fwd_infer :347-356)
 int tg_net_sample(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B, int k,
                   uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
                   tg_stream_t stream) {
-  const char* fn = "tg_net_sample";
-  if (int rc = check_common(fn, cfg, w, B)) return rc;
-  if (k < 1 || k > TG_NET_MAX_SAMPLES)
-    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: k=%d outside [1, TG_NET_MAX_SAMPLES=%d]", fn, k, TG_NET_MAX_SAMPLES);
-  if (B == 0) return TG_OK;
-  if (!ee || (!rows && !uniforms)) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee, or null rows without uniforms", fn);
-  if (!aligned(ee, 4) || !aligned(rows, 8) || !aligned(uniforms, 4) || !aligned(probs, 4) || !aligned(q, 4))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, rows, uniforms, probs or q not aligned to their elements", fn);
-  tg::net::DecArgs a = dec_args(cfg, w, ee, B, k, 0);
-  a.rows = rows;
-  a.seed_lo = static_cast<uint32_t>(seed);
-  a.seed_hi = static_cast<uint32_t>(seed >> 32);
-  a.call_lo = static_cast<uint32_t>(call);
-  a.uniforms = uniforms;
-  a.tokens = tokens_i8;
-  a.probs = probs;
-  a.q = q;
-  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+  return sample_entry("tg_net_sample", cfg, w, ee, rows, B, k, seed, call, uniforms, tokens_i8, probs, q, nullptr, 0,
+                      stream);
+}
+
+int tg_net_sample_masked(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B, int k,
+                         uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
+                         const uint8_t* flags, int need, tg_stream_t stream) {
+  return sample_entry("tg_net_sample_masked", cfg, w, ee, rows, B, k, seed, call, uniforms, tokens_i8, probs, q, flags,
+                      need, stream);
 }
 
 // the forward of PolicyHead.fwd_train, model.py:219-232, and ValueHead on its zz[:, 0] (AlphaTensor.fwd_train :335-338)

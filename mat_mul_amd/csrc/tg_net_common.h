@@ -13,6 +13,11 @@ namespace net {
 
 constexpr int NT = 256;  // threads per workgroup (every network kernel)
 
+// the row mask of the inference kernels: row g takes part when there is no mask or its flags byte holds every `need` bit
+__device__ inline bool active(const uint8_t* flags, uint8_t need, int64_t g) {
+  return !flags || (flags[g] & need) == need;
+}
+
 // ---- blob layout (the header's) ---------------------------------------------------------------------------------------
 // one MHA's tensors; PT = const float* for the weights, float* for a gradient slab of the same layout
 template <class PT>

@@ -154,16 +154,20 @@ class FusedAlphaTensor:
         return cls.from_state_dict(model.state_dict(), model.n_samples, device)
 
     # ---- forward pieces -------------------------------------------------------------------------------------------
-    def torso(self, xx: torch.Tensor, ss: torch.Tensor) -> torch.Tensor:
+    def torso(self, xx: torch.Tensor, ss: torch.Tensor, out: Optional[torch.Tensor] = None,
+              flags: Optional[torch.Tensor] = None, need: int = 0) -> torch.Tensor:
         """Torso.forward: xx (B,T,S,S,S) float32 or int8, ss float32 (B,dim_s) -> ee float32 (B,3S^2,c).  One launch at
-        every supported S (by slices at S = 16)."""
-        return ops.net_torso(self.c, self.w, xx, ss.to(torch.float32))
+        every supported S (by slices at S = 16).  ``flags`` uint8 (B,) / ``need``: only the rows with
+        ``(flags & need) == need`` are computed; the others of ``out`` are left as they are (zeros without ``out``)."""
+        return ops.net_torso(self.c, self.w, xx, ss.to(torch.float32), out=out, flags=flags, need=need)
 
     def sample(self, ee: torch.Tensor, rows: Optional[torch.Tensor] = None, seed: int = 0, call: Optional[int] = None,
-               uniforms: Optional[torch.Tensor] = None, k: Optional[int] = None):
+               uniforms: Optional[torch.Tensor] = None, k: Optional[int] = None, tokens: Optional[torch.Tensor] = None,
+               probs: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+               flags: Optional[torch.Tensor] = None, need: int = 0):
         """The policy and value heads of fwd_infer on ee: tokens int8 (B,k,n_steps), pp float32 (B,k), qq float32 (B,).
         ``rows`` (default 0..B-1) key the random stream; ``call`` defaults to the instance's counter, which every call
-        advances."""
+        advances.  ``tokens`` / ``probs`` / ``q`` are output buffers; ``flags`` / ``need`` as in ``torso``."""
         B = ee.shape[0]
         if rows is None:
             rows = torch.arange(B, device=self.device, dtype=torch.int64)
@@ -171,7 +175,8 @@ class FusedAlphaTensor:
             call = self.calls
         self.calls += 1
         return ops.net_sample(self.c, self.w, ee.contiguous(), rows.to(self.device, torch.int64).contiguous(),
-                              k or self.n_samples, seed, call, uniforms=uniforms)
+                              k or self.n_samples, seed, call, uniforms=uniforms, tokens=tokens, probs=probs, q=q,
+                              flags=flags, need=need)
 
     @torch.no_grad()
     def fwd_infer(self, xx: torch.Tensor, ss: torch.Tensor, seed: int = 0, call: Optional[int] = None,
@@ -188,11 +193,33 @@ class FusedAlphaTensor:
         oo, zz0, q = ops.net_logits(self.c, self.w, self.torso(xx, ss), g_action.to(self.device))
         return (oo, zz0, q) if with_q else (oo, zz0)
 
-    def policy(self, seed: int = 0):
+    def policy(self, seed: int = 0, masked: bool = False):
         """A ``search.Policy``: candidates (tokens int8 (b,k,3S), None, q (b,)) drawn with the random stream keyed by the
         ``games`` argument.  The policy keeps its own call counter, from 0, and advances it on every call, so a retried
-        game draws new candidates and two policies of the same seed replay the same games."""
+        game draws new candidates and two policies of the same seed replay the same games.
+
+        ``masked=True`` gives a policy with ``takes_flags = True`` instead, which the search driver calls on all B rows
+        as ``policy(frames, scalars, games, flags=..., need=..., out=(tokens, q))``: only the rows whose flags hold the
+        ``need`` bits are evaluated, their tokens and q written into ``out`` (the other rows of ``out`` keep what they
+        held).  Same stream and counter rule, so both kinds of policy play the same games."""
         calls = [0]
+        if masked:
+            ee = [None]
+
+            @torch.no_grad()
+            def masked_policy(frames, scalars, games, flags, need, out):
+                B = frames.shape[0]
+                if ee[0] is None or ee[0].shape[0] != B:
+                    S = self.config["S"]
+                    ee[0] = torch.zeros((B, 3 * S * S, self.config["c"]), dtype=torch.float32, device=self.device)
+                tokens, q = out
+                self.torso(frames, scalars, out=ee[0], flags=flags, need=need)
+                self.sample(ee[0], games, seed, call=calls[0], tokens=tokens, q=q, flags=flags, need=need)
+                calls[0] += 1
+                return tokens, None, q
+
+            masked_policy.takes_flags = True
+            return masked_policy
 
         @torch.no_grad()
         def policy(frames, scalars, games):

@@ -834,9 +834,19 @@ def _net_blob(cfg, w: torch.Tensor) -> torch.device:
     return w.device
 
 
-def net_torso(cfg, w, frames, scalars, out=None) -> torch.Tensor:
+def _net_mask(flags, need: int, B: int, dev, name: str) -> Optional[torch.Tensor]:
+    """The row mask of net_torso / net_sample: flags uint8 (B,) with ``need`` in 1 .. 255, or None."""
+    if flags is None:
+        return None
+    if not 1 <= int(need) <= 255:
+        raise TensorGameError(name, -1, f"need={need} with flags given: the bits a row's flags must hold, 1 .. 255")
+    return _flag(flags, (B,), torch.uint8, dev, "flags")
+
+
+def net_torso(cfg, w, frames, scalars, out=None, flags=None, need: int = 0) -> torch.Tensor:
     """Torso.forward (tg_net_torso): frames (B,T,S,S,S) float32 or int8, scalars float32 (B,dim_s) -> ee float32
-    (B,3S^2,c)."""
+    (B,3S^2,c).  With ``flags`` uint8 (B,) only the rows with ``(flags & need) == need`` are computed
+    (tg_net_torso_masked): a given ``out`` keeps its other rows, an allocated one holds zeros there."""
     dev = _net_blob(cfg, w)
     _need_gpu(frames, "frames")
     B = frames.shape[0] if frames.dim() == 5 else -1
@@ -847,36 +857,50 @@ def net_torso(cfg, w, frames, scalars, out=None) -> torch.Tensor:
     frames = frames.contiguous()
     scalars = _flag(scalars.contiguous(), (B, cfg.dim_s), torch.float32, dev, "scalars")
     shape = (B, 3 * cfg.S * cfg.S, cfg.c)
+    flags = _net_mask(flags, need, B, dev, "net_torso")
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        out = (torch.empty if flags is None else torch.zeros)(shape, dtype=torch.float32, device=dev)
     out = _flag(out, shape, torch.float32, dev, "out")
+    i8 = 1 if frames.dtype == torch.int8 else 0
     with torch.cuda.device(dev):
-        call("tg_net_torso", C.byref(cfg), _ptr(w), _ptr(frames), 1 if frames.dtype == torch.int8 else 0,
-             _ptr(scalars), _ptr(out), B, _stream(dev))
+        if flags is None:
+            call("tg_net_torso", C.byref(cfg), _ptr(w), _ptr(frames), i8, _ptr(scalars), _ptr(out), B, _stream(dev))
+        else:
+            call("tg_net_torso_masked", C.byref(cfg), _ptr(w), _ptr(frames), i8, _ptr(scalars), _ptr(out), B, _ptr(flags),
+                 int(need), _stream(dev))
     return out
 
 
-def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None, tokens=None, probs=None, q=None):
+def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None, tokens=None, probs=None, q=None,
+               flags=None, need: int = 0):
     """PolicyHead.fwd_infer + the risk-managed value (tg_net_sample) for ee float32 (B,3S^2,c): returns tokens int8
     (B,k,n_steps), probs float32 (B,k), q float32 (B,).  ``rows`` int64 (B,) key the random stream with ``seed`` and
-    ``call_idx``; ``uniforms`` float32 (B,k,n_steps) replaces the stream when given."""
+    ``call_idx``; ``uniforms`` float32 (B,k,n_steps) replaces the stream when given.  With ``flags`` uint8 (B,)
+    only the rows with ``(flags & need) == need`` are decoded (tg_net_sample_masked): given outputs keep their other
+    rows, allocated ones hold zeros there."""
     dev = _net_blob(cfg, w)
     B = ee.shape[0]
+    flags = _net_mask(flags, need, B, dev, "net_sample")
+    new = torch.empty if flags is None else torch.zeros
     ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
     rows = _flag(rows, (B,), torch.int64, dev, "rows")
     uniforms = _flag(uniforms, (B, k, cfg.n_steps), torch.float32, dev, "uniforms")
     if tokens is None:
-        tokens = torch.empty((B, k, cfg.n_steps), dtype=torch.int8, device=dev)
+        tokens = new((B, k, cfg.n_steps), dtype=torch.int8, device=dev)
     if probs is None:
-        probs = torch.empty((B, k), dtype=torch.float32, device=dev)
+        probs = new((B, k), dtype=torch.float32, device=dev)
     if q is None:
-        q = torch.empty((B,), dtype=torch.float32, device=dev)
+        q = new((B,), dtype=torch.float32, device=dev)
     tokens = _flag(tokens, (B, k, cfg.n_steps), torch.int8, dev, "tokens")
     probs = _flag(probs, (B, k), torch.float32, dev, "probs")
     q = _flag(q, (B,), torch.float32, dev, "q")
+    args = (C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), int(seed) & (2 ** 64 - 1),
+            int(call_idx) & (2 ** 64 - 1), _ptr(uniforms), _ptr(tokens), _ptr(probs), _ptr(q))
     with torch.cuda.device(dev):
-        call("tg_net_sample", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), int(seed) & (2 ** 64 - 1),
-             int(call_idx) & (2 ** 64 - 1), _ptr(uniforms), _ptr(tokens), _ptr(probs), _ptr(q), _stream(dev))
+        if flags is None:
+            call("tg_net_sample", *args, _stream(dev))
+        else:
+            call("tg_net_sample_masked", *args, _ptr(flags), int(need), _stream(dev))
     return tokens, probs, q
 
 

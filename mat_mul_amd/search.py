@@ -14,6 +14,13 @@ deliberate deviations (a terminal leaf inside the horizon is worth 0 instead of 
 q float32 (b,))`` for the rows ``games`` (int64 game indices) of the model input.  The first call of a simulation
 covers all B games (rows of games that need no expansion are ignored), so that no host sync is needed to find the
 games that do; games whose candidates were all dropped are asked again, alone, with ``forest.attempt`` counting.
+
+A policy with the attribute ``takes_flags = True`` (``FusedAlphaTensor.policy(seed, masked=True)``) is called as
+``policy(frames, scalars, games, flags=forest.flags, need=bits, out=(tokens, q))`` instead, always on all B rows with
+``games = arange(B)``: it evaluates the rows whose flags hold every bit of ``need`` (EXPAND | PENDING on the first call
+of a simulation, RETRY on a retry), writes their rows of ``out`` (int8 (B,k,3S), float32 (B,)) in place and returns
+``(tokens, None, q)`` with those two buffers.  The mask is applied on the device, so the rows nobody reads (finished
+games, games out of simulations, terminal leaves, leaves past the horizon) cost nothing.
 """
 from __future__ import annotations
 
@@ -150,11 +157,22 @@ class SearchForest:
         tokens_all = torch.zeros((B, k, 3 * S), dtype=torch.int8, device=self.device)
         q_all = torch.zeros((B,), dtype=torch.float32, device=self.device)
         prior_all = torch.zeros((B, k), dtype=torch.float32, device=self.device) if self.child_prior is not None else None
+        masked = bool(getattr(policy, "takes_flags", False))
+
+        def ask(need):  # the masked policy writes the rows it evaluates straight into tokens_all / q_all
+            tokens, _, q = policy(frames, scalars, games, flags=self.flags, need=need, out=(tokens_all, q_all))
+            if tokens is not tokens_all or q is not q_all:
+                raise TensorGameError("policy", -1, "a policy with takes_flags returns the tokens and q buffers of `out`")
+
         for _ in range(self.max_actions):
             for _ in range(n_sim):
                 frames, scalars = self.select(dtype)
-                tokens, prior, q = policy(frames, scalars, games)
-                self.commit(*self._full(tokens, prior, q, games, tokens_all, prior_all, q_all))
+                if masked:
+                    ask(EXPAND | PENDING)
+                    self.commit(tokens_all, q_all, prior_all)
+                else:
+                    tokens, prior, q = policy(frames, scalars, games)
+                    self.commit(*self._full(tokens, prior, q, games, tokens_all, prior_all, q_all))
                 for attempt in range(max_retries + 1):
                     retry = (self.flags & RETRY) != 0
                     n_retry, n_active = torch.stack([retry.sum(), ((self.sims_left > 0) & (self.done == 0)).sum()]).tolist()
@@ -163,6 +181,10 @@ class SearchForest:
                     if attempt == max_retries:
                         raise TensorGameError("SearchForest.play", -1, f"{n_retry} games found no surviving candidate "
                                               f"after {max_retries} retries")
+                    if masked:
+                        ask(RETRY)
+                        self.commit(tokens_all, q_all, prior_all, mask=retry.to(torch.uint8))
+                        continue
                     sel = retry.nonzero()[:, 0]
                     tokens, prior, q = policy(frames[sel], scalars[sel], sel)
                     self.commit(*self._full(tokens, prior, q, sel, tokens_all, prior_all, q_all),

@@ -1,7 +1,7 @@
 """The fused network (include/tensor_game_net.h) against the float32 restatement run eagerly, at the training app's
 configuration (tests/net_ref.CONFIGS["a"]: S 4, T 2, c 8, W 32, 8 + 2 layers, n_steps 12), k = 8.
 
-    python tools/net_bench.py OUT_DIR [--config a] [--reps 20] [--warmup 3] [--fused-only] [--kernel-stats CSV]
+    python tools/net_bench.py OUT_DIR [--config a] [--reps 20] [--warmup 3] [--fused-only] [--masked] [--kernel-stats CSV]
 
 One process, one GPU.  Per B in {256, 1024, 4096}: FusedAlphaTensor.fwd_infer and the eager Ref.fwd_infer (the
 reference's op structure: the whole prefix rerun at every token step, torch's Categorical) alternate call by call;
@@ -14,6 +14,9 @@ tests/net_s16_ref.CONFIGS (a16, b16: S = 16); the file is then OUT_DIR/r08_net_<
 figure is skipped; at S = 16 the sizes are B = 16, 256 and 1024 and the self-play figure is at B = 256, n_sim = 4.
 --torso-only times tg_net_torso alone at B = 16 and 256 and writes OUT_DIR/r08_torso_<config>[_slices].json; with
 TG_LIB_VARIANT=ab, TG_NET_TORSO_SLICES=1 forces net_torso_slice_kernel at any size (the A/B library's switch).
+--masked times torso + sample through the row mask (tg_net_torso_masked, tg_net_sample_masked) with a share f = 1, 0.75,
+0.5, 0.25 and 1/B of the rows active (seeded random flags) next to the plain call, the calls alternating in one process,
+at B = 256 and 4096 (B = 16 and 256 at S = 16); it merges its result into OUT_DIR/r13_masked.json under net_<config>.
 """
 from __future__ import annotations
 
@@ -86,6 +89,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--torso-only", action="store_true")
+    ap.add_argument("--masked", action="store_true")
     ap.add_argument("--kernel-stats")
     ap.add_argument("--config", default="a", choices=sorted(CONFIGS))
     args = ap.parse_args()
@@ -126,6 +130,50 @@ def main():
         print(f"wrote {path}")
         return
     wide16 = m["S"] == 16
+    if args.masked:
+        res = {"config": m, "k": k, "need": 129, "sizes": [], "command": " ".join(sys.argv)}
+        for B in ((16, 256) if wide16 else (256, 4096)):
+            xx, ss = make_inputs(cfg, B, B)
+            xx, ss = torch.from_numpy(xx).to(DEV).float(), torch.from_numpy(ss).to(DEV)
+            rows = torch.arange(B, device=DEV, dtype=torch.int64)
+            ee = torch.zeros((B, 3 * m["S"] ** 2, m["c"]), dtype=torch.float32, device=DEV)
+            tokens = torch.zeros((B, k, m["n_steps"]), dtype=torch.int8, device=DEV)
+            probs, q = torch.zeros((B, k), device=DEV), torch.zeros((B,), device=DEV)
+            rng = np.random.default_rng(B)
+            variants = {}
+            for name, n_act in (("1", B), ("0.75", 3 * B // 4), ("0.5", B // 2), ("0.25", B // 4), ("1/B", 1)):
+                fl = np.full(B, 128, np.uint8)  # PENDING alone: inactive under need = EXPAND | PENDING
+                fl[rng.permutation(B)[:n_act]] = 129
+                variants[name] = (n_act, torch.from_numpy(fl).to(DEV))
+
+            def call(fl):
+                net.torso(xx, ss, out=ee, flags=fl, need=129)
+                net.sample(ee, rows, seed=1, tokens=tokens, probs=probs, q=q, flags=fl, need=129)
+
+            calls = {"plain": lambda: call(None), **{f: (lambda fl=fl: call(fl)) for f, (_, fl) in variants.items()}}
+            with torch.no_grad():
+                for _ in range(args.warmup):
+                    for fn in calls.values():
+                        fn()
+                torch.cuda.synchronize()
+                ts = {name: [] for name in calls}
+                for _ in range(args.reps):
+                    for name, fn in calls.items():
+                        ts[name].append(timed(fn))
+            row = {"B": B, "plain": stats(ts["plain"]), "masked": {}}
+            for f, (n_act, _) in variants.items():
+                st = stats(ts[f])
+                row["masked"][f] = {**st, "active_rows": n_act, "active_share": n_act / B,
+                                    "time_over_plain": st["median_us"] / row["plain"]["median_us"]}
+            res["sizes"].append(row)
+            print(json.dumps(row), flush=True)
+        res["device"] = torch.cuda.get_device_name(0)
+        path = out / "r13_masked.json"
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole[f"net_{args.config}"] = res
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+        print(f"wrote {path}")
+        return
     for B in ((16, 256, 1024) if wide16 else (256, 1024, 4096)):
         xx, ss = make_inputs(cfg, B, B)
         xx = torch.from_numpy(xx).to(DEV).float()

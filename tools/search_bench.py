@@ -11,6 +11,15 @@ bytes one simulation moves per game by construction (index probes, node rows, fr
 latency-bound (dependent probes per descent level), so no bandwidth figure is claimed.  ``--reference DIR`` times the
 reference's extend_tree (act.py:115-216) on the CPU, one game, with the host form of the same stand-in, and records its
 simulations per second next to the device's.
+
+    python tools/search_bench.py --masked [--out profiles/r13_masked.json]              (GPU)
+
+times whole ``search.actor_prediction`` runs with the fused network (FusedAlphaTensor of tests/net_ref's configurations
+a and a16, rank-2 start states), ``net.policy(seed)`` against ``net.policy(seed, masked=True)`` alternating, at S = 4,
+B = 4096, k = 8, n_sim = 16, max_actions = 8 and at S = 16, B = 256, n_sim = 4, max_actions = 2.  Besides the wall time
+it reports the active share: over the policy calls of the masked run, the rows whose flags hold the needed bits divided
+by B x calls (read from ``forest.flags`` here only; that read is inside the timed run, the same for every repetition).
+The result is merged into the file under ``self_play``.
 """
 import argparse
 import json
@@ -103,6 +112,75 @@ def bench_device():
     return dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, shapes=out)
 
 
+MASKED_RUNS = [("a", 4096, 16, 8), ("a16", 256, 4, 2)]  # configuration, B, n_sim, max_actions
+
+
+def bench_masked(reps=3):
+    import torch
+
+    from mat_mul_amd import FusedAlphaTensor, SyntheticDemos, search
+    from net_ref import CONFIGS, make_weights
+    from net_s16_ref import CONFIGS as CONFIGS_S16
+
+    dev = "cuda:0"
+    out = {}
+    for name, B, n_sim, max_actions in MASKED_RUNS:
+        cfg = {**CONFIGS, **CONFIGS_S16}[name]
+        S, T, k = cfg["dim_3d"], cfg["dim_t"], cfg["n_samples"]
+        sd = make_weights(cfg, 11)
+        start = torch.zeros((B, T, S, S, S), dtype=torch.int8, device=dev)
+        start[:, 0] = SyntheticDemos(2, B, 1, S, device=dev, seed=3).target_tensor.reshape(B, S, S, S)
+        count = {}
+
+        def run(masked):
+            net = FusedAlphaTensor.from_state_dict(sd, k, device=dev)
+            forest = search.SearchForest(B, S, T, k=k, max_actions=max_actions, n_sim=n_sim, device=dev)
+            inner = net.policy(seed=3, masked=masked)
+            count.update(calls=0, rows=0, first=0)
+
+            def plain(frames, scalars, games):
+                count["calls"] += 1
+                count["first"] += int(games.shape[0] == B)
+                return inner(frames, scalars, games)
+
+            def flagged(frames, scalars, games, flags, need, out):
+                count["calls"] += 1
+                count["first"] += int(need != search.RETRY)
+                count["rows"] += int(((flags & need) == need).sum())
+                return inner(frames, scalars, games, flags=flags, need=need, out=out)
+
+            flagged.takes_flags = True
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = search.actor_prediction(flagged if masked else plain, start, max_actions, n_sim=n_sim, n_bar=100,
+                                          n_logits=3, k=k, forest=forest)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, [t.cpu() for t in res], dict(count)
+
+        run(False), run(True)  # warm-up
+        wall = {False: [], True: []}
+        for _ in range(reps):
+            for masked in (False, True):
+                dt, res, c = run(masked)
+                wall[masked].append(dt)
+                if masked:
+                    counted, got = c, res
+                else:
+                    sims, want = c["first"], res
+        assert all(torch.equal(a, b) for a, b in zip(got, want)), "the two policies played different games"
+        med = {m: float(np.median(v)) for m, v in wall.items()}
+        out[f"{name}_B{B}"] = dict(
+            config=name, S=S, B=B, T=T, k=k, n_sim=n_sim, max_actions=max_actions, reps=reps, simulations=sims,
+            policy_calls=counted["calls"], active_share=round(counted["rows"] / (B * counted["calls"]), 4),
+            mean_length=round(float(want[3].float().mean()), 3),
+            plain_seconds=[round(x, 4) for x in wall[False]], masked_seconds=[round(x, 4) for x in wall[True]],
+            plain_us_per_simulation=round(med[False] * 1e6 / sims, 1),
+            masked_us_per_simulation=round(med[True] * 1e6 / sims, 1),
+            masked_over_plain=round(med[True] / med[False], 4))
+        print(name, out[f"{name}_B{B}"], flush=True)
+    return dict(device=torch.cuda.get_device_name(0), command=" ".join(sys.argv), runs=out)
+
+
 def bench_reference(ref_dir):
     """The reference's extend_tree on the CPU, one game per shape, with the host form of the stand-in."""
     import torch
@@ -146,12 +224,15 @@ def bench_reference(ref_dir):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r06_search.json"))
+    ap.add_argument("--out", default=None, help="default profiles/r06_search.json (profiles/r13_masked.json with --masked)")
+    ap.add_argument("--masked", action="store_true", help="self-play with the fused network, plain against masked policy")
     ap.add_argument("--reference", default=None, help="directory of the reference (CPU run; adds its rate)")
     args = ap.parse_args()
-    path = Path(args.out)
+    path = Path(args.out or ROOT / "profiles" / ("r13_masked.json" if args.masked else "r06_search.json"))
     res = json.loads(path.read_text()) if path.exists() else {}
-    if args.reference:
+    if args.masked:
+        res["self_play"] = bench_masked()
+    elif args.reference:
         res["reference_extend_tree_cpu"] = bench_reference(args.reference)
         for name, r in res["reference_extend_tree_cpu"].items():
             dev = res.get("device_search", {}).get("shapes", {}).get(name)
