@@ -38,6 +38,8 @@
  * Per-game status word (uint32): bit 0 = the node pool or the index was full (that simulation's expansion AND backup
  * were dropped), bit 1 = a descent exceeded max_depth, bit 2 = a token >= n_logits (or < 0) met by tg_search_policy.
  * overflow (uint8 per game) is SET when a child head left int8 (two's-complement wrap, as tensor_game.h), sticky.
+ * The children that count are all k candidate children tg_search_commit forms for an EXPAND leaf, on every attempt,
+ * including the candidates it then drops as null or as already a node; only tg_search_reset clears the flag.
  */
 #ifndef TENSOR_GAME_SEARCH_H_
 #define TENSOR_GAME_SEARCH_H_

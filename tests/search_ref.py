@@ -5,6 +5,7 @@ descent is cut at max_depth) and int8 wrap of child heads.  The improved policy 
 reference forms it (float32 log / pow on the host).
 
 ``policy_fn(head int8 (S,S,S), frames int8 (T,S,S,S), scalar int, attempt int, key int) -> (tokens (k,3S), q float32)``.
+``play`` also logs every policy call and whether a candidate child head left int8 (the header's ``overflow``).
 """
 import numpy as np
 import torch
@@ -59,13 +60,17 @@ def improved_policy(N, tokens, n_bar, n_logits):
 
 def play(policy_fn, start, max_actions, n_sim, n_bar, n_logits, horizon=5, max_depth=64, shift=1, max_retries=256):
     """One game.  Returns a dict: states (L,T,S,S,S) int8, policy (L,3S,n_logits) f32, rewards (L,) int64, length,
-    root_N / root_Q (lists of f32 arrays), choice (L,) and status (bit 1: a descent over max_depth)."""
+    root_N / root_Q (lists of f32 arrays), choice (L,) and status (bit 1: a descent over max_depth); further
+    ``calls``, one ``(frames int8 (T,S,S,S), scalar, attempt, key)`` per policy call in order, ``overflow`` (a candidate
+    child head of some expansion attempt left int8 before the wrap -- over all k candidates, kept or dropped) and
+    ``n_nodes``, the size of the tree at the end."""
     frames = np.array(start, np.int8)
     nodes = {}
     root, root_key = frames, head_key(frames[0])
     states, roots, choice = [], [], []
     status = 0
     move = 0
+    calls, overflow = [], False
     while move < max_actions:
         states.append(root)
         sims = n_sim
@@ -93,7 +98,10 @@ def play(policy_fn, start, max_actions, n_sim, n_bar, n_logits, horizon=5, max_d
                     for attempt in range(max_retries + 1):
                         tokens, q = policy_fn(head, fr, move + depth, attempt, key)
                         tokens = np.asarray(tokens)
-                        kids = (head[None].astype(np.int64) - O.action_to_tensor(tokens, shift)).astype(np.int8)
+                        calls.append((fr.copy(), move + depth, attempt, key))
+                        exact = head[None].astype(np.int64) - O.action_to_tensor(tokens, shift)
+                        overflow |= bool(((exact < -128) | (exact > 127)).any())
+                        kids = exact.astype(np.int8)
                         changed = (kids != head[None]).reshape(len(tokens), -1).any(axis=1)
                         kid_keys = O.state_hash(kids)
                         keep = [i for i in range(len(tokens)) if changed[i] and int(kid_keys[i]) not in nodes]
@@ -124,7 +132,7 @@ def play(policy_fn, start, max_actions, n_sim, n_bar, n_logits, horizon=5, max_d
     rewards = np.cumsum(np.array([-1] * (L - 1) + [-1 - rank], np.int64))
     return dict(states=np.stack(states), policy=pol, rewards=rewards, length=L, choice=np.array(choice, np.int32),
                 root_N=[nodes[k].N.copy() for k in roots], root_Q=[nodes[k].Q.copy() for k in roots], status=status,
-                final=root)
+                final=root, calls=calls, overflow=overflow, n_nodes=len(nodes))
 
 
 # ---- the device stand-in of mat_mul_amd.search.keyed_policy, on the host -----------------------------------------

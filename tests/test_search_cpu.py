@@ -127,6 +127,13 @@ def test_restatement_reproduces_reference_games(golden, case):
         r = R.play(fn, g[f"{case}_start"][gi], max_actions, n_sim, n_bar, n_logits, horizon=horizon)
         L = r["length"]
         assert L == int(g[f"{case}_lengths"][gi])
+        rows = np.flatnonzero(g[f"{case}_call_game"] == gi)                 # the calls the reference made in this game
+        assert len(r["calls"]) == len(rows), (case, gi)
+        for (frames, scalar, attempt, key), row in zip(r["calls"], rows):
+            assert frames.shape == (T, S, S, S) and key == R.head_key(frames[0])
+            assert np.array_equal(frames[0], g[f"{case}_call_head"][row]), (case, gi, row)
+            assert float(scalar) == float(g[f"{case}_call_scalar"][row]) and attempt == int(g[f"{case}_call_attempt"][row])
+        assert r["overflow"] is False
         assert np.array_equal(r["states"], g[f"{case}_states"][gi][:L])
         assert not g[f"{case}_states"][gi][L:].any()
         assert np.array_equal(r["policy"].view(np.int32), g[f"{case}_policy"][gi][:L].view(np.int32)), (case, gi)
@@ -137,6 +144,20 @@ def test_restatement_reproduces_reference_games(golden, case):
             assert len(r["root_N"][m]) == nc
             assert np.array_equal(r["root_N"][m].view(np.int32), g[f"{case}_root_n"][gi][m][:nc].view(np.int32))
             assert np.array_equal(r["root_Q"][m].view(np.int32), g[f"{case}_root_q"][gi][m][:nc].view(np.int32)), (case, gi, m)
+
+
+def test_restatement_flags_a_child_that_leaves_int8():
+    """A head of 127 with a product of -1 is 128 before the wrap: ``overflow`` is set (and the stored head wraps to
+    -128); the same action on a head of 126 sets nothing."""
+    S = 4
+    minus = np.array([2, 1, 1, 1, 2, 1, 1, 1, 0, 1, 1, 1], np.int8)       # u = e0, v = e0, w = -e0: product -1 at [0,0,0]
+    null = np.ones(12, np.int8)
+    for top, want in ((127, True), (126, False)):
+        start = np.zeros((1, S, S, S), np.int8)
+        start[0, 0, 0, 0], start[0, 1, 1, 1] = top, 1
+        r = R.play(lambda *a: (np.stack([null, minus]), np.float32(0.25)), start, 1, 1, 100, 3)
+        assert r["overflow"] is want and r["length"] == 1 and len(r["calls"]) == 1
+        assert int(r["final"][0, 0, 0, 0]) == (-128 if want else 127)
 
 
 def test_fixture_covers_the_branches(golden):
