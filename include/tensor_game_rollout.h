@@ -31,9 +31,9 @@ extern "C" {
  *   scalars   float32 (B,dim_s) += 1 (:268), or NULL (then dim_s is ignored).
  *   nnz       int32 (B): non-zero entries of the new head (rank_ubs, :266).
  *   per group (G = B / n entries each, int32, updated from this step's nnz; one writer per record, no atomics; rows
- *   keep being stepped after their group is solved, as in the reference).  The caller initialises them before step 0:
- *   best_nnz to any upper bound (S^3: the reference's lowest_rank starts there, training.py:329), hits to 0,
- *   solved_step and solved_sample to -1.
+ *   keep being stepped after their group is solved, as in the reference; tg_rollout_advance_masked stops them).  The
+ *   caller initialises them before step 0: best_nnz to any upper bound (S^3: the reference's lowest_rank starts there,
+ *   training.py:329), hits to 0, solved_step and solved_sample to -1.
  *     best_nnz       running minimum of nnz over the steps so far and the n samples (:343-345 per group);
  *     hits           number of steps so far at which the group's minimum was 0; summed over the groups this is the
  *                    reference's num_solutions_found (:346);
@@ -54,5 +54,8 @@ int tg_rollout_check(int64_t B, int n, int S, int T, int dim_s, int step, int ma
 #ifdef __cplusplus
 }
 #endif
+
+/* tg_rollout_advance_masked: the same step for the groups that are not solved yet (solved groups are left alone) */
+#include "tensor_game_rollout_masked.h"
 
 #endif /* TENSOR_GAME_ROLLOUT_H_ */

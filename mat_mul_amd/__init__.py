@@ -15,7 +15,8 @@ import importlib
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
-           "FusedAlphaTensor", "net", "FusedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult"]
+           "FusedAlphaTensor", "net", "FusedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult",
+           "solve_states"]
 
 _SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout"}
 _ATTRS = {
@@ -31,6 +32,7 @@ _ATTRS = {
     "FusedTrainer": "train",
     "sample_rollouts": "rollout",
     "RolloutResult": "rollout",
+    "solve_states": "rollout",
 }
 
 

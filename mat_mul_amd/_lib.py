@@ -131,6 +131,11 @@ ROLLOUT_SIGNATURES = {
     "tg_rollout_advance": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
     "tg_rollout_check": [_i64, _i, _i, _i, _i, _i, _i, _i],
 }
+# name -> argtypes; every symbol include/tensor_game_rollout_masked.h declares
+ROLLOUT_MASKED_SIGNATURES = {
+    "tg_rollout_advance_masked": ROLLOUT_SIGNATURES["tg_rollout_advance"][:10] + [_p] +
+                                 ROLLOUT_SIGNATURES["tg_rollout_advance"][10:],
+}
 TG_NET_TRAIN_PARTIALS = 256
 TG_TRAIN_STATUS_BAD_TOKEN = 1
 
@@ -180,7 +185,8 @@ def _load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
-                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES}.items():
+                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES,
+                           **ROLLOUT_MASKED_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -10,9 +10,16 @@
 // next to each other and a workgroup owns whole groups (several small ones, so that a workgroup has about kRollItems
 // items): the per-row counts meet in LDS (integer LDS adds: exact, order-free) and one thread per group updates the
 // group's records -- one writer per record, no global atomics.
+//
+// Row mask (tg_rollout_advance_masked, M = true): a group is ACTIVE in a launch iff its solved_step is negative when the
+// launch starts.  Every wave reads the solved_step of the workgroup's groups itself (they are written only behind the
+// second barrier, which no wave passes before all have read), so the decision to return -- no group active -- is uniform
+// without a barrier.  Of an inactive group nothing else is read and nothing is written; the activity of the groups lives
+// in LDS from the first barrier on, because the records change while the rows are written back.  M = false is the plain
+// entry: the same code with every test of the mask compiled out.
 #include <hip/hip_runtime.h>
 
-#include "../../include/tensor_game_rollout.h"
+#include "../../include/tensor_game_rollout.h"  // and, through it, tensor_game_rollout_masked.h
 #include "tg_host.h"
 
 namespace tg {
@@ -29,6 +36,7 @@ struct RolloutArgs {
   uint8_t* overflow;
   int32_t *best_nnz, *hits, *solved_step, *solved_sample;
   int8_t* actions;
+  uint8_t* active;  // M only, may be null: 1 for the rows of a group still unsolved after this step, else 0
   int64_t G;        // groups
   int n, S, T, dim_s, step, max_actions, shift;
   int gpw;          // groups per workgroup
@@ -66,23 +74,37 @@ __device__ __forceinline__ void roll_store(int8_t* p, int nb, const uint32_t (&q
   }
 }
 
-template <int W>
+template <int W, bool M>
 __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutArgs a) {
   __shared__ __attribute__((aligned(16))) int8_t s_tok[kRollTokBytes];
   __shared__ int s_nnz[kRollMaxRows];
   __shared__ int s_ovf[kRollMaxRows];
+  __shared__ uint8_t s_act[M ? kRollMaxRows : 1];  // per group of the workgroup (at most one group per row)
   const int tid = threadIdx.x;
   const int S = a.S, S2 = S * S, N = S2 * S, A3 = 3 * S, T = a.T, n = a.n;
   const int64_t g0 = static_cast<int64_t>(blockIdx.x) * a.gpw;
   const int ng = static_cast<int>(a.G - g0 < a.gpw ? a.G - g0 : a.gpw);  // >= 1: the grid is ceil(G / gpw)
   const int rows = ng * n;
   const int64_t b0 = g0 * n;
+  bool mixed = false;  // some groups of this workgroup may be inactive: a workgroup of ONE group that goes on is active
+  if constexpr (M) {
+    bool any = false;
+    for (int base = 0; base < ng; base += 64) {  // every wave over all the groups: the same answer in each
+      const int lg = base + (tid & 63);
+      const bool act = lg < ng && a.solved_step[g0 + lg] < 0;
+      if (tid < 64 && lg < ng) s_act[lg] = act;
+      any |= act;
+    }
+    if (!__any(any)) return;
+    mixed = ng > 1;
+  }
 
   // ---- the rows' tokens into LDS (and into the record of played actions), scalars + 1, the counters cleared
   if (a.words) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tokens + b0 * A3);
     const int wpr = A3 / 4;
     for (int x = tid; x < rows * wpr; x += kBlock) {
+      if (M && mixed && a.solved_step[g0 + x / wpr / n] >= 0) continue;
       const uint32_t t = src[x];
       reinterpret_cast<uint32_t*>(s_tok)[x] = t;
       if (a.actions) {
@@ -93,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutAr
   } else {
     const int8_t* src = a.tokens + b0 * A3;
     for (int x = tid; x < rows * A3; x += kBlock) {
+      if (M && mixed && a.solved_step[g0 + x / A3 / n] >= 0) continue;
       const int8_t t = src[x];
       s_tok[x] = t;
       if (a.actions) {
@@ -103,7 +126,10 @@ __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutAr
   }
   if (a.scalars) {
     float* sc = a.scalars + b0 * a.dim_s;
-    for (int x = tid; x < rows * a.dim_s; x += kBlock) sc[x] += 1.0f;
+    for (int x = tid; x < rows * a.dim_s; x += kBlock) {
+      if (M && mixed && a.solved_step[g0 + x / a.dim_s / n] >= 0) continue;
+      sc[x] += 1.0f;
+    }
   }
   for (int r = tid; r < rows; r += kBlock) s_nnz[r] = 0, s_ovf[r] = 0;
   __syncthreads();
@@ -114,6 +140,7 @@ __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutAr
   const int total = rows * a.ipr;
   for (int it = tid; it < total; it += kBlock) {
     const int lr = it / a.ipr, c = it - lr * a.ipr;
+    if (M && mixed && !s_act[lr / n]) continue;
     const int nb = c < full ? W : N - full * W;
     const int e0 = c * W;
     int8_t* const row = a.frames + (b0 + lr) * static_cast<int64_t>(T) * N + e0;
@@ -158,10 +185,18 @@ __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutAr
 
   // ---- per row, then per group
   for (int r = tid; r < rows; r += kBlock) {
+    if (M && mixed && !s_act[r / n]) continue;
     a.nnz[b0 + r] = s_nnz[r];
     if (a.overflow && s_ovf[r]) a.overflow[b0 + r] = 1;
+    if (M && a.active) {  // the group's verdict again, per row: no third barrier
+      const int* const grp = s_nnz + r / n * n;
+      bool zero = false;
+      for (int s = 0; s < n; ++s) zero |= grp[s] == 0;
+      a.active[b0 + r] = zero ? 0 : 1;
+    }
   }
   for (int lg = tid; lg < ng; lg += kBlock) {
+    if (M && mixed && !s_act[lg]) continue;
     int best = s_nnz[lg * n], first = -1;
     for (int s = n - 1; s >= 0; --s) {
       const int v = s_nnz[lg * n + s];
@@ -205,11 +240,13 @@ extern "C" int tg_rollout_check(int64_t B, int n, int S, int T, int dim_s, int s
   return rollout_check("tg_rollout_check", B, n, S, T, dim_s, step, max_actions, with_actions);
 }
 
-extern "C" int tg_rollout_advance(int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz, uint8_t* overflow,
-                                  int32_t* best_nnz, int32_t* hits, int32_t* solved_step, int32_t* solved_sample,
-                                  int8_t* actions, int64_t B, int n, int S, int T, int dim_s, int step, int max_actions,
-                                  int shift, tg_stream_t stream) {
-  const char* fn = "tg_rollout_advance";
+namespace {
+
+// tg_rollout_advance (masked = false: `active` is ignored) and tg_rollout_advance_masked
+int rollout_entry(const char* fn, bool masked, int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz,
+                  uint8_t* overflow, int32_t* best_nnz, int32_t* hits, int32_t* solved_step, int32_t* solved_sample,
+                  int8_t* actions, uint8_t* active, int64_t B, int n, int S, int T, int dim_s, int step, int max_actions,
+                  int shift, tg_stream_t stream) {
   if (int rc = rollout_check(fn, B, n, S, T, dim_s, step, max_actions, actions != nullptr)) return rc;
   if (B == 0) return TG_OK;
   if (!frames) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames", fn);
@@ -225,7 +262,7 @@ extern "C" int tg_rollout_advance(int8_t* frames, const int8_t* tokens, float* s
   const bool wide = S % 4 == 0 && aligned(frames, 16);  // then N % 64 == 0: every frame of every row is 16-byte aligned
   const int W = wide ? 16 : 4;
   tg::RolloutArgs a{frames, tokens, scalars, nnz, overflow, best_nnz, hits, solved_step, solved_sample, actions,
-                    B / n, n, S, T, scalars ? dim_s : 0, step, max_actions, shift, 1, (N + W - 1) / W, 0};
+                    masked ? active : nullptr, B / n, n, S, T, scalars ? dim_s : 0, step, max_actions, shift, 1, (N + W - 1) / W, 0};
   a.words = S % 4 == 0 && aligned(tokens, 4) && (!actions || aligned(actions, 4));
   // several small groups per workgroup, within the LDS tables of the kernel
   int64_t gpw = tg::kRollItems / (static_cast<int64_t>(n) * a.ipr);
@@ -236,6 +273,30 @@ extern "C" int tg_rollout_advance(int8_t* frames, const int8_t* tokens, float* s
   const int64_t grid = (a.G + a.gpw - 1) / a.gpw;
   if (grid > 0x7fffffffll) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld: too large a grid", fn, (long long)B);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (wide) return launch(fn, tg::rollout_advance_kernel<16>, dim3(static_cast<unsigned>(grid)), dim3(tg::kBlock), 0, st, a);
-  return launch(fn, tg::rollout_advance_kernel<4>, dim3(static_cast<unsigned>(grid)), dim3(tg::kBlock), 0, st, a);
+  const dim3 dg(static_cast<unsigned>(grid)), db(tg::kBlock);
+  if (masked) {
+    if (wide) return launch(fn, tg::rollout_advance_kernel<16, true>, dg, db, 0, st, a);
+    return launch(fn, tg::rollout_advance_kernel<4, true>, dg, db, 0, st, a);
+  }
+  if (wide) return launch(fn, tg::rollout_advance_kernel<16, false>, dg, db, 0, st, a);
+  return launch(fn, tg::rollout_advance_kernel<4, false>, dg, db, 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int tg_rollout_advance(int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz, uint8_t* overflow,
+                                  int32_t* best_nnz, int32_t* hits, int32_t* solved_step, int32_t* solved_sample,
+                                  int8_t* actions, int64_t B, int n, int S, int T, int dim_s, int step, int max_actions,
+                                  int shift, tg_stream_t stream) {
+  return rollout_entry("tg_rollout_advance", false, frames, tokens, scalars, nnz, overflow, best_nnz, hits, solved_step,
+                       solved_sample, actions, nullptr, B, n, S, T, dim_s, step, max_actions, shift, stream);
+}
+
+extern "C" int tg_rollout_advance_masked(int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz,
+                                         uint8_t* overflow, int32_t* best_nnz, int32_t* hits, int32_t* solved_step,
+                                         int32_t* solved_sample, int8_t* actions, uint8_t* active, int64_t B, int n,
+                                         int S, int T, int dim_s, int step, int max_actions, int shift,
+                                         tg_stream_t stream) {
+  return rollout_entry("tg_rollout_advance_masked", true, frames, tokens, scalars, nnz, overflow, best_nnz, hits,
+                       solved_step, solved_sample, actions, active, B, n, S, T, dim_s, step, max_actions, shift, stream);
 }

@@ -229,13 +229,34 @@ class FusedAlphaTensor:
 
         return policy
 
-    def rollout_policy(self, seed: int = 0):
+    def rollout_policy(self, seed: int = 0, masked: bool = False):
         """A ``rollout.RolloutPolicy``: ONE action per row (torso on the int8 frames, then ``sample`` with k = 1), drawn
         with the random stream keyed by the global row index -- so the samples of one start state draw differently --
-        and ``call`` = the step, so two rollouts of the same seed play the same games.  Two launches, capturable."""
+        and ``call`` = the step, so two rollouts of the same seed play the same games.  Two launches, capturable.
+
+        ``masked=True`` gives a policy with ``takes_active = True`` instead, which ``sample_rollouts(stop_solved=True)``
+        calls as ``policy(frames, scalars, rows, step, active=..., out=tokens)``: only the rows whose ``active`` byte
+        is set are evaluated (``flags=active, need=1`` in both launches) and their tokens written into ``out`` int8
+        (B,3S); the other rows of ``out`` keep what they held.  Same stream rule, so an active row draws what the plain
+        policy draws for it."""
         if self.n_steps != 3 * self.config["S"]:
             raise TensorGameError("rollout_policy", -1, f"n_steps={self.n_steps} is not 3*dim_3d: the sampled tokens "
                                   "are not one action")
+        if masked:
+            ee = [None]
+
+            @torch.no_grad()
+            def masked_policy(frames, scalars, rows, step, active, out):
+                B = frames.shape[0]
+                if ee[0] is None or ee[0].shape[0] != B:
+                    S = self.config["S"]
+                    ee[0] = torch.zeros((B, 3 * S * S, self.config["c"]), dtype=torch.float32, device=self.device)
+                self.torso(frames, scalars, out=ee[0], flags=active, need=1)
+                self.sample(ee[0], rows, seed, call=step, k=1, tokens=out.view(B, 1, self.n_steps), flags=active, need=1)
+                return out
+
+            masked_policy.takes_active = True
+            return masked_policy
 
         @torch.no_grad()
         def policy(frames, scalars, rows, step):

@@ -1005,15 +1005,23 @@ def rollout_records(G: int, S: int, device):
 
 
 def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nnz=None, overflow=None, actions=None,
-                    shift: int = 1):
+                    shift: int = 1, active=None, stop_solved: bool = False):
     """One step of a sampled rollout in one launch (tg_rollout_advance): == reference training.py:253-268 (the new
     head, the history shift, scalars + 1, rank_ubs and the best sample per group) + the running statistics of
     :343-346.  frames int8 (B,T,S,S,S), stepped IN PLACE (newest first: the next ``net_torso`` input); tokens int8
     (B,3S); rows are group-major, row g*n + s = sample s of group g; ``records`` = (best_nnz, hits, solved_step,
     solved_sample), int32 (B/n,) each (``rollout_records``), updated; scalars float32 (B,dim_s) += 1; overflow uint8
     (B,) is set where an entry left int8; actions int8 (B,max_actions,3S) receives the tokens at index ``step``.
-    Returns nnz int32 (B,), the non-zero count of every new head."""
+    Returns nnz int32 (B,), the non-zero count of every new head.
+
+    ``stop_solved`` (tg_rollout_advance_masked): only the groups whose solved_step is still negative are stepped; of the
+    others nothing but solved_step is read and nothing is written.  ``active`` uint8 (B,), initialised to 1 by the
+    caller, receives 1 for the rows of a group still unsolved after this step and 0 for the rows of a group it solved:
+    the row mask of the next ``net_torso`` / ``net_sample`` call (``need=1``).  A given ``nnz`` keeps the counts of the
+    rows that are not stepped; an allocated one holds zeros there."""
     _need_gpu(frames, "frames")
+    if active is not None and not stop_solved:
+        raise TensorGameError("rollout_advance", -1, "active is written by the masked step only: pass stop_solved=True")
     if frames.dtype != torch.int8 or frames.dim() != 5 or not (frames.shape[2] == frames.shape[3] == frames.shape[4]):
         raise TensorGameError("rollout_advance", -1, f"frames must be int8 (B,T,S,S,S), got {frames.dtype} "
                               f"{tuple(frames.shape)}")
@@ -1032,16 +1040,22 @@ def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nn
         actions = _flag(actions, (B, max_actions, 3 * S), torch.int8, dev, "actions")
     rollout_check(B, n, S, T, dim_s, step, max_actions, actions is not None)
     if nnz is None:
-        nnz = torch.empty((B,), dtype=torch.int32, device=dev)
+        nnz = (torch.zeros if stop_solved else torch.empty)((B,), dtype=torch.int32, device=dev)
     nnz = _flag(nnz, (B,), torch.int32, dev, "nnz")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
+    active = _flag(active, (B,), torch.uint8, dev, "active")
     if len(records) != 4:
         raise TensorGameError("rollout_advance", -1, "records must be (best_nnz, hits, solved_step, solved_sample)")
     rec = [_flag(r, (B // n,), torch.int32, dev, name)
            for r, name in zip(records, ("best_nnz", "hits", "solved_step", "solved_sample"))]
     if any(r is None for r in rec):
         raise TensorGameError("rollout_advance", -1, "records must be four int32 tensors (ops.rollout_records)")
+    sizes = (B, int(n), S, T, dim_s, int(step), max_actions, int(shift))
     with torch.cuda.device(dev):
-        call("tg_rollout_advance", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow), *map(_ptr, rec),
-             _ptr(actions), B, int(n), S, T, dim_s, int(step), max_actions, int(shift), _stream(dev))
+        if stop_solved:
+            call("tg_rollout_advance_masked", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow),
+                 *map(_ptr, rec), _ptr(actions), _ptr(active), *sizes, _stream(dev))
+        else:
+            call("tg_rollout_advance", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow),
+                 *map(_ptr, rec), _ptr(actions), *sizes, _stream(dev))
     return nnz

@@ -1,6 +1,7 @@
 """Sampled policy rollouts (include/tensor_game_rollout.h, mat_mul_amd/rollout.py) on one MI355X.
 
     python tools/rollout_bench.py OUT_DIR [--parts a,b,c] [--configs a,a9,a16] [--reps 20] [--warmup 3]
+    python tools/rollout_bench.py OUT_DIR --masked [--configs a,a16] [--fractions 1,0.5,0.1,0] [--repeats 5]
 
 Writes (and, part by part, merges into) OUT_DIR/r12_rollout.json.  HIP events around each call after warm-up; median,
 p10 and p90 in microseconds; two variants of one figure alternate call by call in one process.
@@ -18,6 +19,14 @@ p10 and p90 in microseconds; two variants of one figure alternate call by call i
  (c) the feature in use, a report and not a test: FusedTrainer at configuration a on SyntheticDemos of 2 actions at
      S = 4, a solution search on 256 held-out targets (n = 8, max_actions = 4) every 50 training steps for 400 steps;
      num_solved, num_hits and lowest_rank per search.
+
+--masked writes OUT_DIR/r14_rollout_masked.json instead: ONE step of the solution search (policy + advance) at
+G = 256 x n = 8 rows with a share f of the groups still active (solved_step < 0 for them, every f-th group; the rows'
+mask to match), for each f: the plain step (rollout_policy + tg_rollout_advance, which does not look at the records:
+the same work at every f) next to the masked step (rollout_policy(masked=True) + tg_rollout_advance_masked), alternating
+call by call in one process.  The records are put back before every call (both variants pay the same four small
+copies), so every call sees the same share.  The whole measurement is made --repeats times; the spread of the plain
+step's medians over the repeats is reported beside the figures.
 """
 from __future__ import annotations
 
@@ -218,6 +227,61 @@ def part_c():
             "wall_s": time.perf_counter() - t0}
 
 
+def part_masked(configs, fractions, reps, warmup, repeats):
+    out = []
+    G, n = 256, 8
+    B = G * n
+    for name in configs:
+        cfg = CONFIGS[name]
+        S, T = cfg["dim_3d"], cfg["dim_t"]
+        net = FusedAlphaTensor.from_state_dict(make_weights(cfg, 11), cfg["n_samples"], device=DEV)
+        rng = np.random.default_rng(S)
+        frames = torch.from_numpy(rng.integers(-1, 2, size=(B, T, S, S, S)).astype(np.int8)).to(DEV)
+        scal = torch.zeros((B, cfg["dim_s"]), device=DEV)
+        rows = torch.arange(B, device=DEV)
+        plain_pol, masked_pol = net.rollout_policy(seed=5), net.rollout_policy(seed=5, masked=True)
+        tokens = torch.ones((B, 3 * S), dtype=torch.int8, device=DEV)
+        nnz = torch.zeros((B,), dtype=torch.int32, device=DEV)
+        rec = ops.rollout_records(G, S, DEV)
+        active = torch.ones((B,), dtype=torch.uint8, device=DEV)
+        for f in fractions:
+            k = int(round(f * G))
+            on = torch.zeros((G,), dtype=torch.bool, device=DEV)
+            if k:
+                on[torch.linspace(0, G - 1, k, device=DEV).round().long()] = True
+            fresh = list(ops.rollout_records(G, S, DEV))
+            fresh[2] = torch.where(on, -1, 0).to(torch.int32)
+            fresh[3] = fresh[2].clone()
+            mask = on.repeat_interleave(n).to(torch.uint8)
+
+            def restore():
+                for r, x in zip(rec, fresh):
+                    r.copy_(x)
+                active.copy_(mask)
+
+            def plain():
+                restore()
+                tok = plain_pol(frames, scal, rows, 0)
+                ops.rollout_advance(frames, tok, n, 0, rec, scalars=scal, nnz=nnz)
+
+            def masked():
+                restore()
+                masked_pol(frames, scal, rows, 0, active=active, out=tokens)
+                ops.rollout_advance(frames, tokens, n, 0, rec, scalars=scal, nnz=nnz, active=active, stop_solved=True)
+
+            runs = [alternate({"plain": plain, "masked": masked}, reps, warmup) for _ in range(repeats)]
+            med = {v: [r[v]["median_us"] for r in runs] for v in ("plain", "masked")}
+            row = {"config": name, "S": S, "T": T, "G": G, "n": n, "active_fraction": k / G,
+                   "plain_median_us": statistics.median(med["plain"]), "masked_median_us": statistics.median(med["masked"]),
+                   "plain_medians_us": med["plain"], "masked_medians_us": med["masked"],
+                   "plain_spread_us": max(med["plain"]) - min(med["plain"]),
+                   "masked_over_plain": statistics.median(med["masked"]) / statistics.median(med["plain"]),
+                   "calls_per_median": runs[0]["plain"]["n"], "repeats": repeats}
+            out.append(row)
+            print(json.dumps(row), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out_dir")
@@ -225,10 +289,26 @@ def main():
     ap.add_argument("--configs", default="a,a9,a16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--masked", action="store_true", help="time the step that stops solved groups (see above)")
+    ap.add_argument("--fractions", default="1,0.5,0.1,0")
+    ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU; there is no CPU path"
     out = Path(args.out_dir)
     out.mkdir(parents=True, exist_ok=True)
+    if args.masked:
+        path = out / "r14_rollout_masked.json"
+        res = json.loads(path.read_text()) if path.exists() else {}
+        configs = [c for c in args.configs.split(",") if c != "a9"] if args.configs == "a,a9,a16" else args.configs.split(",")
+        done = {(r["config"], r["active_fraction"]): r for r in res.get("masked_step", [])}
+        for r in part_masked(configs, [float(x) for x in args.fractions.split(",")], args.reps, args.warmup, args.repeats):
+            done[(r["config"], r["active_fraction"])] = r
+        res["masked_step"] = [done[k] for k in sorted(done, key=lambda k: (k[0], -k[1]))]
+        res["device"] = torch.cuda.get_device_name(0)
+        res.setdefault("commands", []).append(" ".join(sys.argv))
+        path.write_text(json.dumps(res, indent=1))
+        print(f"wrote {path}")
+        return
     path = out / "r12_rollout.json"
     res = json.loads(path.read_text()) if path.exists() else {}
     parts = args.parts.split(",")
