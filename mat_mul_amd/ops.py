@@ -35,6 +35,17 @@ def _stream(dev: torch.device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _launch(dev, name: str, *args) -> None:
+    """Enqueue ``name`` on device ``dev``: the device guard, and the caller's current stream as the last argument."""
+    with torch.cuda.device(dev):
+        call(name, *args, _stream(dev))
+
+
+def _u64(x) -> int:
+    """A seed or call index as the 64 bits the ABI takes (negative values wrap)."""
+    return int(x) & (2 ** 64 - 1)
+
+
 def _need_gpu(t: torch.Tensor, name: str) -> None:
     if not t.is_cuda:
         raise TensorGameError(name, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
@@ -73,6 +84,25 @@ def _flag(t: Optional[torch.Tensor], shape: Tuple[int, ...], dtype, dev, name: s
     return t
 
 
+def _out(t: Optional[torch.Tensor], shape: Tuple[int, ...], dtype, dev, name: str, new=torch.empty) -> torch.Tensor:
+    """An optional output: allocated with ``new`` when it is not given, held to the rule of ``_flag`` when it is."""
+    if t is None:
+        return new(shape, dtype=dtype, device=dev)
+    return _flag(t, shape, dtype, dev, name)
+
+
+def _out_states(out, state, B: int, S: int, stride: int, fn: str) -> torch.Tensor:
+    """The state batch an entry writes for the input batch ``state``: allocated with the input's strides when it is not
+    given, else of the same shape, game stride and device (``out=state`` is the in-place form)."""
+    dev = state.device
+    if out is None:
+        out = torch.empty_strided(state.shape, state.stride(), dtype=torch.int8, device=dev)
+    Bo, So, ostride = _state_layout(out, "out")
+    if (Bo, So) != (B, S) or (B > 1 and ostride != stride) or out.device != dev:
+        raise TensorGameError(fn, -1, "out must match state's shape, stride and device")
+    return out
+
+
 def as_tokens(actions, device=None, check: bool = True) -> torch.Tensor:
     """int64 (reference dtype, datasets.py:140) or any integer tensor -> int8 tokens.
     ``check`` verifies the values fit int8 (one host sync); the reference never range-checks
@@ -106,18 +136,10 @@ def step(state, actions, out=None, done=None, overflow=None, shift: int = 1):
     B, S, stride = _state_layout(state, "state")
     dev = state.device
     actions = _tokens(actions, (B,), S, dev, "actions")
-    if out is None:
-        out = torch.empty_strided(state.shape, state.stride(), dtype=torch.int8, device=dev)
-    Bo, So, ostride = _state_layout(out, "out")
-    if (Bo, So) != (B, S) or (B > 1 and ostride != stride) or out.device != dev:
-        raise TensorGameError("step", -1, "out must match state's shape, stride and device")
-    if done is None:
-        done = torch.empty((B,), dtype=torch.uint8, device=dev)
-    done = _flag(done, (B,), torch.uint8, dev, "done")
+    out = _out_states(out, state, B, S, stride, "step")
+    done = _out(done, (B,), torch.uint8, dev, "done")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
-    with torch.cuda.device(dev):
-        call("tg_step_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done), _ptr(overflow),
-             B, S, stride, int(shift), _stream(dev))
+    _launch(dev, "tg_step_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done), _ptr(overflow), B, S, stride, int(shift))
     return out, done
 
 
@@ -131,8 +153,7 @@ def copy_states(state, out=None):
     Bo, So, ostride = _state_layout(out, "out")
     if (Bo, So) != (B, S) or out.device != dev:
         raise TensorGameError("copy_states", -1, "out must match state's shape and device")
-    with torch.cuda.device(dev):
-        call("tg_copy_i8", _ptr(state), _ptr(out), B, S, stride, ostride, _stream(dev))
+    _launch(dev, "tg_copy_i8", _ptr(state), _ptr(out), B, S, stride, ostride)
     return out
 
 
@@ -170,18 +191,11 @@ def step_many(state, actions, out=None, done_step=None, overflow=None, shift: in
         raise TensorGameError("step_many", -1, "actions must be (B,K,3S)")
     K = actions.shape[1]
     actions = _tokens(actions, (B, K), S, dev, "actions")
-    if out is None:
-        out = torch.empty_strided(state.shape, state.stride(), dtype=torch.int8, device=dev)
-    Bo, So, ostride = _state_layout(out, "out")
-    if (Bo, So) != (B, S) or (B > 1 and ostride != stride) or out.device != dev:
-        raise TensorGameError("step_many", -1, "out must match state's shape, stride and device")
-    if done_step is None:
-        done_step = torch.empty((B,), dtype=torch.int32, device=dev)
-    done_step = _flag(done_step, (B,), torch.int32, dev, "done_step")
+    out = _out_states(out, state, B, S, stride, "step_many")
+    done_step = _out(done_step, (B,), torch.int32, dev, "done_step")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
-    with torch.cuda.device(dev):
-        call("tg_step_many_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done_step), _ptr(overflow),
-             B, S, K, stride, int(shift), _stream(dev))
+    _launch(dev, "tg_step_many_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done_step), _ptr(overflow),
+            B, S, K, stride, int(shift))
     return out, done_step
 
 
@@ -194,13 +208,10 @@ def step_tracked(state, actions, nnz, done=None, overflow=None, shift: int = 1):
     actions = _tokens(actions, (B,), S, dev, "actions")
     if nnz.dtype != torch.int32 or tuple(nnz.shape) != (B,) or not nnz.is_contiguous() or nnz.device != dev:
         raise TensorGameError("step_tracked", -1, f"nnz must be a contiguous int32 ({B},) tensor on {dev}")
-    if done is None:
-        done = torch.empty((B,), dtype=torch.uint8, device=dev)
-    done = _flag(done, (B,), torch.uint8, dev, "done")
+    done = _out(done, (B,), torch.uint8, dev, "done")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
-    with torch.cuda.device(dev):
-        call("tg_step_tracked_i8", _ptr(state), _ptr(actions), _ptr(nnz), _ptr(done), _ptr(overflow), B, S, stride, int(shift),
-             _stream(dev))
+    _launch(dev, "tg_step_tracked_i8", _ptr(state), _ptr(actions), _ptr(nnz), _ptr(done), _ptr(overflow), B, S, stride,
+            int(shift))
     return state, done
 
 
@@ -231,9 +242,7 @@ def step_stream(state, actions, done=None, overflow=None, ready=None, progress=N
         raise TensorGameError("step_stream", -1, "actions must be (K,B,3S), step-major")
     K = actions.shape[0]
     actions = _tokens(actions, (K, B), S, dev, "actions")
-    if done is None:
-        done = torch.empty((K, B), dtype=torch.uint8, device=dev)
-    done = _flag(done, (K, B), torch.uint8, dev, "done")
+    done = _out(done, (K, B), torch.uint8, dev, "done")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
     for name, t, n in (("ready", ready, K), ("progress", progress, None), ("status", status, 1)):
         if t is not None and (t.dtype not in (torch.int32, torch.uint32) or t.dim() != 1 or not t.is_contiguous()
@@ -250,9 +259,8 @@ def step_stream(state, actions, done=None, overflow=None, ready=None, progress=N
             n_units = -(-B // 64)  # beyond the resident batch, without ready words: units of 64 games in rounds
         if progress.numel() < n_units:
             raise TensorGameError("step_stream", -1, "progress needs one word per unit (ops.step_stream_layout)")
-    with torch.cuda.device(dev):
-        call("tg_step_stream_i8", _ptr(state), _ptr(actions), _ptr(done), _ptr(overflow), _ptr(ready), _ptr(progress),
-             _ptr(status), B, S, K, stride, int(shift), _stream(dev))
+    _launch(dev, "tg_step_stream_i8", _ptr(state), _ptr(actions), _ptr(done), _ptr(overflow), _ptr(ready), _ptr(progress),
+            _ptr(status), B, S, K, stride, int(shift))
     return state, done
 
 
@@ -282,25 +290,17 @@ def expand(state, actions, out=None, done=None, changed=None, overflow=None, shi
     if ostride < S ** 3 or (B > 1 and k > 1 and out.stride(0) != k * ostride):
         raise TensorGameError("expand", -1, f"out: children must be evenly spaced (strides {out.stride()[:2]}); "
                                             "a slice like big[:, :k] of a wider buffer is not")
-    if done is None:
-        done = torch.empty((B, k), dtype=torch.uint8, device=dev)
-    if changed is None:
-        changed = torch.empty((B, k), dtype=torch.uint8, device=dev)
-    done = _flag(done, (B, k), torch.uint8, dev, "done")
-    changed = _flag(changed, (B, k), torch.uint8, dev, "changed")
+    done = _out(done, (B, k), torch.uint8, dev, "done")
+    changed = _out(changed, (B, k), torch.uint8, dev, "changed")
     overflow = _flag(overflow, (B, k), torch.uint8, dev, "overflow")
-    if want_keys and keys is None:
-        keys = torch.empty((B, k), dtype=torch.int64, device=dev)
-    if keys is not None:
-        keys = _flag(keys, (B, k), torch.int64, dev, "keys")
-        with torch.cuda.device(dev):
-            call("tg_expand_keyed_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done), _ptr(changed),
-                 _ptr(overflow), _ptr(keys), B, S, k, stride, ostride, int(shift), _stream(dev))
-        return out, done, changed, keys
-    with torch.cuda.device(dev):
-        call("tg_expand_i8", _ptr(state), _ptr(out), _ptr(actions), _ptr(done), _ptr(changed),
-             _ptr(overflow), B, S, k, stride, ostride, int(shift), _stream(dev))
-    return out, done, changed
+    ptrs = (_ptr(state), _ptr(out), _ptr(actions), _ptr(done), _ptr(changed), _ptr(overflow))
+    sizes = (B, S, k, stride, ostride, int(shift))
+    if not want_keys and keys is None:
+        _launch(dev, "tg_expand_i8", *ptrs, *sizes)
+        return out, done, changed
+    keys = _out(keys, (B, k), torch.int64, dev, "keys")
+    _launch(dev, "tg_expand_keyed_i8", *ptrs, _ptr(keys), *sizes)
+    return out, done, changed, keys
 
 
 def done(state, want_nnz: bool = False):
@@ -310,8 +310,7 @@ def done(state, want_nnz: bool = False):
     dev = state.device
     d = torch.empty((B,), dtype=torch.uint8, device=dev)
     nnz = torch.empty((B,), dtype=torch.int32, device=dev) if want_nnz else None
-    with torch.cuda.device(dev):
-        call("tg_done_i8", _ptr(state), _ptr(d), _ptr(nnz), B, S, stride, _stream(dev))
+    _launch(dev, "tg_done_i8", _ptr(state), _ptr(d), _ptr(nnz), B, S, stride)
     return (d, nnz) if want_nnz else d
 
 
@@ -320,8 +319,7 @@ def reset_matmul(out, n: int):
     B, S, stride = _state_layout(out, "out")
     if S != n * n:
         raise TensorGameError("reset_matmul", -1, f"S={S} != n*n={n * n}")
-    with torch.cuda.device(out.device):
-        call("tg_reset_matmul_i8", _ptr(out), B, int(n), stride, _stream(out.device))
+    _launch(out.device, "tg_reset_matmul_i8", _ptr(out), B, int(n), stride)
     return out
 
 
@@ -332,8 +330,7 @@ def reset_broadcast(out, start):
     if start.dtype != torch.int8 or tuple(start.shape) != (S, S, S) or start.device != out.device:
         raise TensorGameError("reset_broadcast", -1, f"start must be int8 {(S, S, S)} on {out.device}")
     start = start.contiguous()
-    with torch.cuda.device(out.device):
-        call("tg_reset_broadcast_i8", _ptr(start), _ptr(out), B, S, stride, _stream(out.device))
+    _launch(out.device, "tg_reset_broadcast_i8", _ptr(start), _ptr(out), B, S, stride)
     return out
 
 
@@ -352,9 +349,7 @@ def gen_from_factors(actions, S: int, out=None, overflow=None, shift: int = 1):
     if (Bo, So) != (B, S) or out.device != dev:
         raise TensorGameError("gen_from_factors", -1, "out shape/device mismatch")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
-    with torch.cuda.device(dev):
-        call("tg_gen_from_factors_i8", _ptr(actions), _ptr(out), _ptr(overflow), B, S, R, stride,
-             int(shift), _stream(dev))
+    _launch(dev, "tg_gen_from_factors_i8", _ptr(actions), _ptr(out), _ptr(overflow), B, S, R, stride, int(shift))
     return out
 
 
@@ -402,10 +397,8 @@ def gen_demos(B: int, S: int, R: int, device, values=(-1, 0, 1), probs=(0.15, 0.
         if basis.dtype != torch.int8 or tuple(basis.shape) != (B, 3, S, S) or basis.device != dev:
             raise TensorGameError("gen_demos", -1, f"basis must be int8 {(B, 3, S, S)} on {dev}")
         basis = basis.contiguous()
-    with torch.cuda.device(dev):
-        call("tg_gen_demos_i8", _ptr(target), _ptr(actions), _ptr(overflow), B, S, R, thr_p, val_p, nv,
-             int(shift), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(game_id_offset), _ptr(basis), stride,
-             _stream(dev))
+    _launch(dev, "tg_gen_demos_i8", _ptr(target), _ptr(actions), _ptr(overflow), B, S, R, thr_p, val_p, nv,
+            int(shift), C.c_uint64(_u64(seed)), C.c_uint64(game_id_offset), _ptr(basis), stride)
     return actions, target
 
 
@@ -425,9 +418,8 @@ def sample_basis(B: int, S: int, device, values=(-1, 0, 1), probs=None, seed: in
     P = torch.empty((B, 3, S, S), dtype=torch.int8, device=dev)
     L = torch.empty_like(P) if want_factors else None
     U = torch.empty_like(P) if want_factors else None
-    with torch.cuda.device(P.device):
-        call("tg_sample_basis_i8", _ptr(P), _ptr(L), _ptr(U), B, S, thr_p, val_p, nv,
-             C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(game_id_offset), _stream(P.device))
+    _launch(P.device, "tg_sample_basis_i8", _ptr(P), _ptr(L), _ptr(U), B, S, thr_p, val_p, nv,
+            C.c_uint64(_u64(seed)), C.c_uint64(game_id_offset))
     return (P, L, U) if want_factors else P
 
 
@@ -438,16 +430,11 @@ def change_basis(state, basis, out=None, overflow=None):
     if basis.dtype != torch.int32 or tuple(basis.shape) != (B, 3, S, S) or basis.device != dev:
         raise TensorGameError("change_basis", -1, f"basis must be int32 {(B, 3, S, S)} on {dev}")
     basis = basis.contiguous()
-    if out is None:
-        out = torch.empty_strided(state.shape, state.stride(), dtype=torch.int8, device=dev)
-    Bo, So, ostride = _state_layout(out, "out")
-    if (Bo, So) != (B, S) or (B > 1 and ostride != stride):
-        raise TensorGameError("change_basis", -1, "out must match state's shape and stride")
+    out = _out_states(out, state, B, S, stride, "change_basis")
     if out.data_ptr() == state.data_ptr():
         raise TensorGameError("change_basis", -1, "in-place change of basis is not supported")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
-    with torch.cuda.device(dev):
-        call("tg_change_basis_i8", _ptr(state), _ptr(basis), _ptr(out), _ptr(overflow), B, S, stride, _stream(dev))
+    _launch(dev, "tg_change_basis_i8", _ptr(state), _ptr(basis), _ptr(out), _ptr(overflow), B, S, stride)
     return out
 
 
@@ -460,31 +447,45 @@ def alloc_ring(B: int, S: int, T: int, device, pad_to: int = 16) -> torch.Tensor
     return buf[:, :, :n].unflatten(2, (S, S, S))
 
 
+# dtype codes of the model input (include/tensor_game.h); items may also be int8
+_FLOAT_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_ITEM_DTYPES = {**_FLOAT_DTYPES, torch.int8: 3}
+
+
+def _ring_layout(ring, fn: str) -> Tuple[int, int, int, int, int]:
+    """(B, T, S, frame_stride, game_stride) in bytes of an int8 (B,T,S,S,S) history ring whose frames are dense (the
+    layout of ``alloc_ring``; a single frame or a single game has no stride of its own to read)."""
+    _need_gpu(ring, "ring")
+    if ring.dtype != torch.int8 or ring.dim() != 5 or not (ring.shape[2] == ring.shape[3] == ring.shape[4]):
+        raise TensorGameError(fn, -1, f"ring must be int8 (B,T,S,S,S), got {ring.dtype} {tuple(ring.shape)}")
+    B, T, S = ring.shape[0], ring.shape[1], ring.shape[2]
+    if ring.stride()[2:] != (S * S, S, 1):
+        raise TensorGameError(fn, -1, "each frame must be C-contiguous (S,S,S)")
+    fs = ring.stride(1) if T > 1 else S ** 3
+    gs = ring.stride(0) if B > 1 else max(ring.stride(0), (T - 1) * fs + S ** 3)
+    return B, T, S, fs, gs
+
+
+def _model_input(out, scalars, shape: Tuple[int, ...], dtype, dev, fn: str):
+    """The model input ``out`` (B,T,S,S,S) of ``dtype`` and its ``scalars`` float32 (B,1), each allocated when it is
+    not given."""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise TensorGameError(fn, -1, "out must be contiguous (B,T,S,S,S) of the requested dtype")
+    return out, _out(scalars, (shape[0], 1), torch.float32, dev, "scalars")
+
+
 def emit_frames(ring, head_slot: int, t_step: float = 0.0, dtype=torch.float32, out=None, scalars=None):
     """(B,T,S,S,S) model input from the history ring, newest frame first, plus the (B,1) scalars.
     == the history shift of get_child_states (act.py:271-274) + get_scalars (utils.py:22-37)."""
-    _need_gpu(ring, "ring")
-    if ring.dtype != torch.int8 or ring.dim() != 5 or not (ring.shape[2] == ring.shape[3] == ring.shape[4]):
-        raise TensorGameError("emit_frames", -1, f"ring must be int8 (B,T,S,S,S), got {ring.dtype} {tuple(ring.shape)}")
-    B, T, S = ring.shape[0], ring.shape[1], ring.shape[2]
-    if ring.stride()[2:] != (S * S, S, 1):
-        raise TensorGameError("emit_frames", -1, "each frame must be C-contiguous (S,S,S)")
-    fs = ring.stride(1) if T > 1 else S ** 3
-    gs = ring.stride(0) if B > 1 else max(ring.stride(0), (T - 1) * fs + S ** 3)
-    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-    if dtype not in codes:
+    B, T, S, fs, gs = _ring_layout(ring, "emit_frames")
+    if dtype not in _FLOAT_DTYPES:
         raise TensorGameError("emit_frames", -1, "dtype must be float32, float16 or bfloat16")
     dev = ring.device
-    if out is None:
-        out = torch.empty((B, T, S, S, S), dtype=dtype, device=dev)
-    if out.dtype != dtype or tuple(out.shape) != (B, T, S, S, S) or not out.is_contiguous() or out.device != dev:
-        raise TensorGameError("emit_frames", -1, "out must be contiguous (B,T,S,S,S) of the requested dtype")
-    if scalars is None:
-        scalars = torch.empty((B, 1), dtype=torch.float32, device=dev)
-    scalars = _flag(scalars, (B, 1), torch.float32, dev, "scalars")
-    with torch.cuda.device(dev):
-        call("tg_emit_frames", _ptr(ring), _ptr(out), _ptr(scalars), codes[dtype], B, S, T,
-             int(head_slot) % T, C.c_float(float(t_step)), fs, gs, _stream(dev))
+    out, scalars = _model_input(out, scalars, (B, T, S, S, S), dtype, dev, "emit_frames")
+    _launch(dev, "tg_emit_frames", _ptr(ring), _ptr(out), _ptr(scalars), _FLOAT_DTYPES[dtype], B, S, T,
+            int(head_slot) % T, C.c_float(float(t_step)), fs, gs)
     return out, scalars
 
 
@@ -493,38 +494,44 @@ def step_emit(ring, head_slot: int, actions, t_step: float = 0.0, dtype=torch.fl
     """One env step on the history ring and the model input of the new state, in one call (the fused form of
     ``step`` + ``emit_frames``; one kernel at S=4).  The new head is written into slot ``(head_slot + 1) % T``.
     Returns (out (B,T,S,S,S), scalars (B,1), done (B,), new_head_slot)."""
-    _need_gpu(ring, "ring")
-    if ring.dtype != torch.int8 or ring.dim() != 5 or not (ring.shape[2] == ring.shape[3] == ring.shape[4]):
-        raise TensorGameError("step_emit", -1, f"ring must be int8 (B,T,S,S,S), got {ring.dtype} {tuple(ring.shape)}")
-    B, T, S = ring.shape[0], ring.shape[1], ring.shape[2]
-    if ring.stride()[2:] != (S * S, S, 1):
-        raise TensorGameError("step_emit", -1, "each frame must be C-contiguous (S,S,S)")
-    fs = ring.stride(1) if T > 1 else S ** 3
-    gs = ring.stride(0) if B > 1 else max(ring.stride(0), (T - 1) * fs + S ** 3)
-    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-    if dtype not in codes:
+    B, T, S, fs, gs = _ring_layout(ring, "step_emit")
+    if dtype not in _FLOAT_DTYPES:
         raise TensorGameError("step_emit", -1, "dtype must be float32, float16 or bfloat16")
     dev = ring.device
     actions = _tokens(actions, (B,), S, dev, "actions")
-    if out is None:
-        out = torch.empty((B, T, S, S, S), dtype=dtype, device=dev)
-    if out.dtype != dtype or tuple(out.shape) != (B, T, S, S, S) or not out.is_contiguous() or out.device != dev:
-        raise TensorGameError("step_emit", -1, "out must be contiguous (B,T,S,S,S) of the requested dtype")
-    if scalars is None:
-        scalars = torch.empty((B, 1), dtype=torch.float32, device=dev)
-    scalars = _flag(scalars, (B, 1), torch.float32, dev, "scalars")
-    if done is None:
-        done = torch.empty((B,), dtype=torch.uint8, device=dev)
-    done = _flag(done, (B,), torch.uint8, dev, "done")
+    out, scalars = _model_input(out, scalars, (B, T, S, S, S), dtype, dev, "step_emit")
+    done = _out(done, (B,), torch.uint8, dev, "done")
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
     head = int(head_slot) % T
-    with torch.cuda.device(dev):
-        call("tg_step_emit", _ptr(ring), _ptr(actions), _ptr(out), _ptr(scalars), _ptr(done), _ptr(overflow), codes[dtype],
-             B, S, T, head, C.c_float(float(t_step)), fs, gs, int(shift), _stream(dev))
+    _launch(dev, "tg_step_emit", _ptr(ring), _ptr(actions), _ptr(out), _ptr(scalars), _ptr(done), _ptr(overflow),
+            _FLOAT_DTYPES[dtype], B, S, T, head, C.c_float(float(t_step)), fs, gs, int(shift))
     return out, scalars, done, (head + 1) % T
 
 
-_ITEM_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.int8: 3}
+def _item_idx(idx, dev, fn: str) -> torch.Tensor:
+    """The flat item indices int64 (N,) on ``dev``, made contiguous."""
+    _need_gpu(idx, "idx")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
+        raise TensorGameError(fn, -1, f"idx must be int64 (N,) on {dev}, got {idx.dtype} {tuple(idx.shape)} on {idx.device}")
+    return idx if idx.is_contiguous() else idx.contiguous()
+
+
+def _item_outputs(N: int, T: int, S: int, dtype, dev, fn: str, out, scalars, actions, rewards, overflow, status):
+    """The outputs of N items in the layout of ``demo_items``: (dtype code, frames (N,T,S,S,S) of ``dtype``, scalars
+    float32 (N,1), actions int8 (N,3S), rewards float32 (N,1)), each allocated when it is not given, and the optional
+    overflow uint8 (N,) and status uint32 (1,)."""
+    if dtype not in _ITEM_DTYPES:
+        raise TensorGameError(fn, -1, "dtype must be float32, float16, bfloat16 or int8")
+    if out is None:
+        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
+    elif out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
+        raise TensorGameError(fn, -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
+    return (_ITEM_DTYPES[dtype], out,
+            _out(scalars, (N, 1), torch.float32, dev, "scalars"),
+            _out(actions, (N, 3 * S), torch.int8, dev, "actions"),
+            _out(rewards, (N, 1), torch.float32, dev, "rewards"),
+            _flag(overflow, (N,), torch.uint8, dev, "overflow"),
+            _flag(status, (1,), torch.uint32, dev, "status"))
 
 
 def demo_items(tokens, targets, idx, T: int, dtype=torch.float32, out=None, scalars=None, actions=None, rewards=None,
@@ -542,32 +549,12 @@ def demo_items(tokens, targets, idx, T: int, dtype=torch.float32, out=None, scal
         raise TensorGameError("demo_items", -1, f"tokens must be int8 (n_demos,R,3S) with n_demos={B}, got {tuple(tokens.shape)}")
     R = tokens.shape[1]
     tokens = _tokens(tokens, (B, R), S, dev, "tokens")
-    _need_gpu(idx, "idx")
-    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
-        raise TensorGameError("demo_items", -1, f"idx must be int64 (N,) on {dev}, got {idx.dtype} {tuple(idx.shape)} on {idx.device}")
-    idx = idx if idx.is_contiguous() else idx.contiguous()
+    idx = _item_idx(idx, dev, "demo_items")
     N = idx.shape[0]
-    if dtype not in _ITEM_DTYPES:
-        raise TensorGameError("demo_items", -1, "dtype must be float32, float16, bfloat16 or int8")
-    if out is None:
-        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
-    if out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
-        raise TensorGameError("demo_items", -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
-    if scalars is None:
-        scalars = torch.empty((N, 1), dtype=torch.float32, device=dev)
-    if actions is None:
-        actions = torch.empty((N, 3 * S), dtype=torch.int8, device=dev)
-    if rewards is None:
-        rewards = torch.empty((N, 1), dtype=torch.float32, device=dev)
-    scalars = _flag(scalars, (N, 1), torch.float32, dev, "scalars")
-    actions = _flag(actions, (N, 3 * S), torch.int8, dev, "actions")
-    rewards = _flag(rewards, (N, 1), torch.float32, dev, "rewards")
-    overflow = _flag(overflow, (N,), torch.uint8, dev, "overflow")
-    status = _flag(status, (1,), torch.uint32, dev, "status")
-    with torch.cuda.device(dev):
-        call("tg_demo_items", _ptr(tokens), _ptr(targets), B, R, S, stride, _ptr(idx), N, int(T), _ITEM_DTYPES[dtype],
-             _ptr(out), _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), int(shift),
-             _stream(dev))
+    code, out, scalars, actions, rewards, overflow, status = _item_outputs(
+        N, T, S, dtype, dev, "demo_items", out, scalars, actions, rewards, overflow, status)
+    _launch(dev, "tg_demo_items", _ptr(tokens), _ptr(targets), B, R, S, stride, _ptr(idx), N, int(T), code,
+            _ptr(out), _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), int(shift))
     return out, scalars, actions, rewards
 
 
@@ -576,8 +563,7 @@ def state_hash(state) -> torch.Tensor:
     replaces state_to_str (utils.py:164-169).  Equal states <=> equal keys (up to 2^-64 collisions)."""
     B, S, stride = _state_layout(state, "state")
     out = torch.empty((B,), dtype=torch.int64, device=state.device)
-    with torch.cuda.device(state.device):
-        call("tg_hash_u64", _ptr(state), _ptr(out), B, S, stride, _stream(state.device))
+    _launch(state.device, "tg_hash_u64", _ptr(state), _ptr(out), B, S, stride)
     return out
 
 
@@ -603,16 +589,12 @@ def seen(keys, table, mask=None, insert: bool = False, status=None, fresh=None) 
     if table.dtype != torch.int64 or table.dim() != 1 or not table.is_contiguous() or table.device != dev:
         raise TensorGameError("seen", -1, f"table must be a contiguous int64 vector on {dev} (ops.alloc_seen_table)")
     n = keys.numel()
-    if mask is not None:
-        mask = _flag(mask, tuple(keys.shape), torch.uint8, dev, "mask")
-    if fresh is None:
-        fresh = torch.empty(tuple(keys.shape), dtype=torch.uint8, device=dev)
-    fresh = _flag(fresh, tuple(keys.shape), torch.uint8, dev, "fresh")
+    mask = _flag(mask, tuple(keys.shape), torch.uint8, dev, "mask")
+    fresh = _out(fresh, tuple(keys.shape), torch.uint8, dev, "fresh")
     if status is not None and (status.dtype not in (torch.int32, torch.uint32) or status.numel() != 1 or status.device != dev):
         raise TensorGameError("seen", -1, f"status must be one 32-bit word on {dev}")
-    with torch.cuda.device(dev):
-        call("tg_seen_u64", _ptr(keys), _ptr(table), table.numel(), _ptr(fresh), _ptr(mask), _ptr(status), n,
-             1 if insert else 0, _stream(dev))
+    _launch(dev, "tg_seen_u64", _ptr(keys), _ptr(table), table.numel(), _ptr(fresh), _ptr(mask), _ptr(status), n,
+            1 if insert else 0)
     return fresh
 
 
@@ -621,8 +603,7 @@ def slice_rank(state) -> torch.Tensor:
     (== get_rank per game, utils.py:134-140, which sums torch.linalg.matrix_rank over slices)."""
     B, S, stride = _state_layout(state, "state")
     out = torch.empty((B,), dtype=torch.int32, device=state.device)
-    with torch.cuda.device(state.device):
-        call("tg_rank_i32", _ptr(state), _ptr(out), B, S, stride, _stream(state.device))
+    _launch(state.device, "tg_rank_i32", _ptr(state), _ptr(out), B, S, stride)
     return out
 
 
@@ -645,12 +626,9 @@ def debug_handovers(device="cuda:0") -> int:
 
 # ---- batched MCTS (include/tensor_game_search.h) ---------------------------------------------------------------
 
-_SEARCH_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-
 
 def _search_call(name: str, forest, *args) -> None:
-    with torch.cuda.device(forest.device):
-        call(name, C.byref(forest.desc), *args, _stream(forest.device))
+    _launch(forest.device, name, C.byref(forest.desc), *args)
 
 
 def search_reset(forest, states, n_sim: int) -> None:
@@ -670,10 +648,10 @@ def search_select(forest, model_in=None, scalars=None) -> None:
     code = 0
     if model_in is not None:
         want = (forest.B, forest.T, forest.S, forest.S, forest.S)
-        if model_in.dtype not in _SEARCH_DTYPES or tuple(model_in.shape) != want or not model_in.is_contiguous() \
+        if model_in.dtype not in _FLOAT_DTYPES or tuple(model_in.shape) != want or not model_in.is_contiguous() \
                 or model_in.device != forest.device:
             raise TensorGameError("search_select", -1, f"model_in must be contiguous float32/float16/bfloat16 {want}")
-        code = _SEARCH_DTYPES[model_in.dtype]
+        code = _FLOAT_DTYPES[model_in.dtype]
     scalars = _flag(scalars, (forest.B, 1), torch.float32, forest.device, "scalars")
     _search_call("tg_search_select", forest, _ptr(model_in), code, _ptr(scalars))
 
@@ -697,9 +675,7 @@ def search_advance(forest, n_sim: int) -> None:
 def search_policy(forest, n_logits: int, n_bar: int, out=None) -> torch.Tensor:
     """Improved policy float32 (B, max_actions, 3S, n_logits) of every move played (tg_search_policy)."""
     shape = (forest.B, forest.max_actions, 3 * forest.S, n_logits)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=forest.device)
-    out = _flag(out, shape, torch.float32, forest.device, "out")
+    out = _out(out, shape, torch.float32, forest.device, "out")
     _search_call("tg_search_policy", forest, _ptr(out), int(n_logits), int(n_bar))
     return out
 
@@ -731,9 +707,8 @@ def replay_add(buf, states, policy, rewards, lengths, select: bool = False, stat
     lengths = _flag(lengths, (B,), torch.int64, dev, "lengths")
     status = _flag(status, (1,), torch.uint32, dev, "status")
     states, policy = states.contiguous(), policy.contiguous()
-    with torch.cuda.device(dev):
-        call("tg_replay_add", C.byref(buf.desc), _ptr(states), _ptr(policy), int(n_logits), _ptr(rewards),
-             _ptr(lengths), B, 1 if select else 0, _ptr(status), _stream(dev))
+    _launch(dev, "tg_replay_add", C.byref(buf.desc), _ptr(states), _ptr(policy), int(n_logits), _ptr(rewards),
+            _ptr(lengths), B, 1 if select else 0, _ptr(status))
 
 
 def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=None, best=None, kind=None, src=None,
@@ -748,11 +723,7 @@ def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=
     played / best rows are PlayedGamesDataset.__getitem__ (scalar = the move index).  A bad row is all zero and sets
     bit 0 of ``status`` uint32 (1,); ``overflow`` uint8 (N,) as ``demo_items``.  No host sync."""
     dev = torch.device(device)
-    _need_gpu(idx, "idx")
-    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev:
-        raise TensorGameError("replay_items", -1, f"idx must be int64 (N,) on {dev}, got {idx.dtype} "
-                              f"{tuple(idx.shape)} on {idx.device}")
-    idx = idx if idx.is_contiguous() else idx.contiguous()
+    idx = _item_idx(idx, dev, "replay_items")
     N = idx.shape[0]
     if (tokens is None) != (targets is None):
         raise TensorGameError("replay_items", -1, "pass both tokens and targets, or neither")
@@ -784,29 +755,13 @@ def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=
         if direct_kind not in (0, 1, 2):
             raise TensorGameError("replay_items", -1, "without an epoch table direct_kind must be 0, 1 or 2")
         len_data, code = 0, int(direct_kind)
-    if dtype not in _ITEM_DTYPES:
-        raise TensorGameError("replay_items", -1, "dtype must be float32, float16, bfloat16 or int8")
-    if out is None:
-        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
-    if out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
-        raise TensorGameError("replay_items", -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
-    if scalars is None:
-        scalars = torch.empty((N, 1), dtype=torch.float32, device=dev)
-    if actions is None:
-        actions = torch.empty((N, 3 * S), dtype=torch.int8, device=dev)
-    if rewards is None:
-        rewards = torch.empty((N, 1), dtype=torch.float32, device=dev)
-    scalars = _flag(scalars, (N, 1), torch.float32, dev, "scalars")
-    actions = _flag(actions, (N, 3 * S), torch.int8, dev, "actions")
-    rewards = _flag(rewards, (N, 1), torch.float32, dev, "rewards")
-    overflow = _flag(overflow, (N,), torch.uint8, dev, "overflow")
-    status = _flag(status, (1,), torch.uint32, dev, "status")
+    dcode, out, scalars, actions, rewards, overflow, status = _item_outputs(
+        N, T, S, dtype, dev, "replay_items", out, scalars, actions, rewards, overflow, status)
     pdesc = None if played is None else C.byref(played.desc)
     bdesc = None if best is None else C.byref(best.desc)
-    with torch.cuda.device(dev):
-        call("tg_replay_items", _ptr(tokens), _ptr(targets), n_demos, R, S, stride, int(shift), pdesc, bdesc,
-             _ptr(kind), _ptr(src), len_data, code, _ptr(idx), N, int(T), _ITEM_DTYPES[dtype], _ptr(out),
-             _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), _stream(dev))
+    _launch(dev, "tg_replay_items", _ptr(tokens), _ptr(targets), n_demos, R, S, stride, int(shift), pdesc, bdesc,
+            _ptr(kind), _ptr(src), len_data, code, _ptr(idx), N, int(T), dcode, _ptr(out),
+            _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status))
     return out, scalars, actions, rewards
 
 
@@ -843,31 +798,33 @@ def _net_mask(flags, need: int, B: int, dev, name: str) -> Optional[torch.Tensor
     return _flag(flags, (B,), torch.uint8, dev, "flags")
 
 
+def _net_frames(cfg, frames, dev, fn: str) -> int:
+    """B of the network's input frames: float32 or int8 (B,T,S,S,S) with the T and S of ``cfg``, on ``dev``."""
+    B = frames.shape[0] if frames.dim() == 5 else -1
+    want = (B, cfg.T, cfg.S, cfg.S, cfg.S)
+    if frames.dtype not in (torch.float32, torch.int8) or tuple(frames.shape) != want or frames.device != dev:
+        raise TensorGameError(fn, -1, f"frames must be float32 or int8 (B,T,S,S,S) = {want[1:]} per game on "
+                              f"{dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    return B
+
+
 def net_torso(cfg, w, frames, scalars, out=None, flags=None, need: int = 0) -> torch.Tensor:
     """Torso.forward (tg_net_torso): frames (B,T,S,S,S) float32 or int8, scalars float32 (B,dim_s) -> ee float32
     (B,3S^2,c).  With ``flags`` uint8 (B,) only the rows with ``(flags & need) == need`` are computed
     (tg_net_torso_masked): a given ``out`` keeps its other rows, an allocated one holds zeros there."""
     dev = _net_blob(cfg, w)
     _need_gpu(frames, "frames")
-    B = frames.shape[0] if frames.dim() == 5 else -1
-    want = (B, cfg.T, cfg.S, cfg.S, cfg.S)
-    if frames.dtype not in (torch.float32, torch.int8) or tuple(frames.shape) != want or frames.device != dev:
-        raise TensorGameError("net_torso", -1, f"frames must be float32 or int8 (B,T,S,S,S) = {want[1:]} per game on "
-                              f"{dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    B = _net_frames(cfg, frames, dev, "net_torso")
     frames = frames.contiguous()
     scalars = _flag(scalars.contiguous(), (B, cfg.dim_s), torch.float32, dev, "scalars")
     shape = (B, 3 * cfg.S * cfg.S, cfg.c)
     flags = _net_mask(flags, need, B, dev, "net_torso")
-    if out is None:
-        out = (torch.empty if flags is None else torch.zeros)(shape, dtype=torch.float32, device=dev)
-    out = _flag(out, shape, torch.float32, dev, "out")
-    i8 = 1 if frames.dtype == torch.int8 else 0
-    with torch.cuda.device(dev):
-        if flags is None:
-            call("tg_net_torso", C.byref(cfg), _ptr(w), _ptr(frames), i8, _ptr(scalars), _ptr(out), B, _stream(dev))
-        else:
-            call("tg_net_torso_masked", C.byref(cfg), _ptr(w), _ptr(frames), i8, _ptr(scalars), _ptr(out), B, _ptr(flags),
-                 int(need), _stream(dev))
+    out = _out(out, shape, torch.float32, dev, "out", torch.empty if flags is None else torch.zeros)
+    args = (C.byref(cfg), _ptr(w), _ptr(frames), 1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(out), B)
+    if flags is None:
+        _launch(dev, "tg_net_torso", *args)
+    else:
+        _launch(dev, "tg_net_torso_masked", *args, _ptr(flags), int(need))
     return out
 
 
@@ -885,22 +842,15 @@ def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None
     ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
     rows = _flag(rows, (B,), torch.int64, dev, "rows")
     uniforms = _flag(uniforms, (B, k, cfg.n_steps), torch.float32, dev, "uniforms")
-    if tokens is None:
-        tokens = new((B, k, cfg.n_steps), dtype=torch.int8, device=dev)
-    if probs is None:
-        probs = new((B, k), dtype=torch.float32, device=dev)
-    if q is None:
-        q = new((B,), dtype=torch.float32, device=dev)
-    tokens = _flag(tokens, (B, k, cfg.n_steps), torch.int8, dev, "tokens")
-    probs = _flag(probs, (B, k), torch.float32, dev, "probs")
-    q = _flag(q, (B,), torch.float32, dev, "q")
-    args = (C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), int(seed) & (2 ** 64 - 1),
-            int(call_idx) & (2 ** 64 - 1), _ptr(uniforms), _ptr(tokens), _ptr(probs), _ptr(q))
-    with torch.cuda.device(dev):
-        if flags is None:
-            call("tg_net_sample", *args, _stream(dev))
-        else:
-            call("tg_net_sample_masked", *args, _ptr(flags), int(need), _stream(dev))
+    tokens = _out(tokens, (B, k, cfg.n_steps), torch.int8, dev, "tokens", new)
+    probs = _out(probs, (B, k), torch.float32, dev, "probs", new)
+    q = _out(q, (B,), torch.float32, dev, "q", new)
+    args = (C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), _u64(seed), _u64(call_idx), _ptr(uniforms),
+            _ptr(tokens), _ptr(probs), _ptr(q))
+    if flags is None:
+        _launch(dev, "tg_net_sample", *args)
+    else:
+        _launch(dev, "tg_net_sample_masked", *args, _ptr(flags), int(need))
     return tokens, probs, q
 
 
@@ -919,9 +869,7 @@ def net_logits(cfg, w, ee, g_action):
     oo = torch.empty((B, cfg.n_steps, cfg.n_logits), dtype=torch.float32, device=dev)
     zz0 = torch.empty((B, cfg.W), dtype=torch.float32, device=dev)
     q = torch.empty((B, cfg.n_quantile), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        call("tg_net_logits", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q),
-             _stream(dev))
+    _launch(dev, "tg_net_logits", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q))
     return oo, zz0, q
 
 
@@ -948,11 +896,7 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
     net_train_workspace_size bytes.  grad (like theta) None means a loss-only call.  keep_in / keep_out: uint8
     (B, blocks, 2, n_steps, W) or None.  Returns (losses float32 [2], status int32 [1]); no host sync."""
     dev = _net_blob(cfg, theta)
-    B = frames.shape[0] if frames.dim() == 5 else -1
-    want = (B, cfg.T, cfg.S, cfg.S, cfg.S)
-    if frames.dtype not in (torch.float32, torch.int8) or tuple(frames.shape) != want or frames.device != dev:
-        raise TensorGameError("net_loss_grad", -1, f"frames must be float32 or int8 (B,T,S,S,S) = {want[1:]} per game "
-                              f"on {dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    B = _net_frames(cfg, frames, dev, "net_loss_grad")
     if B < 1:
         raise TensorGameError("net_loss_grad", -1, "B must be at least 1")
     if not 0.0 <= float(dropout_p) < 1.0:
@@ -965,26 +909,19 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
     mask = (B, cfg.blocks, 2, cfg.n_steps, cfg.W)
     keep_in = _flag(keep_in, mask, torch.uint8, dev, "keep_in")
     keep_out = _flag(keep_out, mask, torch.uint8, dev, "keep_out")
-    if grad is not None:
-        grad = _flag(grad, tuple(theta.shape), torch.float32, dev, "grad")
-    if losses is None:
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-    if status is None:
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-    losses = _flag(losses, (2,), torch.float32, dev, "losses")
-    status = _flag(status, (1,), torch.int32, dev, "status")
+    grad = _flag(grad, tuple(theta.shape), torch.float32, dev, "grad")
+    losses = _out(losses, (2,), torch.float32, dev, "losses")
+    status = _out(status, (1,), torch.int32, dev, "status")
     need = net_train_workspace_size(cfg, B)
     _need_gpu(workspace, "workspace")
     if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
             workspace.numel() < need or workspace.device != dev:
         raise TensorGameError("net_loss_grad", -1, f"workspace must be contiguous uint8 of at least {need} bytes on "
                               f"{dev}, got {workspace.dtype} {tuple(workspace.shape)} on {workspace.device}")
-    with torch.cuda.device(dev):
-        call("tg_net_loss_grad", C.byref(cfg), _ptr(theta), _ptr(pos_fix), _ptr(frames),
-             1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(g_action), _ptr(g_value), B,
-             float(weight_pol), float(weight_val), float(dropout_p), int(seed) & (2 ** 64 - 1),
-             int(call_idx) & (2 ** 64 - 1), _ptr(keep_in), _ptr(keep_out), _ptr(workspace), workspace.numel(),
-             _ptr(grad), _ptr(losses), _ptr(status), _stream(dev))
+    _launch(dev, "tg_net_loss_grad", C.byref(cfg), _ptr(theta), _ptr(pos_fix), _ptr(frames),
+            1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(g_action), _ptr(g_value), B,
+            float(weight_pol), float(weight_val), float(dropout_p), _u64(seed), _u64(call_idx), _ptr(keep_in),
+            _ptr(keep_out), _ptr(workspace), workspace.numel(), _ptr(grad), _ptr(losses), _ptr(status))
     return losses, status
 
 
@@ -1039,9 +976,7 @@ def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nn
         max_actions = actions.shape[1] if actions.dim() == 3 else -1
         actions = _flag(actions, (B, max_actions, 3 * S), torch.int8, dev, "actions")
     rollout_check(B, n, S, T, dim_s, step, max_actions, actions is not None)
-    if nnz is None:
-        nnz = (torch.zeros if stop_solved else torch.empty)((B,), dtype=torch.int32, device=dev)
-    nnz = _flag(nnz, (B,), torch.int32, dev, "nnz")
+    nnz = _out(nnz, (B,), torch.int32, dev, "nnz", torch.zeros if stop_solved else torch.empty)
     overflow = _flag(overflow, (B,), torch.uint8, dev, "overflow")
     active = _flag(active, (B,), torch.uint8, dev, "active")
     if len(records) != 4:
@@ -1050,12 +985,10 @@ def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nn
            for r, name in zip(records, ("best_nnz", "hits", "solved_step", "solved_sample"))]
     if any(r is None for r in rec):
         raise TensorGameError("rollout_advance", -1, "records must be four int32 tensors (ops.rollout_records)")
+    ptrs = (_ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow), *map(_ptr, rec), _ptr(actions))
     sizes = (B, int(n), S, T, dim_s, int(step), max_actions, int(shift))
-    with torch.cuda.device(dev):
-        if stop_solved:
-            call("tg_rollout_advance_masked", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow),
-                 *map(_ptr, rec), _ptr(actions), _ptr(active), *sizes, _stream(dev))
-        else:
-            call("tg_rollout_advance", _ptr(frames), _ptr(tokens), _ptr(scalars), _ptr(nnz), _ptr(overflow),
-                 *map(_ptr, rec), _ptr(actions), *sizes, _stream(dev))
+    if stop_solved:
+        _launch(dev, "tg_rollout_advance_masked", *ptrs, _ptr(active), *sizes)
+    else:
+        _launch(dev, "tg_rollout_advance", *ptrs, *sizes)
     return nnz
