@@ -6,6 +6,9 @@ configurations of net_ref and net_s9_ref, and a restatement of the kernels' LDS 
   share one value of: decoder rows per workgroup R < 8 and a partial last chunk, k > 8, torso_d != d, torso_heads !=
   heads, ff != 4W, dim_s > 1, W % 4 != 0, n_quantile != 8, n_logits 1 and 8, every dimension 1, every bound, the S = 9
   training torso in one chunk, and the training decoder plan at the LDS limit;
+* ``CHUNKED``: three more S = 9 training rows, apart from ``FAMILY``, whose training torso runs a partial last chunk
+  (5 + 4 and 2 + 2 + 2 + 2 + 1 sequences) or nine chunks of one, the plan tg_net_train_check compares with 160 KiB;
+  ``train_config(name)`` finds a training row's configuration by name in net_ref, net_s9_ref, ``FAMILY`` or ``CHUNKED``;
 * the LDS plans in floats, as tg_net.hip (``torso_plan``, ``dec_plan``) and tg_train.hip (``scr_plan``,
   ``scr_plan_kv``, ``tplan``, ``dplan``, ``dplan_kv``) lay them out, and what the host code derives from them:
   ``decoder_rows`` (launch_decode's R), ``torso_chunk`` (the S = 9 training torso's sequences per chunk) and the byte
@@ -13,7 +16,8 @@ configurations of net_ref and net_s9_ref, and a restatement of the kernels' LDS 
 """
 from typing import NamedTuple
 
-from net_ref import FIELDS, dims
+from net_ref import CONFIGS, FIELDS, dims
+from net_s9_ref import CONFIGS as CONFIGS_S9
 
 LDS = 160 * 1024      # bytes of dynamic LDS per workgroup (gfx950)
 MAX_LOGITS = 8        # TG_NET_MAX_LOGITS: the decoder's logits stride
@@ -53,6 +57,27 @@ FAMILY = {
     "r1_9": Row(dict(_R2_9, c=24), False, 8),
 }
 REFERENCE_ROWS = ("e", "f", "g")  # recorded by tests/golden/make_golden_net_family.py
+
+# S = 9 rows by the training torso's sequences per chunk (c and torso_d set the chunk; the plans depend on neither
+# torso_layers nor torso_heads).  c1 sits just inside 160 KiB in both families.
+_C9 = dict(S=9, T=4, dim_s=1, torso_layers=2, torso_heads=2, torso_ff=16, W=8, heads=1, d=8, ff=16, blocks=1, n_steps=5,
+           n_logits=3, n_hidden=16, n_quantile=8)
+CHUNKED = {
+    "c5": Row(dict(_C9, c=4, torso_d=16), True, 4),   # chunks of 5, 4
+    "c2": Row(dict(_C9, c=24, torso_d=8), True, 4),   # chunks of 2, 2, 2, 2, 1
+    "c1": Row(dict(_C9, c=32, torso_d=8), True, 4),   # nine chunks of 1
+}
+CHUNKS = {"c5": 5, "c2": 2, "c1": 1}                  # torso_chunk of each
+
+
+def train_config(name):
+    """The configuration (either form of net_ref.dims) of the training row ``name``."""
+    for table in (CONFIGS, CONFIGS_S9):
+        if name in table:
+            return table[name]
+    row = FAMILY[name] if name in FAMILY else CHUNKED[name]
+    assert row.train, name
+    return row.cfg
 
 
 # ---- tg_net.hip ------------------------------------------------------------------------------------------------------
@@ -164,6 +189,6 @@ def fits(nbytes):
     return all(b <= LDS for b in nbytes)
 
 
-__all__ = ["FAMILY", "REFERENCE_ROWS", "Row", "LDS", "dims", "torso_plan", "dec_plan", "decoder_rows",
-           "inference_bytes", "scr_plan", "scr_plan_kv", "tplan", "dplan", "dplan_kv", "torso_chunk",
-           "training_bytes", "fits"]
+__all__ = ["FAMILY", "CHUNKED", "CHUNKS", "train_config", "REFERENCE_ROWS", "Row", "LDS", "dims", "torso_plan",
+           "dec_plan", "decoder_rows", "inference_bytes", "scr_plan", "scr_plan_kv", "tplan", "dplan", "dplan_kv",
+           "torso_chunk", "training_bytes", "fits"]

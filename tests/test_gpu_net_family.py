@@ -6,7 +6,7 @@ at W % 4 != 0); bitwise reproducible gradients; FusedTrainer's inference blob af
 
 Bounds are the suite's: 1e-5 * max(1, max |ref|) per inference tensor and 1e-4 per training tensor.  Where the eager
 float32 restatement of the same inputs itself misses that bound against float64, the tensor's bound is twice that
-eager float32 error, computed here (``within``); the rows and tensors that used it are printed (run with -s), as are
+eager float32 error, computed here (``train_ref.within``); the rows and tensors that used it are printed (run with -s), as are
 the worst errors per row."""
 import functools
 from pathlib import Path
@@ -21,7 +21,7 @@ from mat_mul_amd.train import unpack_weights
 
 import net_family as F
 from net_ref import P, Ref, dims, make_inputs, make_weights, philox_uniforms, pick
-from train_ref import TrainRef, keep_mask, make_batch, multipliers
+from train_ref import TrainRef, err, keep_mask, make_batch, multipliers, within
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -70,24 +70,6 @@ def host(name, B, dtype=torch.float64):
     oo, zz0, q = ref.teacher(ee, ga)
     return {k: v.detach().cpu().double().numpy()
             for k, v in (("ee", ee), ("oo", oo), ("zz0", zz0), ("q", q), ("qq", Ref.risk(q)))}
-
-
-def err(got, ref):
-    got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
-    return float(np.abs(got - ref).max())
-
-
-def within(e, tol, ref, f32_err, what):
-    """e <= tol * max(1, max |ref|), or, where the eager float32 restatement's error f32_err() misses that bound too,
-    e <= twice that error."""
-    b = tol * max(1.0, float(np.abs(ref).max()))
-    if e <= b:
-        return True
-    e32 = f32_err()
-    if e32 < b:
-        return False
-    print(f"FAMILY-F32-BOUND {what}: error {e:.3g}, eager float32 {e32:.3g} >= {b:.3g}")
-    return e <= 2.0 * e32
 
 
 def net(name, k=None):

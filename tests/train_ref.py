@@ -4,7 +4,11 @@
   ``AlphaTensor.fwd_train`` (the policy cross entropy summed, the quantile loss averaged) and their gradient by torch
   autograd, in float64 (or float32 for the eager stand-in of tools/train_bench.py);
 * ``keep_mask``: the header's dropout keep rule restated on the host (Philox from oracle.tensor_game);
-* ``make_batch``: states, scalars, actions and rewards for a configuration.
+* ``make_batch``: states, scalars, actions and rewards for a configuration; ``two_sided_rewards`` and
+  ``two_sided_batch``: rewards on both sides of the random networks' quantiles, inside and outside the Huber kink;
+  ``bad_tokens``: a batch's actions with out-of-range entries and the rows that hold them;
+* ``value_branches``: how a batch's (game, quantile) pairs fall on the quantile loss's four branches;
+* ``err`` and ``within``: the suite's per-tensor bound.
 """
 import numpy as np
 import torch
@@ -38,17 +42,39 @@ class TrainRef(Ref):
             x = xb + (c2 if masks is None else c2 * masks[:, b, 1])
         return self._lin(torch.relu(x), P + "li1"), x
 
-    def losses(self, xx, ss, g_action, g_value, masks=None):
-        """(l_pol, l_val) of AlphaTensor.fwd_train for g_action int (B,n_steps), g_value (B,1)."""
+    def forward(self, xx, ss, g_action, masks=None):
+        """(logits (B,n_steps,n_logits), value quantiles (B,n_quantile)) of the teacher-forced decoder on START followed
+        by g_action shifted by one; an input token outside [0, n_logits) reads as START."""
         g = torch.as_tensor(g_action, device=self.device).long()
-        gv = torch.as_tensor(g_value, device=self.device).to(self.dtype).reshape(-1, 1)
         if masks is not None:
             masks = torch.as_tensor(masks, device=self.device).to(self.dtype)
         ee = self.torso(xx, ss)
-        start = torch.full((g.shape[0], 1), self.m["n_logits"], dtype=torch.long, device=self.device)
-        oo, x = self.decode_masked(ee, torch.cat([start, g[:, :-1]], 1), masks)
-        l_pol = torch.nn.functional.cross_entropy(oo.reshape(-1, self.m["n_logits"]), g.reshape(-1), reduction="sum")
-        q = self.value(x[:, 0])
+        NL = self.m["n_logits"]
+        start = torch.full((g.shape[0], 1), NL, dtype=torch.long, device=self.device)
+        tin = torch.cat([start, g[:, :-1]], 1)
+        tin = torch.where((tin >= 0) & (tin <= NL), tin, torch.full_like(tin, NL))
+        oo, x = self.decode_masked(ee, tin, masks)
+        return oo, self.value(x[:, 0])
+
+    def losses(self, xx, ss, g_action, g_value, masks=None, skip_rows=None):
+        """(l_pol, l_val) of AlphaTensor.fwd_train for g_action int (B,n_steps), g_value (B,1).  The rows of skip_rows
+        (bool (B,), the header's rows with a token outside [0, n_logits)) add nothing to l_pol and count in l_val."""
+        g = torch.as_tensor(g_action, device=self.device).long()
+        gv = torch.as_tensor(g_value, device=self.device).to(self.dtype).reshape(-1, 1)
+        oo, q = self.forward(xx, ss, g_action, masks)
+        NL = self.m["n_logits"]
+        if skip_rows is None:
+            l_pol = torch.nn.functional.cross_entropy(oo.reshape(-1, NL), g.reshape(-1), reduction="sum")
+        else:
+            skip = torch.as_tensor(np.asarray(skip_rows, bool), device=self.device)
+            tgt = torch.where(skip[:, None], torch.zeros_like(g), g)  # a skipped row's targets are never used
+            ce = torch.nn.functional.cross_entropy(oo.reshape(-1, NL), tgt.reshape(-1), reduction="none")
+            l_pol = (ce.reshape(g.shape) * (~skip)[:, None].to(self.dtype)).sum()
+        return l_pol, self.quantile_loss(q, gv)
+
+    def quantile_loss(self, q, gv):
+        """The reference's quantile_loss of quantiles q (B,n_quantile) against gv (B,1): the mean of huber(gv - q_j) *
+        |tau_j - 1[gv - q_j > 0]|."""
         n = q.shape[-1]
         # the quantile levels and their weights in float32, as the reference's quantile_loss forms them (exact when n
         # is a power of two)
@@ -57,13 +83,13 @@ class TrainRef(Ref):
         ad = dd.abs()
         hh = torch.where(ad < 1.0, 0.5 * dd * dd, ad - 0.5)
         kk = (tau - (dd > 0).float()).abs().to(self.dtype)
-        return l_pol, (hh * kk).mean()
+        return (hh * kk).mean()
 
-    def loss_grad(self, xx, ss, g_action, g_value, masks=None, weight_pol=1.0, weight_val=1000.0):
+    def loss_grad(self, xx, ss, g_action, g_value, masks=None, weight_pol=1.0, weight_val=1000.0, skip_rows=None):
         """(l_pol, l_val, {name: gradient of weight_pol * l_pol + weight_val * l_val}) as float64 numpy values."""
         for v in self.w.values():
             v.grad = None
-        l_pol, l_val = self.losses(xx, ss, g_action, g_value, masks)
+        l_pol, l_val = self.losses(xx, ss, g_action, g_value, masks, skip_rows)
         (weight_pol * l_pol + weight_val * l_val).backward()
         grads = {k: v.grad.detach().cpu().numpy().astype(np.float64) for k, v in self.w.items() if v.requires_grad}
         return l_pol.item(), l_val.item(), grads
@@ -105,10 +131,75 @@ def make_batch(cfg, B, seed):
     return xx, ss, aa, rr
 
 
+def two_sided_rewards(B, seed):
+    """float32 rewards (B,1) uniform in [-1.5, 1.5]: on both sides of the random networks' quantiles (about +-0.2), and
+    on both sides of the Huber kink |g_value - q| = 1."""
+    return np.random.default_rng(seed).uniform(-1.5, 1.5, size=(B, 1)).astype(np.float32)
+
+
+def two_sided_batch(cfg, B, seed):
+    """make_batch(cfg, B, seed) with two_sided_rewards(B, seed) in place of its integer rewards."""
+    xx, ss, aa, _ = make_batch(cfg, B, seed)
+    return xx, ss, aa, two_sided_rewards(B, seed)
+
+
+def bad_tokens(aa, n_logits):
+    """(actions, skip_rows) for int8 actions aa (B >= 300, n_steps): n_logits at position 0 of row 5, 127 at the last
+    position of row 6 (never a decoder input; rows 5 and 6 share a partial slab at B = 300), -128 mid-row in row 200
+    and -1 in row 299."""
+    bad = aa.copy()
+    n = aa.shape[1]
+    bad[5, 0] = n_logits
+    bad[6, n - 1] = 127
+    bad[200, n // 2] = -128
+    bad[299, min(1, n - 1)] = -1
+    skip = np.zeros(aa.shape[0], bool)
+    skip[[5, 6, 200, 299]] = True
+    return bad, skip
+
+
+def value_branches(ref, xx, ss, g_action, g_value):
+    """Of d = g_value - q over the B * n_quantile pairs of ``ref`` (a float64 TrainRef): the shares of the four classes
+    {quadratic |d| < 1, linear} x {d > 0, d <= 0} as a dict, and the distance of the nearest pair to a branch change,
+    min(min |d|, min ||d| - 1|)."""
+    with torch.no_grad():
+        _, q = ref.forward(xx, ss, g_action)
+    d = (torch.as_tensor(g_value, device=q.device).to(q.dtype).reshape(-1, 1) - q).cpu().numpy()
+    quad, pos = np.abs(d) < 1.0, d > 0
+    shares = {("quad", "pos"): float((quad & pos).mean()), ("quad", "neg"): float((quad & ~pos).mean()),
+              ("lin", "pos"): float((~quad & pos).mean()), ("lin", "neg"): float((~quad & ~pos).mean())}
+    return shares, float(min(np.abs(d).min(), np.abs(np.abs(d) - 1.0).min()))
+
+
 def rel_err(got, ref):
     """max |got - ref| / max(1, max |ref|)."""
     ref = np.asarray(ref, np.float64)
     return float(np.abs(np.asarray(got, np.float64) - ref).max() / max(1.0, float(np.abs(ref).max())))
 
 
-__all__ = ["TrainRef", "keep_mask", "multipliers", "make_batch", "rel_err"]
+def err(got, ref):
+    """max |got - ref|."""
+    got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
+    return float(np.abs(got - ref).max())
+
+
+def bound(tol, ref):
+    """The suite's bound of a tensor: tol * max(1, max |ref|)."""
+    return tol * max(1.0, float(np.abs(ref).max()))
+
+
+def within(e, tol, ref, f32_err, what):
+    """e <= tol * max(1, max |ref|), or, where the eager float32 restatement's error f32_err() misses that bound too,
+    e <= twice that error."""
+    b = bound(tol, ref)
+    if e <= b:
+        return True
+    e32 = f32_err()
+    if e32 < b:
+        return False
+    print(f"FAMILY-F32-BOUND {what}: error {e:.3g}, eager float32 {e32:.3g} >= {b:.3g}")
+    return e <= 2.0 * e32
+
+
+__all__ = ["TrainRef", "keep_mask", "multipliers", "make_batch", "two_sided_rewards", "two_sided_batch", "bad_tokens",
+           "value_branches", "rel_err", "err", "bound", "within"]
