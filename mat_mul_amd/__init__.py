@@ -16,7 +16,7 @@ __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
            "FusedAlphaTensor", "net", "FusedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult",
-           "solve_states"]
+           "solve_states", "solve_stream"]
 
 _SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout"}
 _ATTRS = {
@@ -33,6 +33,7 @@ _ATTRS = {
     "sample_rollouts": "rollout",
     "RolloutResult": "rollout",
     "solve_states": "rollout",
+    "solve_stream": "rollout",
 }
 
 

@@ -136,6 +136,13 @@ ROLLOUT_MASKED_SIGNATURES = {
     "tg_rollout_advance_masked": ROLLOUT_SIGNATURES["tg_rollout_advance"][:10] + [_p] +
                                  ROLLOUT_SIGNATURES["tg_rollout_advance"][10:],
 }
+# name -> argtypes; every symbol include/tensor_game_rollout_slots.h declares
+ROLLOUT_SLOTS_SIGNATURES = {
+    # the masked entry with (slot_state, slot_step) behind `active` and without the host `step`
+    "tg_rollout_advance_slots": [_p] * 13 + [_i64, _i, _i, _i, _i, _i, _i, _p],
+    "tg_rollout_refill": [_p, _p, _i64, _p, _i64, _u64, _i] + [_p] * 21 + [_i64, _i, _i, _i, _i, _i, _p],
+}
+TG_ROLLOUT_MAX_SLOTS = 65536
 TG_NET_TRAIN_PARTIALS = 256
 TG_TRAIN_STATUS_BAD_TOKEN = 1
 
@@ -186,7 +193,7 @@ def _load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
                            **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES,
-                           **ROLLOUT_MASKED_SIGNATURES}.items():
+                           **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

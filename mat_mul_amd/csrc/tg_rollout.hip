@@ -17,9 +17,17 @@
 // without a barrier.  Of an inactive group nothing else is read and nothing is written; the activity of the groups lives
 // in LDS from the first barrier on, because the records change while the rows are written back.  M = false is the plain
 // entry: the same code with every test of the mask compiled out.
+//
+// Slots (include/tensor_game_rollout_slots.h, tg_rollout_advance_slots, mode 2): the masked step with the activity of a
+// group read from three words (slot_state, solved_step, slot_step) and the step index per group: both go to LDS
+// before one extra barrier, so everything behind it is the masked code with `step` looked up per group.  The body is
+// one text, tg_rollout_body.h, included into rollout_advance_kernel<W, M> (Q = false: the code objects of its four
+// instantiations are unchanged) and into rollout_advance_slots_kernel<W>, whose argument block carries the two extra
+// pointers.  tg_rollout_refill (a one-workgroup plan kernel with a block scan, then one workgroup per
+// slot) is at the end of the file.
 #include <hip/hip_runtime.h>
 
-#include "../../include/tensor_game_rollout.h"  // and, through it, tensor_game_rollout_masked.h
+#include "../../include/tensor_game_rollout_slots.h"  // and, through it, tensor_game_rollout[_masked].h
 #include "tg_host.h"
 
 namespace tg {
@@ -42,6 +50,11 @@ struct RolloutArgs {
   int gpw;          // groups per workgroup
   int ipr;          // items per row (the tail item included)
   int words;        // 1: tokens and actions move as aligned dwords (S % 4 == 0, 4-byte aligned pointers)
+};
+
+struct RolloutSlotArgs : RolloutArgs {
+  const int64_t* slot_state;  // (G)
+  int32_t* slot_step;         // (G)
 };
 
 struct __attribute__((packed)) RollU32 { uint32_t v; };
@@ -74,141 +87,176 @@ __device__ __forceinline__ void roll_store(int8_t* p, int nb, const uint32_t (&q
   }
 }
 
+__device__ __forceinline__ const int64_t* slot_state_of(const RolloutArgs&) { return nullptr; }
+__device__ __forceinline__ int32_t* slot_step_of(const RolloutArgs&) { return nullptr; }
+__device__ __forceinline__ const int64_t* slot_state_of(const RolloutSlotArgs& a) { return a.slot_state; }
+__device__ __forceinline__ int32_t* slot_step_of(const RolloutSlotArgs& a) { return a.slot_step; }
+
 template <int W, bool M>
 __global__ __launch_bounds__(kBlock) void rollout_advance_kernel(const RolloutArgs a) {
-  __shared__ __attribute__((aligned(16))) int8_t s_tok[kRollTokBytes];
-  __shared__ int s_nnz[kRollMaxRows];
-  __shared__ int s_ovf[kRollMaxRows];
-  __shared__ uint8_t s_act[M ? kRollMaxRows : 1];  // per group of the workgroup (at most one group per row)
-  const int tid = threadIdx.x;
-  const int S = a.S, S2 = S * S, N = S2 * S, A3 = 3 * S, T = a.T, n = a.n;
-  const int64_t g0 = static_cast<int64_t>(blockIdx.x) * a.gpw;
-  const int ng = static_cast<int>(a.G - g0 < a.gpw ? a.G - g0 : a.gpw);  // >= 1: the grid is ceil(G / gpw)
-  const int rows = ng * n;
-  const int64_t b0 = g0 * n;
-  bool mixed = false;  // some groups of this workgroup may be inactive: a workgroup of ONE group that goes on is active
-  if constexpr (M) {
-    bool any = false;
-    for (int base = 0; base < ng; base += 64) {  // every wave over all the groups: the same answer in each
-      const int lg = base + (tid & 63);
-      const bool act = lg < ng && a.solved_step[g0 + lg] < 0;
-      if (tid < 64 && lg < ng) s_act[lg] = act;
-      any |= act;
-    }
-    if (!__any(any)) return;
-    mixed = ng > 1;
-  }
+  constexpr bool Q = false;
+#include "tg_rollout_body.h"
+}
 
-  // ---- the rows' tokens into LDS (and into the record of played actions), scalars + 1, the counters cleared
-  if (a.words) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tokens + b0 * A3);
-    const int wpr = A3 / 4;
-    for (int x = tid; x < rows * wpr; x += kBlock) {
-      if (M && mixed && a.solved_step[g0 + x / wpr / n] >= 0) continue;
-      const uint32_t t = src[x];
-      reinterpret_cast<uint32_t*>(s_tok)[x] = t;
-      if (a.actions) {
-        const int r = x / wpr, c = x - r * wpr;
-        reinterpret_cast<uint32_t*>(a.actions + ((b0 + r) * a.max_actions + a.step) * A3)[c] = t;
-      }
-    }
-  } else {
-    const int8_t* src = a.tokens + b0 * A3;
-    for (int x = tid; x < rows * A3; x += kBlock) {
-      if (M && mixed && a.solved_step[g0 + x / A3 / n] >= 0) continue;
-      const int8_t t = src[x];
-      s_tok[x] = t;
-      if (a.actions) {
-        const int r = x / A3, c = x - r * A3;
-        a.actions[((b0 + r) * a.max_actions + a.step) * A3 + c] = t;
-      }
-    }
-  }
-  if (a.scalars) {
-    float* sc = a.scalars + b0 * a.dim_s;
-    for (int x = tid; x < rows * a.dim_s; x += kBlock) {
-      if (M && mixed && a.solved_step[g0 + x / a.dim_s / n] >= 0) continue;
-      sc[x] += 1.0f;
-    }
-  }
-  for (int r = tid; r < rows; r += kBlock) s_nnz[r] = 0, s_ovf[r] = 0;
+template <int W>
+__global__ __launch_bounds__(kBlock) void rollout_advance_slots_kernel(const RolloutSlotArgs a) {
+  constexpr bool M = true, Q = true;
+#include "tg_rollout_body.h"
+}
+
+// ---- tg_rollout_refill ------------------------------------------------------------------------------------------------
+constexpr int kRefillScan = 1024;  // threads of the plan kernel; each owns up to TG_ROLLOUT_MAX_SLOTS / kRefillScan slots
+
+struct RefillArgs {
+  const int8_t* q_states;
+  const float* q_scalars;
+  int64_t N;
+  int64_t* head;
+  int64_t first_state;
+  uint32_t seed_lo, seed_hi;
+  int n_uniforms;  // 0: no uniforms
+  int8_t* frames;
+  float* scalars;
+  int32_t* nnz;
+  uint8_t* overflow;
+  int32_t *best_nnz, *hits, *solved_step, *solved_sample;
+  const int8_t* actions;
+  uint8_t* active;
+  int64_t* slot_state;
+  int32_t* slot_step;
+  int32_t *out_best_nnz, *out_hits, *out_solved_step, *out_solved_sample;
+  uint8_t* out_overflow;
+  int8_t* out_tokens;
+  int64_t* rows;
+  float* uniforms;
+  int32_t* live;
+  int R;  // slots
+  int n, S, T, dim_s, max_actions;
+  int wide;  // 1: 16-byte copies of the frames
+};
+
+// 0: the slot keeps its state; 1: it is finished (flush, then take); 2: it is empty (take)
+__device__ __forceinline__ int slot_kind(const RefillArgs& a, int64_t g) {
+  if (a.slot_state[g] < 0) return 2;
+  return a.solved_step[g] >= 0 || a.slot_step[g] >= a.max_actions ? 1 : 0;
+}
+
+// The plan: in slot order, the j-th slot that wants a state gets head + j, or -1 when the queue is dry.  The answer
+// goes to rows[g * n], which the fill kernel reads before it writes the slot's row keys; head and live are updated.
+__global__ __launch_bounds__(kRefillScan) void rollout_refill_plan_kernel(const RefillArgs a) {
+  __shared__ int sh[kRefillScan];
+  const int t = threadIdx.x;
+  const int per = (a.R + kRefillScan - 1) / kRefillScan;  // <= 64
+  const int lo = min(t * per, a.R), hi = min(lo + per, a.R);
+  int64_t head = a.head[0];
+  head = head < 0 ? 0 : head > a.N ? a.N : head;
+  int want = 0;
+  for (int g = lo; g < hi; ++g) want += slot_kind(a, g) != 0;
+  sh[t] = want;
   __syncthreads();
+  for (int d = 1; d < kRefillScan; d <<= 1) {
+    const int add = t >= d ? sh[t - d] : 0;
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  const int64_t total = sh[kRefillScan - 1], avail = a.N - head;
+  int64_t j = sh[t] - want;
+  for (int g = lo; g < hi; ++g)
+    if (slot_kind(a, g) != 0) {
+      a.rows[static_cast<int64_t>(g) * a.n] = j < avail ? head + j : -1;
+      ++j;
+    }
+  if (t == 0) {  // every thread read head[0] before the first barrier
+    const int64_t taken = total < avail ? total : avail;
+    a.head[0] = head + taken;
+    a.live[0] = static_cast<int32_t>(a.R - total + taken);
+  }
+}
 
-  // ---- the items: new head, history shift, per-row counts
-  const int full = N / W;  // items of W whole bytes; item `full` (W == 4 only) is the N % 4 tail
-  const int nkeep = T > 1 ? T - 1 : 1;  // frames loaded: 0 .. T - 2 move back by one; T == 1 loads the head alone
-  const int total = rows * a.ipr;
-  for (int it = tid; it < total; it += kBlock) {
-    const int lr = it / a.ipr, c = it - lr * a.ipr;
-    if (M && mixed && !s_act[lr / n]) continue;
-    const int nb = c < full ? W : N - full * W;
-    const int e0 = c * W;
-    int8_t* const row = a.frames + (b0 + lr) * static_cast<int64_t>(T) * N + e0;
-    uint32_t fr[TG_NET_MAX_T][W / 4];
-#pragma unroll
-    for (int t = 0; t < TG_NET_MAX_T - 1; ++t)
-      if (t < nkeep) roll_load<W>(row + static_cast<int64_t>(t) * N, nb, fr[t]);
+// One workgroup per slot: flush a finished slot, fill a slot that takes a state, then active and the uniforms.
+__global__ __launch_bounds__(kBlock) void rollout_refill_fill_kernel(const RefillArgs a) {
+  const int tid = threadIdx.x, n = a.n, K = a.max_actions, A3 = 3 * a.S;
+  const int64_t g = blockIdx.x, b0 = g * n;
+  const int kind = slot_kind(a, g);
+  const int64_t old = a.slot_state[g];
+  const int step = a.slot_step[g], sstep = a.solved_step[g], ssample = a.solved_sample[g];
+  const int64_t q = kind ? a.rows[b0] : old;  // the state the slot holds from now on, < 0: none
+  __syncthreads();                            // all of the above is read by every thread before any of it is written
 
-    const int8_t* const tk = s_tok + lr * A3;
-    int i = e0 / S2, rem = e0 - i * S2, j = rem / S, l = rem - j * S;
-    uint32_t uv = static_cast<uint32_t>(tk[i] - a.shift) * static_cast<uint32_t>(tk[S + j] - a.shift);
-    uint32_t head[W / 4];
-    int ovf = 0, cnt = 0;
-#pragma unroll
-    for (int d = 0; d < W / 4; ++d) {
-      uint32_t out = 0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (4 * d + t < nb) {
-          const int p = static_cast<int>(uv * static_cast<uint32_t>(tk[2 * S + l] - a.shift));
-          const int nw = sbyte(fr[0][d], t) - p;  // 32-bit, then narrowed with wrap as tg_step_i8 does
-          ovf |= nw + 128;
-          out |= (static_cast<uint32_t>(nw) & 255u) << (8 * t);
-          if (++l == S) {  // the row (i, j) of the tensor ends inside the item: next factors (tk[S] / tk[2S] past the
-            l = 0;         // last element are in-row reads of v_0 / w_0 that are never used)
-            if (++j == S) j = 0, ++i;
-            uv = static_cast<uint32_t>(tk[i] - a.shift) * static_cast<uint32_t>(tk[S + j] - a.shift);
-          }
+  if (kind == 1 && old < a.N) {
+    if (tid == 0) {
+      a.out_best_nnz[old] = a.best_nnz[g];
+      a.out_hits[old] = a.hits[g];
+      a.out_solved_step[old] = sstep;
+      a.out_solved_sample[old] = ssample;
+      uint8_t ovf = 0;
+      for (int s = 0; s < n; ++s) ovf |= a.overflow[b0 + s];
+      a.out_overflow[old] = ovf ? 1 : 0;
+    }
+    const bool won = sstep >= 0 && sstep < K && ssample >= 0 && ssample < n;
+    const int8_t* const src = a.actions + (b0 + (won ? ssample : 0)) * K * A3;
+    int8_t* const dst = a.out_tokens + old * K * A3;
+    const int keep = won ? (sstep + 1) * A3 : 0;
+    for (int x = tid; x < K * A3; x += kBlock) dst[x] = x < keep ? src[x] : static_cast<int8_t>(0);
+    __syncthreads();  // the overflow flags are read before they are cleared
+  }
+
+  if (kind && q >= 0) {
+    const int64_t RB = static_cast<int64_t>(a.T) * a.S * a.S * a.S;  // bytes of a row
+    const int8_t* const src = a.q_states + q * RB;
+    int8_t* const dst = a.frames + b0 * RB;
+    if (a.wide) {
+      const int ipr = static_cast<int>(RB / 16);
+      for (int x = tid; x < n * ipr; x += kBlock)
+        reinterpret_cast<uint4*>(dst)[x] = reinterpret_cast<const uint4*>(src)[x % ipr];
+    } else {
+      const int full = static_cast<int>(RB / 4), ipr = static_cast<int>((RB + 3) / 4);
+      for (int x = tid; x < n * ipr; x += kBlock) {
+        const int r = x / ipr, c = x - r * ipr;
+        const int8_t* const sp = src + 4 * c;
+        int8_t* const dp = dst + r * RB + 4 * c;
+        if (c < full) {
+          reinterpret_cast<RollU32*>(dp)->v = reinterpret_cast<const RollU32*>(sp)->v;
+        } else {
+          for (int k = 0; k < static_cast<int>(RB) - 4 * full; ++k) dp[k] = sp[k];
         }
       }
-      head[d] = out;
-      cnt = count_nonzero_bytes(out, cnt);
     }
-#pragma unroll
-    for (int t = TG_NET_MAX_T - 2; t >= 0; --t)
-      if (t < T - 1) roll_store<W>(row + static_cast<int64_t>(t + 1) * N, nb, fr[t]);
-    roll_store<W>(row, nb, head);
-    if (cnt) atomicAdd(&s_nnz[lr], cnt);
-    if (ovf & ~255) s_ovf[lr] = 1;
+    if (a.scalars)
+      for (int x = tid; x < n * a.dim_s; x += kBlock) a.scalars[b0 * a.dim_s + x] = a.q_scalars[q * a.dim_s + x % a.dim_s];
+    for (int s = tid; s < n; s += kBlock) {
+      a.rows[b0 + s] = (a.first_state + q) * n + s;
+      a.nnz[b0 + s] = 0;
+      a.overflow[b0 + s] = 0;
+    }
+    if (tid == 0) {
+      a.best_nnz[g] = a.S * a.S * a.S;
+      a.hits[g] = 0;
+      a.solved_step[g] = -1;
+      a.solved_sample[g] = -1;
+      a.slot_state[g] = q;
+      a.slot_step[g] = 0;
+    }
+  } else if (kind) {
+    for (int s = tid; s < n; s += kBlock) a.rows[b0 + s] = -1;
+    if (tid == 0) a.slot_state[g] = -1;
   }
-  __syncthreads();
+  if (a.active)
+    for (int s = tid; s < n; s += kBlock) a.active[b0 + s] = q >= 0 ? 1 : 0;
 
-  // ---- per row, then per group
-  for (int r = tid; r < rows; r += kBlock) {
-    if (M && mixed && !s_act[r / n]) continue;
-    a.nnz[b0 + r] = s_nnz[r];
-    if (a.overflow && s_ovf[r]) a.overflow[b0 + r] = 1;
-    if (M && a.active) {  // the group's verdict again, per row: no third barrier
-      const int* const grp = s_nnz + r / n * n;
-      bool zero = false;
-      for (int s = 0; s < n; ++s) zero |= grp[s] == 0;
-      a.active[b0 + r] = zero ? 0 : 1;
-    }
-  }
-  for (int lg = tid; lg < ng; lg += kBlock) {
-    if (M && mixed && !s_act[lg]) continue;
-    int best = s_nnz[lg * n], first = -1;
-    for (int s = n - 1; s >= 0; --s) {
-      const int v = s_nnz[lg * n + s];
-      best = v < best ? v : best;
-      first = v == 0 ? s : first;
-    }
-    const int64_t g = g0 + lg;
-    const int old = a.best_nnz[g];
-    a.best_nnz[g] = best < old ? best : old;
-    if (best == 0) {
-      a.hits[g] += 1;
-      if (a.solved_step[g] < 0) a.solved_step[g] = a.step, a.solved_sample[g] = first;
+  if (a.uniforms && q >= 0) {
+    const int nu = a.n_uniforms, quads = (nu + 3) / 4;
+    const uint32_t call = kind ? 0u : static_cast<uint32_t>(step);
+    for (int x = tid; x < n * quads; x += kBlock) {
+      const int s = x / quads, c = x - s * quads;
+      const uint32_t key = static_cast<uint32_t>((a.first_state + q) * n + s);
+      const U4 w = philox4x32_10(U4{key, call, 0u, static_cast<uint32_t>(c)}, a.seed_lo, a.seed_hi);
+      const uint32_t word[4] = {w.x, w.y, w.z, w.w};
+      float* const u = a.uniforms + (b0 + s) * nu + 4 * c;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * c + k < nu) u[k] = static_cast<float>(word[k] >> 8) * 5.9604644775390625e-8f;
     }
   }
 }
@@ -242,21 +290,35 @@ extern "C" int tg_rollout_check(int64_t B, int n, int S, int T, int dim_s, int s
 
 namespace {
 
-// tg_rollout_advance (masked = false: `active` is ignored) and tg_rollout_advance_masked
-int rollout_entry(const char* fn, bool masked, int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz,
+int slots_check(const char* fn, int64_t B, int n, int max_actions) {
+  if (max_actions < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: max_actions=%d < 1", fn, max_actions);
+  if (B / n > TG_ROLLOUT_MAX_SLOTS)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: B/n=%lld slots, more than %d (TG_ROLLOUT_MAX_SLOTS)", fn,
+                            (long long)(B / n), TG_ROLLOUT_MAX_SLOTS);
+  return TG_OK;
+}
+
+// tg_rollout_advance (masked = false: `active` is ignored), tg_rollout_advance_masked, and tg_rollout_advance_slots
+// (slots = true: masked, `step` is ignored, slot_state / slot_step say which groups are stepped and at which index)
+int rollout_entry(const char* fn, bool masked, bool slots, const int64_t* slot_state, int32_t* slot_step, int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz,
                   uint8_t* overflow, int32_t* best_nnz, int32_t* hits, int32_t* solved_step, int32_t* solved_sample,
                   int8_t* actions, uint8_t* active, int64_t B, int n, int S, int T, int dim_s, int step, int max_actions,
                   int shift, tg_stream_t stream) {
   if (int rc = rollout_check(fn, B, n, S, T, dim_s, step, max_actions, actions != nullptr)) return rc;
+  if (slots)
+    if (int rc = slots_check(fn, B, n, max_actions)) return rc;
   if (B == 0) return TG_OK;
   if (!frames) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames", fn);
   if (!tokens) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens", fn);
   if (!nnz) return tg_internal_fail(TG_ERR_INVALID, "%s: null nnz", fn);
   if (!best_nnz || !hits || !solved_step || !solved_sample)
     return tg_internal_fail(TG_ERR_INVALID, "%s: null group record (best_nnz, hits, solved_step, solved_sample)", fn);
+  if (slots && (!slot_state || !slot_step)) return tg_internal_fail(TG_ERR_INVALID, "%s: null slot_state or slot_step", fn);
   if (!aligned(nnz, 4) || !aligned(best_nnz, 4) || !aligned(hits, 4) || !aligned(solved_step, 4) ||
       !aligned(solved_sample, 4) || (scalars && !aligned(scalars, 4)))
     return tg_internal_fail(TG_ERR_INVALID, "%s: nnz, the group records and scalars must be 4-byte aligned", fn);
+  if (slots && (!aligned(slot_state, 8) || !aligned(slot_step, 4)))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: slot_state must be 8-byte and slot_step 4-byte aligned", fn);
 
   const int N = S * S * S;
   const bool wide = S % 4 == 0 && aligned(frames, 16);  // then N % 64 == 0: every frame of every row is 16-byte aligned
@@ -274,6 +336,13 @@ int rollout_entry(const char* fn, bool masked, int8_t* frames, const int8_t* tok
   if (grid > 0x7fffffffll) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld: too large a grid", fn, (long long)B);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 dg(static_cast<unsigned>(grid)), db(tg::kBlock);
+  if (slots) {
+    tg::RolloutSlotArgs sa;
+    static_cast<tg::RolloutArgs&>(sa) = a;
+    sa.slot_state = slot_state, sa.slot_step = slot_step;
+    if (wide) return launch(fn, tg::rollout_advance_slots_kernel<16>, dg, db, 0, st, sa);
+    return launch(fn, tg::rollout_advance_slots_kernel<4>, dg, db, 0, st, sa);
+  }
   if (masked) {
     if (wide) return launch(fn, tg::rollout_advance_kernel<16, true>, dg, db, 0, st, a);
     return launch(fn, tg::rollout_advance_kernel<4, true>, dg, db, 0, st, a);
@@ -288,7 +357,7 @@ extern "C" int tg_rollout_advance(int8_t* frames, const int8_t* tokens, float* s
                                   int32_t* best_nnz, int32_t* hits, int32_t* solved_step, int32_t* solved_sample,
                                   int8_t* actions, int64_t B, int n, int S, int T, int dim_s, int step, int max_actions,
                                   int shift, tg_stream_t stream) {
-  return rollout_entry("tg_rollout_advance", false, frames, tokens, scalars, nnz, overflow, best_nnz, hits, solved_step,
+  return rollout_entry("tg_rollout_advance", false, false, nullptr, nullptr, frames, tokens, scalars, nnz, overflow, best_nnz, hits, solved_step,
                        solved_sample, actions, nullptr, B, n, S, T, dim_s, step, max_actions, shift, stream);
 }
 
@@ -297,6 +366,75 @@ extern "C" int tg_rollout_advance_masked(int8_t* frames, const int8_t* tokens, f
                                          int32_t* solved_sample, int8_t* actions, uint8_t* active, int64_t B, int n,
                                          int S, int T, int dim_s, int step, int max_actions, int shift,
                                          tg_stream_t stream) {
-  return rollout_entry("tg_rollout_advance_masked", true, frames, tokens, scalars, nnz, overflow, best_nnz, hits,
+  return rollout_entry("tg_rollout_advance_masked", true, false, nullptr, nullptr, frames, tokens, scalars, nnz, overflow, best_nnz, hits,
                        solved_step, solved_sample, actions, active, B, n, S, T, dim_s, step, max_actions, shift, stream);
+}
+
+extern "C" int tg_rollout_advance_slots(int8_t* frames, const int8_t* tokens, float* scalars, int32_t* nnz,
+                                        uint8_t* overflow, int32_t* best_nnz, int32_t* hits, int32_t* solved_step,
+                                        int32_t* solved_sample, int8_t* actions, uint8_t* active,
+                                        const int64_t* slot_state, int32_t* slot_step, int64_t B, int n, int S, int T,
+                                        int dim_s, int max_actions, int shift, tg_stream_t stream) {
+  // step 0 passes the step checks of the plain entry whenever max_actions >= 1, which slots_check asks for
+  return rollout_entry("tg_rollout_advance_slots", true, true, slot_state, slot_step, frames, tokens, scalars, nnz,
+                       overflow, best_nnz, hits, solved_step, solved_sample, actions, active, B, n, S, T, dim_s, 0,
+                       max_actions, shift, stream);
+}
+
+extern "C" int tg_rollout_refill(const int8_t* q_states, const float* q_scalars, int64_t N, int64_t* head,
+                                 int64_t first_state, uint64_t seed, int n_uniforms, int8_t* frames, float* scalars,
+                                 int32_t* nnz, uint8_t* overflow, int32_t* best_nnz, int32_t* hits, int32_t* solved_step,
+                                 int32_t* solved_sample, const int8_t* actions, uint8_t* active, int64_t* slot_state,
+                                 int32_t* slot_step, int32_t* out_best_nnz, int32_t* out_hits, int32_t* out_solved_step,
+                                 int32_t* out_solved_sample, uint8_t* out_overflow, int8_t* out_tokens, int64_t* rows,
+                                 float* uniforms, int32_t* live, int64_t B, int n, int S, int T, int dim_s,
+                                 int max_actions, tg_stream_t stream) {
+  const char* fn = "tg_rollout_refill";
+  if (int rc = rollout_check(fn, B, n, S, T, dim_s, 0, max_actions, 1)) return rc;
+  if (int rc = slots_check(fn, B, n, max_actions)) return rc;
+  if (N < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: N=%lld < 0", fn, (long long)N);
+  if (first_state < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: first_state=%lld < 0", fn, (long long)first_state);
+  if (uniforms && n_uniforms != 3 * S)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: n_uniforms=%d with uniforms given: must be 3*S=%d", fn, n_uniforms, 3 * S);
+  if (B == 0 || N == 0) return TG_OK;
+  if (!q_states) return tg_internal_fail(TG_ERR_INVALID, "%s: null q_states", fn);
+  if (scalars && dim_s > 0 && !q_scalars) return tg_internal_fail(TG_ERR_INVALID, "%s: null q_scalars with scalars given", fn);
+  if (!head) return tg_internal_fail(TG_ERR_INVALID, "%s: null head", fn);
+  if (!frames) return tg_internal_fail(TG_ERR_INVALID, "%s: null frames", fn);
+  if (!nnz) return tg_internal_fail(TG_ERR_INVALID, "%s: null nnz", fn);
+  if (!overflow) return tg_internal_fail(TG_ERR_INVALID, "%s: null overflow", fn);
+  if (!best_nnz || !hits || !solved_step || !solved_sample)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: null group record (best_nnz, hits, solved_step, solved_sample)", fn);
+  if (!actions) return tg_internal_fail(TG_ERR_INVALID, "%s: null actions", fn);
+  if (!slot_state || !slot_step) return tg_internal_fail(TG_ERR_INVALID, "%s: null slot_state or slot_step", fn);
+  if (!out_best_nnz || !out_hits || !out_solved_step || !out_solved_sample || !out_overflow || !out_tokens)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: null output (out_best_nnz, out_hits, out_solved_step, "
+                            "out_solved_sample, out_overflow, out_tokens)", fn);
+  if (!rows) return tg_internal_fail(TG_ERR_INVALID, "%s: null rows", fn);
+  if (!live) return tg_internal_fail(TG_ERR_INVALID, "%s: null live", fn);
+  if (!aligned(nnz, 4) || !aligned(best_nnz, 4) || !aligned(hits, 4) || !aligned(solved_step, 4) ||
+      !aligned(solved_sample, 4) || (scalars && !aligned(scalars, 4)) || (q_scalars && !aligned(q_scalars, 4)))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: nnz, the group records, scalars and q_scalars must be 4-byte aligned", fn);
+  if (!aligned(head, 8) || !aligned(slot_state, 8) || !aligned(rows, 8) || !aligned(slot_step, 4) || !aligned(live, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: head, slot_state and rows must be 8-byte, slot_step and live 4-byte "
+                            "aligned", fn);
+  if (!aligned(out_best_nnz, 4) || !aligned(out_hits, 4) || !aligned(out_solved_step, 4) || !aligned(out_solved_sample, 4) ||
+      (uniforms && !aligned(uniforms, 4)))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: the int32 outputs and uniforms must be 4-byte aligned", fn);
+
+  tg::RefillArgs a{};
+  a.q_states = q_states, a.q_scalars = q_scalars, a.N = N, a.head = head, a.first_state = first_state;
+  a.seed_lo = static_cast<uint32_t>(seed), a.seed_hi = static_cast<uint32_t>(seed >> 32);
+  a.n_uniforms = uniforms ? n_uniforms : 0;
+  a.frames = frames, a.scalars = dim_s > 0 ? scalars : nullptr, a.nnz = nnz, a.overflow = overflow;
+  a.best_nnz = best_nnz, a.hits = hits, a.solved_step = solved_step, a.solved_sample = solved_sample;
+  a.actions = actions, a.active = active, a.slot_state = slot_state, a.slot_step = slot_step;
+  a.out_best_nnz = out_best_nnz, a.out_hits = out_hits, a.out_solved_step = out_solved_step;
+  a.out_solved_sample = out_solved_sample, a.out_overflow = out_overflow, a.out_tokens = out_tokens;
+  a.rows = rows, a.uniforms = uniforms, a.live = live;
+  a.R = static_cast<int>(B / n), a.n = n, a.S = S, a.T = T, a.dim_s = dim_s, a.max_actions = max_actions;
+  a.wide = S % 4 == 0 && aligned(frames, 16) && aligned(q_states, 16);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = launch(fn, tg::rollout_refill_plan_kernel, dim3(1), dim3(tg::kRefillScan), 0, st, a)) return rc;
+  return launch(fn, tg::rollout_refill_fill_kernel, dim3(static_cast<unsigned>(a.R)), dim3(tg::kBlock), 0, st, a);
 }

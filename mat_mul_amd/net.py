@@ -264,3 +264,30 @@ class FusedAlphaTensor:
             return tokens.view(frames.shape[0], self.n_steps)
 
         return policy
+
+    def slot_policy(self, seed: int = 0):
+        """The policy of ``rollout.solve_stream`` (``takes_slots = True``, ``seed``): called as ``policy(frames, scalars,
+        rows, steps, active=..., uniforms=..., out=tokens)``, it evaluates the rows whose ``active`` byte is set (torso
+        and ``sample`` with k = 1, ``flags=active, need=1``) with the given ``uniforms`` float32 (B,1,n_steps) -- which
+        ``ops.rollout_refill`` fills by the sampling rule at (row key, call = the row's own step) under ``seed`` -- and
+        writes their tokens into ``out`` int8 (B,3S); the other rows of ``out`` keep what they held.  A row so draws
+        what ``rollout_policy(seed)`` draws for the row of the same key at the same step.  Two launches, capturable."""
+        if self.n_steps != 3 * self.config["S"]:
+            raise TensorGameError("slot_policy", -1, f"n_steps={self.n_steps} is not 3*dim_3d: the sampled tokens "
+                                  "are not one action")
+        ee = [None]
+
+        @torch.no_grad()
+        def policy(frames, scalars, rows, steps, active, uniforms, out):
+            B = frames.shape[0]
+            if ee[0] is None or ee[0].shape[0] != B:
+                S = self.config["S"]
+                ee[0] = torch.zeros((B, 3 * S * S, self.config["c"]), dtype=torch.float32, device=self.device)
+            self.torso(frames, scalars, out=ee[0], flags=active, need=1)
+            self.sample(ee[0], rows, seed, call=0, k=1, uniforms=uniforms, tokens=out.view(B, 1, self.n_steps),
+                        flags=active, need=1)
+            return out
+
+        policy.takes_slots = True
+        policy.seed = seed
+        return policy

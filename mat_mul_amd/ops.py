@@ -8,6 +8,7 @@ no CPU path: a non-GPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -24,6 +25,7 @@ __all__ = [
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
     "rollout_check", "rollout_records", "rollout_advance",
+    "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
 ]
 
 
@@ -992,3 +994,124 @@ def rollout_advance(frames, tokens, n: int, step: int, records, scalars=None, nn
     else:
         _launch(dev, "tg_rollout_advance", *ptrs, *sizes)
     return nnz
+
+
+# ---- the solution search over a queue of start states (include/tensor_game_rollout_slots.h) -------------------------
+@dataclass
+class RolloutSlots:
+    """The slot-side buffers of ``rollout_advance_slots`` / ``rollout_refill``: R slots of n rows, B = R*n.  ``records``
+    = (best_nnz, hits, solved_step, solved_sample) int32 (R,); ``slot_state`` int64 (R,) (< 0: empty), ``slot_step``
+    int32 (R,); per row frames int8 (B,T,S,S,S), scalars float32 (B,dim_s), nnz int32, overflow / active uint8, actions
+    int8 (B,max_actions,3S), tokens int8 (B,3S) (the policy's persistent output), rows int64 (the stream keys),
+    uniforms float32 (B,1,3S); ``head`` int64 [1] and ``live`` int32 [1] are the queue's device words."""
+
+    n: int
+    max_actions: int
+    frames: torch.Tensor
+    scalars: torch.Tensor
+    nnz: torch.Tensor
+    overflow: torch.Tensor
+    active: torch.Tensor
+    actions: torch.Tensor
+    tokens: torch.Tensor
+    rows: torch.Tensor
+    uniforms: torch.Tensor
+    records: Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
+    slot_state: torch.Tensor
+    slot_step: torch.Tensor
+    head: torch.Tensor
+    live: torch.Tensor
+
+
+def rollout_slots(R: int, n: int, S: int, T: int, dim_s: int, max_actions: int, device) -> RolloutSlots:
+    """R empty slots of n rows each (``slot_state`` = -1, ``head`` = 0): the first ``rollout_refill`` fills them."""
+    R, n, K = int(R), int(n), int(max_actions)
+    if R < 0 or R > _lib.TG_ROLLOUT_MAX_SLOTS:
+        raise TensorGameError("rollout_slots", -1, f"R={R} slots outside [0,{_lib.TG_ROLLOUT_MAX_SLOTS}] "
+                              "(TG_ROLLOUT_MAX_SLOTS)")
+    B = R * max(n, 0)
+    rollout_check(B, n, S, T, dim_s, 0, K, True)
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+    return RolloutSlots(n, K, z((B, T, S, S, S), torch.int8), z((B, dim_s), torch.float32), z((B,), torch.int32),
+                        z((B,), torch.uint8), z((B,), torch.uint8), z((B, K, 3 * S), torch.int8),
+                        z((B, 3 * S), torch.int8), torch.full((B,), -1, dtype=torch.int64, device=device),
+                        z((B, 1, 3 * S), torch.float32), rollout_records(R, S, device),
+                        torch.full((R,), -1, dtype=torch.int64, device=device), z((R,), torch.int32),
+                        z((1,), torch.int64), z((1,), torch.int32))
+
+
+def _slot_rows(slots: RolloutSlots, fn: str):
+    """(B, R, S, T, dim_s, K, dev) of the slot buffers, every one held to its shape."""
+    f = slots.frames
+    _need_gpu(f, "frames")
+    if f.dtype != torch.int8 or f.dim() != 5 or not (f.shape[2] == f.shape[3] == f.shape[4]) or not f.is_contiguous():
+        raise TensorGameError(fn, -1, f"frames must be contiguous int8 (B,T,S,S,S), got {f.dtype} {tuple(f.shape)}")
+    B, T, S = f.shape[0], f.shape[1], f.shape[2]
+    dev, n, K = f.device, int(slots.n), int(slots.max_actions)
+    dim_s = slots.scalars.shape[1] if slots.scalars.dim() == 2 else -1
+    rollout_check(B, n, S, T, dim_s, 0, K, True)
+    R = B // n
+    for name, shape, dtype in (("scalars", (B, dim_s), torch.float32), ("nnz", (B,), torch.int32),
+                               ("overflow", (B,), torch.uint8), ("active", (B,), torch.uint8),
+                               ("actions", (B, K, 3 * S), torch.int8), ("tokens", (B, 3 * S), torch.int8),
+                               ("rows", (B,), torch.int64), ("uniforms", (B, 1, 3 * S), torch.float32),
+                               ("slot_state", (R,), torch.int64), ("slot_step", (R,), torch.int32),
+                               ("head", (1,), torch.int64), ("live", (1,), torch.int32)):
+        if getattr(slots, name) is None:
+            raise TensorGameError(fn, -1, f"slots.{name} is missing (ops.rollout_slots allocates it)")
+        _flag(getattr(slots, name), shape, dtype, dev, name)
+    if len(slots.records) != 4:
+        raise TensorGameError(fn, -1, "records must be (best_nnz, hits, solved_step, solved_sample)")
+    for r, name in zip(slots.records, ("best_nnz", "hits", "solved_step", "solved_sample")):
+        if r is None:
+            raise TensorGameError(fn, -1, "records must be four int32 tensors (ops.rollout_records)")
+        _flag(r, (R,), torch.int32, dev, name)
+    return B, R, S, T, dim_s, K, dev
+
+
+def rollout_advance_slots(slots: RolloutSlots, tokens=None, shift: int = 1) -> None:
+    """One step of every LIVE slot, each at its own step index, in one launch (tg_rollout_advance_slots): a slot is
+    live iff it holds a state (slot_state >= 0) that is unsolved (solved_step < 0) with slot_step < max_actions.  Live
+    slots get what ``rollout_advance(stop_solved=True)`` gives an active group with ``step`` = their slot_step, then
+    slot_step += 1; of the others nothing but the three words is read and nothing is written.  ``tokens`` int8 (B,3S)
+    defaults to ``slots.tokens``."""
+    B, R, S, T, dim_s, K, dev = _slot_rows(slots, "rollout_advance_slots")
+    tokens = _tokens(slots.tokens if tokens is None else tokens, (B,), S, dev, "tokens")
+    _launch(dev, "tg_rollout_advance_slots", _ptr(slots.frames), _ptr(tokens), _ptr(slots.scalars), _ptr(slots.nnz),
+            _ptr(slots.overflow), *map(_ptr, slots.records), _ptr(slots.actions), _ptr(slots.active),
+            _ptr(slots.slot_state), _ptr(slots.slot_step), B, int(slots.n), S, T, dim_s, K, int(shift))
+
+
+def rollout_refill(slots: RolloutSlots, states, scalars, out, seed: int = 0, first_state: int = 0,
+                   uniforms: bool = True) -> None:
+    """Flush the finished slots to the dense per-state outputs, hand the next queue states to the finished and the empty
+    slots in slot order, and prepare the next policy call (tg_rollout_refill: two launches, no host sync).  ``states``
+    int8 (N,T,S,S,S) and ``scalars`` float32 (N,dim_s) are the queue, ``slots.head`` its read position; ``out`` =
+    (best_nnz, hits, solved_step, solved_sample int32 (N,), overflow uint8 (N,), tokens int8 (N,max_actions,3S)).
+    Afterwards ``slots.active`` marks the rows of the slots that hold an unfinished state, ``slots.live`` counts those
+    slots, ``slots.rows`` = (first_state + state) * n + sample keys their streams, and with ``uniforms`` the rows'
+    ``slots.uniforms`` are what ``net_sample`` would draw with ``seed`` and ``call_idx`` = the slot's own step."""
+    B, R, S, T, dim_s, K, dev = _slot_rows(slots, "rollout_refill")
+    _need_gpu(states, "states")
+    N = states.shape[0] if states.dim() == 5 else -1
+    if states.dtype != torch.int8 or tuple(states.shape) != (N, T, S, S, S) or states.device != dev or \
+            not states.is_contiguous():
+        raise TensorGameError("rollout_refill", -1, f"states must be contiguous int8 (N,T,S,S,S) = {(T, S, S, S)} per "
+                              f"state on {dev}, got {states.dtype} {tuple(states.shape)} on {states.device}")
+    scalars = _flag(scalars, (N, dim_s), torch.float32, dev, "scalars")
+    if int(first_state) < 0:
+        raise TensorGameError("rollout_refill", -1, f"first_state={first_state} < 0")
+    if len(out) != 6:
+        raise TensorGameError("rollout_refill", -1, "out must be (best_nnz, hits, solved_step, solved_sample, overflow, "
+                              "tokens)")
+    shapes = [((N,), torch.int32)] * 4 + [((N,), torch.uint8), ((N, K, 3 * S), torch.int8)]
+    names = ("out best_nnz", "out hits", "out solved_step", "out solved_sample", "out overflow", "out tokens")
+    for t, (shape, dtype), name in zip(out, shapes, names):
+        if t is None:
+            raise TensorGameError("rollout_refill", -1, f"{name} is missing")
+        _flag(t, shape, dtype, dev, name)
+    _launch(dev, "tg_rollout_refill", _ptr(states), _ptr(scalars), N, _ptr(slots.head), int(first_state), _u64(seed),
+            3 * S if uniforms else 0, _ptr(slots.frames), _ptr(slots.scalars), _ptr(slots.nnz), _ptr(slots.overflow),
+            *map(_ptr, slots.records), _ptr(slots.actions), _ptr(slots.active), _ptr(slots.slot_state),
+            _ptr(slots.slot_step), *map(_ptr, out), _ptr(slots.rows), _ptr(slots.uniforms if uniforms else None),
+            _ptr(slots.live), B, int(slots.n), S, T, dim_s, K)

@@ -21,6 +21,10 @@ vocabulary; the reference hard-codes ``- 2`` (:253, the Strassen vocabulary): pa
 again and a policy with ``takes_active = True`` (``FusedAlphaTensor.rollout_policy(seed, masked=True)``) does not
 evaluate them, ``check_every=m`` leaves the loop once no group is left, and ``solve_states`` runs a whole dataset that
 way, chunk by chunk (the dataset loop of training.py:331-346).
+
+``solve_stream`` runs the same dataset through ``slots`` resident groups that are refilled from a device-side queue
+(include/tensor_game_rollout_slots.h): a group that is solved or out of steps is flushed and takes the next start state
+in the same tick, so every policy call stays full until the queue is drained and the host reads one word now and then.
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ import torch
 from . import ops
 from ._lib import TensorGameError
 
-__all__ = ["sample_rollouts", "RolloutResult", "model_policy", "RolloutPolicy", "solve_states", "SolveResult"]
+__all__ = ["sample_rollouts", "RolloutResult", "model_policy", "RolloutPolicy", "solve_states", "SolveResult",
+           "solve_stream"]
 
 # (frames int8 (B,T,S,S,S), scalars float32 (B,dim_s), rows int64 (B,), step) -> tokens int8 (B,3S)
 RolloutPolicy = Callable[[torch.Tensor, torch.Tensor, torch.Tensor, int], torch.Tensor]
@@ -207,7 +212,8 @@ class SolveResult:
     """What ``solve_states`` leaves on the device: the per-group records of ``RolloutResult`` for all G states (int32
     (G,) each) and ``solutions()`` of all chunks -- ``groups`` int64 (M,) indexes ``states``, ``tokens`` int8
     (M,max_actions,3S), ``lengths`` int64 (M,).  ``steps_run`` has one entry per chunk and is the only field that
-    depends on the chunking."""
+    depends on the chunking.  ``solve_stream`` also fills ``overflow`` uint8 (G,) (1 where an entry of some row of the
+    state left int8) and ``ticks`` (the policy calls it made; ``steps_run`` = (ticks,))."""
 
     best_nnz: torch.Tensor
     hits: torch.Tensor
@@ -217,6 +223,8 @@ class SolveResult:
     tokens: torch.Tensor
     lengths: torch.Tensor
     steps_run: Sequence[int]
+    overflow: Optional[torch.Tensor] = None
+    ticks: int = 0
 
 
 def solve_states(policy: RolloutPolicy, states: torch.Tensor, scalars: torch.Tensor, n_samples: int, max_actions: int,
@@ -241,3 +249,106 @@ def solve_states(policy: RolloutPolicy, states: torch.Tensor, scalars: torch.Ten
                        cat(p.solved_sample for p in parts),
                        cat(s[0] + i * c for i, s in enumerate(sols)), cat(s[1] for s in sols),
                        cat(s[2] for s in sols), tuple(p.steps_run for p in parts))
+
+
+def solve_stream(policy, states: torch.Tensor, scalars: torch.Tensor, n_samples: int, max_actions: int, slots: int,
+                 check_every: int = 8, shift: int = 1, graph: bool = False, first_state: int = 0) -> SolveResult:
+    """``solve_states`` with continuous refill: ``slots`` groups of ``n_samples`` rows stay resident; after every step
+    the finished ones (solved, or ``max_actions`` steps old) are flushed to per-state outputs and take the next start
+    states in slot order (``ops.rollout_refill``), so a tick is ``policy -> advance_slots -> refill`` on full launches
+    until the dataset is drained.  Every ``check_every`` ticks (0: never before the bound) the host reads the number of
+    occupied slots and leaves when it is 0; after ``max_actions * (N // slots + 1)`` ticks, the makespan bound of
+    handing states out greedily, the loop ends either way and raises if a slot is still occupied.
+
+    A row's stream is keyed by ``(first_state + state index) * n_samples + sample`` and by the row's OWN step, so for
+    a policy that decides from the row key, the row's state and that step, every field but ``steps_run`` / ``ticks``
+    equals ``solve_states`` bit for bit, for every ``slots`` >= 1.
+
+    ``policy`` with ``takes_slots = True`` (``FusedAlphaTensor.slot_policy(seed)``; it exposes ``seed``) is called as
+    ``policy(frames, scalars, rows, steps, active=..., uniforms=..., out=...)``: ``steps`` int32 (B,) is each row's own
+    step, ``uniforms`` float32 (B,1,3S) the row's draws for that step, ``out`` the persistent int8 (B,3S) token buffer
+    it returns.  Any other policy is called as ``policy(frames, scalars, rows, steps)`` and no uniforms are generated.
+    ``graph=True`` captures ONE tick (a linear chain: nothing in it depends on a host step number) and replays it,
+    reading the occupied count between blocks of ``check_every`` replays; the results equal the eager loop."""
+    if not states.is_cuda:
+        raise TensorGameError("solve_stream", -1, f"states must live on a ROCm device (got {states.device}); there is "
+                              "no CPU path")
+    if states.dtype != torch.int8 or states.dim() != 5 or not (states.shape[2] == states.shape[3] == states.shape[4]):
+        raise TensorGameError("solve_stream", -1, f"states must be int8 (N,T,S,S,S), got {states.dtype} "
+                              f"{tuple(states.shape)}")
+    N, T, S = states.shape[0], states.shape[1], states.shape[2]
+    dev = states.device
+    if scalars.dim() != 2 or scalars.shape[0] != N or scalars.dtype != torch.float32 or scalars.device != dev:
+        raise TensorGameError("solve_stream", -1, f"scalars must be float32 ({N},dim_s) on {dev}, got "
+                              f"{scalars.dtype} {tuple(scalars.shape)} on {scalars.device}")
+    n, K, R, m = int(n_samples), int(max_actions), int(slots), int(check_every)
+    if K < 1:
+        raise TensorGameError("solve_stream", -1, f"max_actions={max_actions} < 1")
+    if R < 1:
+        raise TensorGameError("solve_stream", -1, f"slots={slots} < 1")
+    if m < 0:
+        raise TensorGameError("solve_stream", -1, f"check_every={check_every} < 0")
+    if int(first_state) < 0:
+        raise TensorGameError("solve_stream", -1, f"first_state={first_state} < 0")
+    dim_s = scalars.shape[1]
+    sl = ops.rollout_slots(R, n, S, T, dim_s, K, dev)
+    states, scalars = states.contiguous(), scalars.contiguous()
+    kw = dict(dtype=torch.int32, device=dev)
+    # a state the queue never hands out (there is none unless the loop fails) reads as unsolved
+    out = (torch.full((N,), S ** 3, **kw), torch.zeros((N,), **kw), torch.full((N,), -1, **kw),
+           torch.full((N,), -1, **kw), torch.zeros((N,), dtype=torch.uint8, device=dev),
+           torch.zeros((N, K, 3 * S), dtype=torch.int8, device=dev))
+    takes_slots = bool(getattr(policy, "takes_slots", False))
+    seed = int(policy.seed) if takes_slots else 0
+    steps = torch.zeros((R * n,), dtype=torch.int32, device=dev)
+
+    def refill() -> None:
+        ops.rollout_refill(sl, states, scalars, out, seed=seed, first_state=first_state, uniforms=takes_slots)
+
+    def tick() -> None:
+        steps.view(R, n).copy_(sl.slot_step.view(R, 1).expand(R, n))
+        if takes_slots:
+            tokens = policy(sl.frames, sl.scalars, sl.rows, steps, active=sl.active, uniforms=sl.uniforms,
+                            out=sl.tokens)
+            if tokens is not sl.tokens:
+                raise TensorGameError("policy", -1, "a policy with takes_slots returns the token buffer `out`")
+        else:
+            tokens = policy(sl.frames, sl.scalars, sl.rows, steps)
+        ops.rollout_advance_slots(sl, tokens, shift=shift)
+        refill()
+
+    bound = K * (N // R + 1)
+    ticks, live, g = 0, 0, None
+    if N:
+        refill()
+        if graph:
+            # one warm-up tick on a side stream (lazy initialisation of the policy's launches); it is a real tick
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                tick()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            ticks = 1
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                tick()
+            run = g.replay
+        else:
+            run = tick
+        live = -1
+        if m and ticks and ticks % m == 0:
+            live = int(sl.live.item())
+        while live != 0 and ticks < bound:
+            run()
+            ticks += 1
+            if m and ticks % m == 0:
+                live = int(sl.live.item())
+        if live != 0:
+            live = int(sl.live.item())
+        if live != 0:
+            raise TensorGameError("solve_stream", -1, f"{live} slots are still occupied after {ticks} ticks, the bound "
+                                  f"max_actions * (N // slots + 1) = {bound}: the refill does not drain the queue")
+    best_nnz, hits, solved_step, solved_sample, overflow, tokens = out
+    groups = torch.nonzero(solved_step >= 0).flatten()
+    return SolveResult(best_nnz, hits, solved_step, solved_sample, groups, tokens[groups],
+                       solved_step[groups].to(torch.int64) + 1, (ticks,), overflow, ticks)

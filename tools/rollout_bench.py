@@ -2,6 +2,7 @@
 
     python tools/rollout_bench.py OUT_DIR [--parts a,b,c] [--configs a,a9,a16] [--reps 20] [--warmup 3]
     python tools/rollout_bench.py OUT_DIR --masked [--configs a,a16] [--fractions 1,0.5,0.1,0] [--repeats 5]
+    python tools/rollout_bench.py OUT_DIR --stream [--configs a,a16] [--parent DIR] [--reps 7]
 
 Writes (and, part by part, merges into) OUT_DIR/r12_rollout.json.  HIP events around each call after warm-up; median,
 p10 and p90 in microseconds; two variants of one figure alternate call by call in one process.
@@ -27,6 +28,18 @@ the same work at every f) next to the masked step (rollout_policy(masked=True) +
 call by call in one process.  The records are put back before every call (both variants pay the same four small
 copies), so every call sees the same share.  The whole measurement is made --repeats times; the spread of the plain
 step's medians over the repeats is reported beside the figures.
+
+--stream writes OUT_DIR/r15_rollout_stream.json instead: the solution search over a dataset of start states with
+continuous refill (``solve_stream(slots=R)``, include/tensor_game_rollout_slots.h) against the chunked search
+(``solve_states(chunk_groups=R)``), wall time per dataset, alternating run by run in one process.  With --parent DIR the
+chunked side is the package of ANOTHER checkout (the parent commit, built there), loaded beside this one under its own
+name with its own library; without it, this tree's solve_states (same Python, same code objects of the masked step).
+N = 4 096 start states at configuration a, 512 at a16, n = 8, R = 256 and 1 024, the fused policy with the bias towards
+the null action of the tests' ``fused_setup``, and three shares of start states that are solved at once (zero states):
+0, 1/3 and 2/3; the others hold random entries and are practically never solved, so they take all max_actions steps.
+Then ``rollout_refill`` (every slot takes a new state / every slot is kept) and ``rollout_advance_slots`` alone at
+2 048 and 65 536 rows (S = 4, T = 2, n = 8) next to the masked advance, HIP events, the slot words put back before
+every call on both sides.
 """
 from __future__ import annotations
 
@@ -45,7 +58,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 from mat_mul_amd import FusedAlphaTensor, FusedTrainer, SyntheticDemos, functional, ops, rollout  # noqa: E402
-from net_ref import CONFIGS, Ref, make_weights  # noqa: E402
+from net_ref import CONFIGS, P, Ref, make_weights  # noqa: E402
 from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
 from net_s16_ref import CONFIGS as CONFIGS_S16  # noqa: E402
 
@@ -282,6 +295,143 @@ def part_masked(configs, fractions, reps, warmup, repeats):
     return out
 
 
+def load_parent(path):
+    """The package of another checkout under the name mat_mul_amd_parent (its own _lib loads its own library)."""
+    import importlib.util
+    pkg = Path(path).resolve() / "mat_mul_amd"
+    spec = importlib.util.spec_from_file_location("mat_mul_amd_parent", pkg / "__init__.py",
+                                                  submodule_search_locations=[str(pkg)])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["mat_mul_amd_parent"] = mod
+    spec.loader.exec_module(mod)
+    assert Path(mod._lib.LIB_PATH).resolve().parent.parent == pkg, mod._lib.LIB_PATH
+    return mod
+
+
+def null_biased(cfg, seed=77):
+    """The weights of the tests' fused_setup: the last policy layer scaled down, its bias favouring the token of 0."""
+    sd = make_weights(cfg, seed)
+    sd[P + "li1.weight"] = sd[P + "li1.weight"] * 0.25
+    assert cfg["n_logits"] == 3
+    sd[P + "li1.bias"] = np.array([0.0, 3.0, 0.0], np.float32)
+    return sd
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6
+
+
+def part_stream(configs, parent, reps, warmup):
+    out = []
+    n = 8
+    for name in configs:
+        cfg = CONFIGS[name]
+        S, T, K = cfg["dim_3d"], cfg["dim_t"], HORIZON[name]
+        N = {"a": 4096, "a16": 512}.get(name, 512)
+        sd = null_biased(cfg)
+        net = FusedAlphaTensor.from_state_dict(sd, cfg["n_samples"], device=DEV)
+        chunk_pkg = parent if parent is not None else sys.modules["mat_mul_amd"]
+        net_c = chunk_pkg.FusedAlphaTensor.from_state_dict(sd, cfg["n_samples"], device=DEV) if parent is not None else net
+        rng = np.random.default_rng(S)
+        base = np.zeros((N, T, S, S, S), np.int8)
+        base[:, 0] = rng.integers(-1, 2, size=(N, S, S, S))
+        scalars = torch.zeros((N, cfg["dim_s"]), device=DEV)
+        for share, zero in (("0", np.zeros(N, bool)), ("1/3", np.arange(N) % 3 == 0), ("2/3", np.arange(N) % 3 != 2)):
+            st = base.copy()
+            st[zero] = 0
+            states = torch.from_numpy(st).to(DEV)
+            for R in (256, 1024):
+                res = {}
+
+                def stream():
+                    res["stream"] = rollout.solve_stream(net.slot_policy(5), states, scalars, n, K, slots=R, check_every=4)
+
+                def chunked():
+                    res["chunked"] = chunk_pkg.rollout.solve_states(net_c.rollout_policy(5, masked=True), states, scalars,
+                                                                    n, K, chunk_groups=R, check_every=1)
+
+                fns = {"solve_states_chunked": chunked, "solve_stream": stream}
+                for _ in range(warmup):
+                    for fn in fns.values():
+                        fn()
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, fn in fns.items():
+                        ts[k].append(wall(fn))
+                a, b = res["stream"], res["chunked"]
+                equal = all(torch.equal(getattr(a, f), getattr(b, f)) for f in
+                            ("best_nnz", "hits", "solved_step", "solved_sample", "groups", "tokens", "lengths"))
+                row = {"config": name, "S": S, "N": N, "n": n, "R": R, "max_actions": K, "zero_share": share,
+                       "solved": int((a.solved_step >= 0).sum().item()), "stream_ticks": a.ticks,
+                       "chunked_steps": int(sum(b.steps_run)), "results_equal": equal,
+                       "chunked_is_parent_checkout": parent is not None, **{k: stats(v) for k, v in ts.items()}}
+                row["stream_over_chunked"] = row["solve_stream"]["median_us"] / row["solve_states_chunked"]["median_us"]
+                out.append(row)
+                print(json.dumps(row), flush=True)
+    return out
+
+
+def part_slot_entries(reps, warmup):
+    out = []
+    S, T, n, K, dim_s = 4, 2, 8, 7, 1
+    for B in (2048, 65536):
+        R = B // n
+        rng = np.random.default_rng(B)
+        N = 4 * R
+        q_states = torch.from_numpy(rng.integers(-2, 3, size=(N, T, S, S, S)).astype(np.int8)).to(DEV)
+        q_scal = torch.zeros((N, dim_s), device=DEV)
+        sl = ops.rollout_slots(R, n, S, T, dim_s, K, DEV)
+        outs = (*ops.rollout_records(N, S, DEV), torch.zeros((N,), dtype=torch.uint8, device=DEV),
+                torch.zeros((N, K, 3 * S), dtype=torch.int8, device=DEV))
+        ops.rollout_refill(sl, q_states, q_scal, outs, seed=1)
+        tokens = torch.from_numpy(rng.integers(0, 3, size=(B, 3 * S)).astype(np.int8)).to(DEV)
+        frames0 = sl.frames.clone()
+        step0, stepK = torch.zeros_like(sl.slot_step), torch.full_like(sl.slot_step, K)
+        head0 = torch.zeros_like(sl.head)
+        rec = ops.rollout_records(R, S, DEV)
+        fresh = ops.rollout_records(R, S, DEV)
+        nnz = torch.zeros((B,), dtype=torch.int32, device=DEV)
+        active = torch.ones((B,), dtype=torch.uint8, device=DEV)
+
+        def put_back(step):
+            sl.slot_step.copy_(step)
+            sl.records[2].copy_(fresh[2])
+            rec[2].copy_(fresh[2])
+            sl.head.copy_(head0)
+
+        def advance_slots():
+            put_back(step0)
+            ops.rollout_advance_slots(sl, tokens)
+
+        def advance_masked():
+            put_back(step0)
+            ops.rollout_advance(frames0, tokens, n, 0, rec, scalars=sl.scalars, nnz=nnz, overflow=sl.overflow,
+                                actions=sl.actions, active=active, stop_solved=True)
+
+        def refill_all_take():
+            put_back(stepK)
+            ops.rollout_refill(sl, q_states, q_scal, outs, seed=1)
+
+        def refill_all_kept():
+            put_back(step0)
+            ops.rollout_refill(sl, q_states, q_scal, outs, seed=1)
+
+        def put_back_alone():
+            put_back(step0)
+
+        res = alternate({"advance_slots": advance_slots, "advance_masked": advance_masked,
+                         "refill_all_take": refill_all_take, "refill_all_kept": refill_all_kept,
+                         "put_back_alone": put_back_alone}, reps, warmup)
+        row = {"S": S, "T": T, "n": n, "rows": B, "slots": R, "max_actions": K, **res}
+        out.append(row)
+        print(json.dumps(row), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out_dir")
@@ -292,10 +442,28 @@ def main():
     ap.add_argument("--masked", action="store_true", help="time the step that stops solved groups (see above)")
     ap.add_argument("--fractions", default="1,0.5,0.1,0")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--stream", action="store_true", help="time solve_stream against solve_states (see above)")
+    ap.add_argument("--parent", default=None, help="--stream: another checkout whose solve_states is the chunked side")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU; there is no CPU path"
     out = Path(args.out_dir)
     out.mkdir(parents=True, exist_ok=True)
+    if args.stream:
+        path = out / "r15_rollout_stream.json"
+        res = json.loads(path.read_text()) if path.exists() else {}
+        configs = ["a", "a16"] if args.configs == "a,a9,a16" else args.configs.split(",")
+        parent = load_parent(args.parent) if args.parent else None
+        reps = 7 if args.reps == 20 else args.reps
+        done = {(r["config"], r["zero_share"], r["R"]): r for r in res.get("dataset", [])}
+        for r in part_stream(configs, parent, reps, min(args.warmup, 1)):
+            done[(r["config"], r["zero_share"], r["R"])] = r
+        res["dataset"] = [done[k] for k in sorted(done)]
+        res["entries"] = part_slot_entries(50, 5)
+        res["device"] = torch.cuda.get_device_name(0)
+        res.setdefault("commands", []).append(" ".join(sys.argv))
+        path.write_text(json.dumps(res, indent=1))
+        print(f"wrote {path}")
+        return
     if args.masked:
         path = out / "r14_rollout_masked.json"
         res = json.loads(path.read_text()) if path.exists() else {}
