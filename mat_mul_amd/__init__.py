@@ -16,9 +16,9 @@ __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
            "FusedAlphaTensor", "net", "FusedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult",
-           "solve_states", "solve_stream"]
+           "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -34,6 +34,9 @@ _ATTRS = {
     "RolloutResult": "rollout",
     "solve_states": "rollout",
     "solve_stream": "rollout",
+    "PackedGames": "replay_io",
+    "save_run": "replay_io",
+    "load_run": "replay_io",
 }
 
 

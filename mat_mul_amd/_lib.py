@@ -101,6 +101,15 @@ TG_REPLAY_MAX_CAPACITY, TG_REPLAY_MAX_ACTIONS, TG_REPLAY_MAX_T, TG_REPLAY_MAX_LO
 TG_REPLAY_SYNTH, TG_REPLAY_PLAYED, TG_REPLAY_BEST = 0, 1, 2
 
 
+# name -> argtypes; every symbol include/tensor_game_replay_io.h declares
+REPLAY_IO_SIGNATURES = {
+    "tg_replay_pack": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    "tg_replay_add_packed": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p],
+}
+# status bits of include/tensor_game_replay_io.h
+TG_REPLAY_IO_BAD_LENGTH, TG_REPLAY_IO_TRUNCATED = 1, 2
+
+
 class ReplayBufferDesc(C.Structure):
     """``tg_replay_buffer`` of include/tensor_game_replay.h (sizes, then device pointers)."""
 
@@ -192,6 +201,7 @@ def _load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
+                           **REPLAY_IO_SIGNATURES,
                            **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES,
                            **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
         try:

@@ -36,6 +36,7 @@ SOURCES = sorted(CSRC.glob("*.hip"))
 HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "tensor_game.h", PKG.parent / "include" / "tensor_game_demos.h",
                                             PKG.parent / "include" / "tensor_game_search.h",
                                             PKG.parent / "include" / "tensor_game_replay.h",
+                                            PKG.parent / "include" / "tensor_game_replay_io.h",
                                             PKG.parent / "include" / "tensor_game_net.h",
                                             PKG.parent / "include" / "tensor_game_train.h",
                                             PKG.parent / "include" / "tensor_game_rollout.h",

@@ -22,6 +22,7 @@ __all__ = [
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
+    "replay_pack", "replay_add_packed",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
     "rollout_check", "rollout_records", "rollout_advance",
@@ -765,6 +766,60 @@ def replay_items(idx, T: int, S: int, device, tokens=None, targets=None, played=
             _ptr(kind), _ptr(src), len_data, code, _ptr(idx), N, int(T), dcode, _ptr(out),
             _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status))
     return out, scalars, actions, rewards
+
+
+# ---- a buffer's stored moves as dense arrays (include/tensor_game_replay_io.h) --------------------------------------
+
+
+def _dense_rows(buf, M: int):
+    """The shapes of M dense rows of ``buf``'s games: frames, tokens, rewards."""
+    return (M, buf.T, buf.S, buf.S, buf.S), (M, 3 * buf.S), (M,)
+
+
+def replay_pack(buf, max_moves: int, frames=None, tokens=None, rewards=None, lengths=None, move_offset=None,
+                counts=None, status=None):
+    """The stored games of a ``replay.GameBuffer`` as dense rows, oldest first (tg_replay_pack): returns (frames int8
+    (max_moves,T,S,S,S), tokens int8 (max_moves,3S), rewards float32 (max_moves,), lengths int32 (C,), move_offset int64
+    (C+1,), counts int64 (2,) = (G, M)), each allocated when it is not given.  Rows [0, M), lengths[:G] and
+    move_offset[:G+1] are written; a game whose rows would pass ``max_moves`` is not written and sets bit 1 of
+    ``status`` uint32 (1,).  No host sync."""
+    dev = buf.device
+    max_moves = int(max_moves)
+    if max_moves < 0:
+        raise TensorGameError("replay_pack", -1, f"max_moves={max_moves} < 0")
+    f_shape, t_shape, r_shape = _dense_rows(buf, max_moves)
+    frames = _out(frames, f_shape, torch.int8, dev, "frames")
+    tokens = _out(tokens, t_shape, torch.int8, dev, "tokens")
+    rewards = _out(rewards, r_shape, torch.float32, dev, "rewards")
+    lengths = _out(lengths, (buf.C,), torch.int32, dev, "lengths")
+    move_offset = _out(move_offset, (buf.C + 1,), torch.int64, dev, "move_offset")
+    counts = _out(counts, (2,), torch.int64, dev, "counts")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_replay_pack", C.byref(buf.desc), max_moves, _ptr(lengths), _ptr(move_offset), _ptr(counts),
+            _ptr(rewards), _ptr(tokens), _ptr(frames), _ptr(status))
+    return frames, tokens, rewards, lengths, move_offset, counts
+
+
+def replay_add_packed(buf, frames, tokens, rewards, lengths, first_slot: int = -1, games_added: int = -1,
+                      status=None) -> None:
+    """Store games given as dense rows in a ``replay.GameBuffer`` (tg_replay_add_packed): frames int8 (M,T,S,S,S),
+    tokens int8 (M,3S), rewards float32 (M,), lengths int32 (G,); game g's rows start at the sum of the earlier
+    (non-negative) lengths.  ``first_slot`` -1 continues at the ring's next slot, else the first stored game goes there;
+    ``games_added`` >= 0 sets the games-ever-added counter instead of growing it.  ``status`` uint32 (1,) gets bit 0 for
+    a length < 1 or > L and bit 1 for a game whose rows would pass M (neither is stored).  No host sync."""
+    dev = buf.device
+    for t, name in ((frames, "frames"), (tokens, "tokens"), (rewards, "rewards"), (lengths, "lengths")):
+        _need_gpu(t, name)
+    M = frames.shape[0] if frames.dim() == 5 else -1
+    G = lengths.shape[0] if lengths.dim() == 1 else -1
+    f_shape, t_shape, r_shape = _dense_rows(buf, M)
+    frames = _flag(frames, f_shape, torch.int8, dev, "frames")
+    tokens = _flag(tokens, t_shape, torch.int8, dev, "tokens")
+    rewards = _flag(rewards, r_shape, torch.float32, dev, "rewards")
+    lengths = _flag(lengths, (G,), torch.int32, dev, "lengths")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_replay_add_packed", C.byref(buf.desc), _ptr(frames), _ptr(tokens), _ptr(rewards), _ptr(lengths),
+            G, M, int(first_slot), int(games_added), _ptr(status))
 
 
 # ---- fused network inference (include/tensor_game_net.h) ------------------------------------------------------------

@@ -12,7 +12,7 @@ from typing import Iterator, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, replay_io
 from ._lib import TG_REPLAY_BEST, TG_REPLAY_PLAYED, TG_REPLAY_SYNTH, ReplayBufferDesc, TensorGameError
 
 __all__ = ["GameBuffer", "TensorGameData"]
@@ -83,6 +83,68 @@ class GameBuffer:
             raise IndexError(f"move {i} outside [0, {len(self)})")
         state, scalar, action, reward = self.items(torch.tensor([i], device=self.device))
         return state[0], scalar[0], action[0], reward[0]
+
+    # ---- dense form and disk (include/tensor_game_replay_io.h, replay_io) ----------------------------------------
+    def pack(self):
+        """The stored games as dense device tensors, oldest first: (frames int8 (M,T,S,S,S), tokens int8 (M,3S), rewards
+        float32 (M,), lengths int32 (G,), ring int64 (2,)).  One host sync (G and M, read together), then one
+        ``tg_replay_pack`` call into exactly M rows."""
+        G, M = (int(v) for v in torch.stack([(self.length > 0).sum(), self.offset[self.C]]).cpu())
+        frames, tokens, rewards, lengths, _, _ = ops.replay_pack(self, M, status=self.status)
+        return frames, tokens, rewards, lengths[:G], self.ring.clone()
+
+    def add_packed(self, frames, tokens, rewards, lengths, first_slot: Optional[int] = None,
+                   games_added: Optional[int] = None) -> None:
+        """Store games given in the dense form of ``pack`` (``tg_replay_add_packed``): oldest first into consecutive
+        slots from the ring's next slot, or from ``first_slot``; ``games_added`` sets the games-ever-added counter
+        instead of growing it.  No float policy is needed.  Asynchronous."""
+        dev = self.device
+        ops.replay_add_packed(self, torch.as_tensor(frames, device=dev).contiguous(),
+                              torch.as_tensor(tokens, device=dev).contiguous(),
+                              torch.as_tensor(rewards, device=dev).to(torch.float32).contiguous(),
+                              torch.as_tensor(lengths, device=dev).to(torch.int32).contiguous(),
+                              -1 if first_slot is None else int(first_slot),
+                              -1 if games_added is None else int(games_added), status=self.status)
+
+    def packed(self) -> "replay_io.PackedGames":
+        """``pack`` on the host (``replay_io.PackedGames``)."""
+        frames, tokens, rewards, lengths, ring = (t.cpu().numpy() for t in self.pack())
+        return replay_io.PackedGames(self.C, self.L, self.T, self.S, (int(ring[0]), int(ring[1])), lengths, rewards,
+                                     tokens, frames)
+
+    @classmethod
+    def from_packed(cls, p: "replay_io.PackedGames", device="cuda", capacity: Optional[int] = None,
+                    max_actions: Optional[int] = None) -> "GameBuffer":
+        """A buffer holding the games of ``p``.  With ``p``'s capacity every game returns to the slot it had
+        (first_slot = (ring[0] - G) mod C, games_added = ring[1]; the stored games of a ring the adds filled are
+        consecutive), so flat move indices stay what they were.  With another capacity the buffer is what adding the
+        games oldest first to an empty buffer leaves, the newest ``capacity`` of them when it holds fewer.  A game
+        longer than ``max_actions`` is refused."""
+        C = p.C if capacity is None else int(capacity)
+        L = p.L if max_actions is None else int(max_actions)
+        if p.G and int(p.lengths.max()) > L:
+            raise ValueError(f"a stored game has {int(p.lengths.max())} moves, max_actions={L}")
+        buf = cls(C, L, p.T, p.S, device)
+        if C == p.C:
+            first, added, row0, g0 = (p.ring[0] - p.G) % C, p.ring[1], 0, 0
+            if p.G == 0:  # add_packed of no games is a no-op: the ring words of an empty ring that had games
+                buf.ring.copy_(torch.tensor(p.ring, dtype=torch.int64))
+        else:
+            g0 = max(0, p.G - C)
+            first, added, row0 = None, None, int(p.starts()[g0])
+        buf.add_packed(torch.from_numpy(p.frames[row0:]), torch.from_numpy(p.tokens[row0:]),
+                       torch.from_numpy(p.rewards[row0:]), torch.from_numpy(p.lengths[g0:]), first_slot=first,
+                       games_added=added)
+        return buf
+
+    def save(self, path) -> None:
+        """The stored games to one file (``replay_io``: a header, then lengths, rewards, tokens, frames)."""
+        replay_io.save_games(path, self.packed())
+
+    @classmethod
+    def load(cls, path, device="cuda", capacity: Optional[int] = None, max_actions: Optional[int] = None) -> "GameBuffer":
+        """The buffer ``save`` wrote (``from_packed``: the same slots at the saved capacity)."""
+        return cls.from_packed(replay_io.load_games(path), device, capacity, max_actions)
 
 
 def _take(index: Optional[torch.Tensor], pos: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -227,6 +289,64 @@ class TensorGameData:
         played buffer, the first game with the greatest final reward to the best buffer.  Asynchronous."""
         self.played.add_games(states, policy, rewards, lengths)
         self.best.add_best(states, policy, rewards, lengths)
+
+    # ---- disk -----------------------------------------------------------------------------------------------------
+    def _targets_hash(self, targets) -> int:
+        h = ops.state_hash(targets).cpu().numpy()
+        return int(np.bitwise_xor.reduce(h)) if h.size else 0
+
+    def save(self, path, demos: bool = True) -> None:
+        """The dataset to one file (``replay_io.save_dataset``): both buffers, the sizes and fractions, the epoch's four
+        index arrays (``kind`` / ``src`` are recomposed at load), the device generator's state and, unless ``demos`` is
+        false, the demos.  Without them the caller passes the same demos to ``load``."""
+        host = lambda t: None if t is None else t.cpu().numpy()
+        replay_io.save_dataset(path, dict(
+            len_data=self.len_data, dim_t=self.dim_t, shift=self.shift, R=self.R, S=self.S,
+            n_demos=self.tokens.shape[0], fract_synth=self.fract_synth, fract_best=self.fract_best,
+            targets_hash=self._targets_hash(self.targets), is_synth=host(self.is_synth),
+            index_synth=host(self.index_synth), index_played=host(self.index_played), index_best=host(self.index_best),
+            generator=self.generator.get_state().numpy(), played=self.played.packed(), best=self.best.packed(),
+            tokens=host(self.tokens) if demos else None, targets=host(self.targets) if demos else None))
+
+    @classmethod
+    def load(cls, path, device="cuda", tokens=None, targets=None) -> "TensorGameData":
+        """The dataset ``save`` wrote, on ``device``: its next ``resample_buffer_indexes`` and its batches are those of
+        the object that was saved.  ``tokens`` / ``targets`` (device tensors) are needed exactly when the file holds no
+        demos; their shapes and the hash of the targets must match what the file recorded."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise TensorGameError("TensorGameData", -1, "the demos must live on a ROCm device; there is no CPU path")
+        d = replay_io.load_dataset(path)
+        self = cls.__new__(cls)
+        self.device = dev
+        self.S, self.R, self.dim_t, self.shift = d["S"], d["R"], d["dim_t"], d["shift"]
+        if d["tokens"] is not None:
+            if tokens is not None or targets is not None:
+                raise ValueError(f"{path} holds its demos; pass none")
+            tokens, targets = torch.from_numpy(d["tokens"]).to(dev), torch.from_numpy(d["targets"]).to(dev)
+        else:
+            if tokens is None or targets is None:
+                raise ValueError(f"{path} holds no demos; pass the tokens and targets it was saved with")
+            want = ((d["n_demos"], self.R, 3 * self.S), (d["n_demos"], self.S, self.S, self.S))
+            if (tuple(tokens.shape), tuple(targets.shape)) != want or tokens.device != dev or targets.device != dev:
+                raise ValueError(f"the demos must be {want[0]} and {want[1]} on {dev}, got {tuple(tokens.shape)} and "
+                                 f"{tuple(targets.shape)} on {tokens.device}")
+            if self._targets_hash(targets) != d["targets_hash"]:
+                raise ValueError(f"the targets are not the ones {path} was saved with")
+        self.tokens, self.targets = tokens, targets
+        self.n_synth, self.len_data = d["n_demos"] * self.R, d["len_data"]
+        self.played = GameBuffer.from_packed(d["played"], dev)
+        self.best = GameBuffer.from_packed(d["best"], dev)
+        self.status = torch.zeros((1,), dtype=torch.uint32, device=dev)
+        self.generator = torch.Generator(device=dev)
+        self.generator.set_state(torch.from_numpy(d["generator"].copy()))
+        self.fract_synth, self.fract_best = d["fract_synth"], d["fract_best"]
+        on_dev = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+        self.is_synth = on_dev(d["is_synth"])
+        self.index_synth, self.index_played, self.index_best = (on_dev(d[k]) for k in (
+            "index_synth", "index_played", "index_best"))
+        self._compose()
+        return self
 
     # ---- items -------------------------------------------------------------------------------------------------------
     def __len__(self) -> int:

@@ -218,6 +218,27 @@ class FusedTrainer:
         """A ``FusedAlphaTensor`` on the trainer's inference blob (shared: every train_step updates it)."""
         return FusedAlphaTensor(self.config, self._blob, n_samples or self.n_samples)
 
+    def checkpoint(self) -> dict:
+        """Everything a resumed trainer needs, as host tensors and plain scalars (``torch.save`` it; it loads with
+        ``weights_only=True``): the configuration, ``params`` (the training vector, bit for bit), ``pos_fix``, the
+        dropout probability, both loss weights, ``n_samples``, the dropout ``seed`` and the ``calls`` counter that keys
+        the next mask.  A host copy."""
+        return {"config": dict(self.config), "params": self.params.detach().cpu(), "pos_fix": self.pos_fix.cpu(),
+                "dropout_p": self.dropout_p, "weight_pol": self.weight_pol, "weight_val": self.weight_val,
+                "n_samples": self.n_samples, "seed": self.seed, "calls": self.calls}
+
+    @classmethod
+    def from_checkpoint(cls, d: Mapping, device="cuda") -> "FusedTrainer":
+        """The trainer ``checkpoint`` described, on ``device``: its next ``train_step`` is the one the saved trainer
+        would have made."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise TensorGameError("FusedTrainer", -1, "a ROCm device is required; there is no CPU path")
+        tr = cls(d["config"], d["params"].to(dev), d["pos_fix"], d["dropout_p"], d["weight_pol"], d["weight_val"],
+                 d["n_samples"], d["seed"])
+        tr.calls = int(d["calls"])
+        return tr
+
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference-format weights (float32 CPU tensors; a host copy)."""
         return unpack_weights(self.params.detach(), self.config, self.pos_fix)
