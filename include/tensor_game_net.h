@@ -74,8 +74,8 @@ extern "C" {
 #define TG_NET_WIDE_S 9
 #define TG_NET_WIDE_MAX_STEPS 27
 
-/* And a second one: the 4x4 matmul tensor, S = 16 exactly, with n_steps up to TG_NET_WIDE2_MAX_STEPS (= 3S); inference
- * only (tg_net_train_check refuses it).  A whole game's torso does not fit there (344 KiB at the training app's
+/* And a second one: the 4x4 matmul tensor, S = 16 exactly, with n_steps up to TG_NET_WIDE2_MAX_STEPS (= 3S); training
+ * there goes through tensor_game_train_sliced.h (tg_net_train_check refuses the size).  A whole game's torso does not fit there (344 KiB at the training app's
  * configuration), and does not have to: the first grid index is a batch index through every attention block of the
  * torso, so tg_net_torso runs one workgroup per (game, slice i) on the 3S rows (i, m, j) of the three grids.  The torso
  * term of the LDS check is that slice plan (3S x c grids, four 2S x c buffers, one head's q/k/v or the MLP's hidden

@@ -63,8 +63,8 @@ extern "C" {
  * training app's configuration), so there the torso runs each pair's attention block over a chunk of its S independent
  * sequences at a time (the fewest chunks that fit: 3 of 3 sequences, 116 KiB, at that configuration), and the decoder's
  * cross-attention keeps no keys or values (scores (Wk_h^T q) . y_j, output Wv_h (sum_j a_j y_j), 148 KiB); a
- * configuration fits when one sequence at a time does.  S = TG_NET_WIDE2_S is inside tg_net_check's family for inference
- * only: training there is not built and every configuration of that size is refused here.  Host only. */
+ * configuration fits when one sequence at a time does.  S = TG_NET_WIDE2_S is inside tg_net_check's family, and every
+ * configuration of that size is refused here: training there goes through tensor_game_train_sliced.h.  Host only. */
 int tg_net_train_check(const tg_net_config* cfg);
 
 /* *bytes = the workspace tg_net_loss_grad needs for B >= 1 games (grad or not):

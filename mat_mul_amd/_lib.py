@@ -135,6 +135,12 @@ TRAIN_SIGNATURES = {
     "tg_net_loss_grad": [_p, _p, _p, _p, _i, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_float, _u64, _u64, _p, _p, _p,
                          _i64, _p, _p, _p, _p],
 }
+# name -> argtypes; every symbol include/tensor_game_train_sliced.h declares (the same three at S = TG_NET_WIDE2_S)
+TRAIN_SLICED_SIGNATURES = {
+    "tg_net_train_sliced_check": TRAIN_SIGNATURES["tg_net_train_check"],
+    "tg_net_train_sliced_workspace_size": TRAIN_SIGNATURES["tg_net_train_workspace_size"],
+    "tg_net_loss_grad_sliced": TRAIN_SIGNATURES["tg_net_loss_grad"],
+}
 # name -> argtypes; every symbol include/tensor_game_rollout.h declares
 ROLLOUT_SIGNATURES = {
     "tg_rollout_advance": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -162,7 +168,7 @@ NET_LIMITS = {"S": 5, "T": 8, "dim_s": 4, "c": 32, "torso_layers": 16, "torso_he
 TG_NET_MAX_SAMPLES = 64
 # the first state size outside NET_LIMITS["S"]: the 3x3 matmul tensor, with its own n_steps bound
 TG_NET_WIDE_S, TG_NET_WIDE_MAX_STEPS = 9, 27
-# and the second: the 4x4 matmul tensor, inference only (the torso runs by slices there)
+# and the second: the 4x4 matmul tensor (the torso runs by slices there; training through tensor_game_train_sliced.h)
 TG_NET_WIDE2_S, TG_NET_WIDE2_MAX_STEPS = 16, 48
 
 
@@ -202,7 +208,7 @@ def _load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
                            **REPLAY_IO_SIGNATURES,
-                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **ROLLOUT_SIGNATURES,
+                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES, **ROLLOUT_SIGNATURES,
                            **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)

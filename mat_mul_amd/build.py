@@ -39,6 +39,7 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "tensor_game.h", 
                                             PKG.parent / "include" / "tensor_game_replay_io.h",
                                             PKG.parent / "include" / "tensor_game_net.h",
                                             PKG.parent / "include" / "tensor_game_train.h",
+                                            PKG.parent / "include" / "tensor_game_train_sliced.h",
                                             PKG.parent / "include" / "tensor_game_rollout.h",
                                             PKG.parent / "include" / "tensor_game_rollout_masked.h",
                                             PKG.parent / "include" / "tensor_game_rollout_slots.h"]

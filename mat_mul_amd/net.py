@@ -10,8 +10,8 @@ head) -- from one packed float32 weight blob.
     oo, zz0 = net.logits(xx, ss, g_action)                  # teacher-forced, PolicyHead.fwd_train's forward
     states, policy, rewards, lengths = search.actor_prediction(net.policy(seed=0), start, 8, n_sim=16, ...)
 
-Supported: dim_3d <= 5, or exactly 9 (3x3 matmul) or 16 (4x4 matmul, n_steps <= 48, inference only: the torso then
-runs one workgroup per (game, slice) instead of one per game), inside the TG_NET_MAX_* bounds and the LDS plans of the
+Supported: dim_3d <= 5, or exactly 9 (3x3 matmul) or 16 (4x4 matmul, n_steps <= 48: the torso then runs one
+workgroup per (game, slice) instead of one per game, and training goes through ``train.SlicedTrainer``), inside the TG_NET_MAX_* bounds and the LDS plans of the
 header; ``check_config`` names the bound otherwise.
 
 The draws follow the header's sampling rule (Philox keyed by seed, counter (game, call, sample, step block)), not

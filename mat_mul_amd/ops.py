@@ -25,6 +25,7 @@ __all__ = [
     "replay_pack", "replay_add_packed",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
+    "net_train_sliced_check", "net_train_sliced_workspace_size", "net_loss_grad_sliced",
     "rollout_check", "rollout_records", "rollout_advance",
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
 ]
@@ -936,11 +937,15 @@ def net_train_check(cfg) -> None:
     call("tg_net_train_check", C.byref(cfg))
 
 
+def _workspace_size(symbol: str, cfg, B: int) -> int:
+    out = C.c_int64(0)
+    call(symbol, C.byref(cfg), int(B), C.byref(out))
+    return int(out.value)
+
+
 def net_train_workspace_size(cfg, B: int) -> int:
     """Bytes of workspace tg_net_loss_grad needs for B games."""
-    out = C.c_int64(0)
-    call("tg_net_train_workspace_size", C.byref(cfg), int(B), C.byref(out))
-    return int(out.value)
+    return _workspace_size("tg_net_train_workspace_size", cfg, B)
 
 
 def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad=None, losses=None,
@@ -952,12 +957,20 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
     int8, scalars float32 (B,dim_s), g_action int8 (B,n_steps), g_value float32 (B,1), workspace uint8 of at least
     net_train_workspace_size bytes.  grad (like theta) None means a loss-only call.  keep_in / keep_out: uint8
     (B, blocks, 2, n_steps, W) or None.  Returns (losses float32 [2], status int32 [1]); no host sync."""
+    return _loss_grad("net_loss_grad", "tg_net_loss_grad", "tg_net_train_workspace_size", cfg, theta, pos_fix, frames,
+                      scalars, g_action, g_value, workspace, grad, losses, status, weight_pol, weight_val, dropout_p, seed,
+                      call_idx, keep_in, keep_out)
+
+
+def _loss_grad(fn, symbol, size_symbol, cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad, losses,
+               status, weight_pol, weight_val, dropout_p, seed, call_idx, keep_in, keep_out):
+    """The argument rules and the launch of net_loss_grad and net_loss_grad_sliced, which differ in the C symbols."""
     dev = _net_blob(cfg, theta)
-    B = _net_frames(cfg, frames, dev, "net_loss_grad")
+    B = _net_frames(cfg, frames, dev, fn)
     if B < 1:
-        raise TensorGameError("net_loss_grad", -1, "B must be at least 1")
+        raise TensorGameError(fn, -1, "B must be at least 1")
     if not 0.0 <= float(dropout_p) < 1.0:
-        raise TensorGameError("net_loss_grad", -1, f"dropout_p={dropout_p} outside [0, 1)")
+        raise TensorGameError(fn, -1, f"dropout_p={dropout_p} outside [0, 1)")
     frames = frames.contiguous()
     pos_fix = _flag(pos_fix, (cfg.n_steps, cfg.W), torch.float32, dev, "pos_fix")
     scalars = _flag(scalars, (B, cfg.dim_s), torch.float32, dev, "scalars")
@@ -969,17 +982,39 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
     grad = _flag(grad, tuple(theta.shape), torch.float32, dev, "grad")
     losses = _out(losses, (2,), torch.float32, dev, "losses")
     status = _out(status, (1,), torch.int32, dev, "status")
-    need = net_train_workspace_size(cfg, B)
+    need = _workspace_size(size_symbol, cfg, B)
     _need_gpu(workspace, "workspace")
     if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
             workspace.numel() < need or workspace.device != dev:
-        raise TensorGameError("net_loss_grad", -1, f"workspace must be contiguous uint8 of at least {need} bytes on "
+        raise TensorGameError(fn, -1, f"workspace must be contiguous uint8 of at least {need} bytes on "
                               f"{dev}, got {workspace.dtype} {tuple(workspace.shape)} on {workspace.device}")
-    _launch(dev, "tg_net_loss_grad", C.byref(cfg), _ptr(theta), _ptr(pos_fix), _ptr(frames),
+    _launch(dev, symbol, C.byref(cfg), _ptr(theta), _ptr(pos_fix), _ptr(frames),
             1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(g_action), _ptr(g_value), B,
             float(weight_pol), float(weight_val), float(dropout_p), _u64(seed), _u64(call_idx), _ptr(keep_in),
             _ptr(keep_out), _ptr(workspace), workspace.numel(), _ptr(grad), _ptr(losses), _ptr(status))
     return losses, status
+
+
+# ---- include/tensor_game_train_sliced.h: the same three entries at S = TG_NET_WIDE2_S ---------------------------------
+def net_train_sliced_check(cfg) -> None:
+    """Raise TensorGameError (naming the bound) unless ``cfg`` is in the sliced training family
+    (tg_net_train_sliced_check): S = 16 and both LDS plans within 160 KiB."""
+    call("tg_net_train_sliced_check", C.byref(cfg))
+
+
+def net_train_sliced_workspace_size(cfg, B: int) -> int:
+    """Bytes of workspace tg_net_loss_grad_sliced needs for B games."""
+    return _workspace_size("tg_net_train_sliced_workspace_size", cfg, B)
+
+
+def net_loss_grad_sliced(cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad=None, losses=None,
+                         status=None, weight_pol: float = 1.0, weight_val: float = 1000.0, dropout_p: float = 0.0,
+                         seed: int = 0, call_idx: int = 0, keep_in=None, keep_out=None):
+    """net_loss_grad at S = TG_NET_WIDE2_S (tg_net_loss_grad_sliced): the same arguments and results, workspace of at
+    least net_train_sliced_workspace_size bytes."""
+    return _loss_grad("net_loss_grad_sliced", "tg_net_loss_grad_sliced", "tg_net_train_sliced_workspace_size", cfg, theta,
+                      pos_fix, frames, scalars, g_action, g_value, workspace, grad, losses, status, weight_pol, weight_val,
+                      dropout_p, seed, call_idx, keep_in, keep_out)
 
 
 # ---- sampled policy rollouts (include/tensor_game_rollout.h) --------------------------------------------------------

@@ -309,7 +309,7 @@ def save_run(path, trainer, optimizer, data, generators: Optional[Mapping[str, t
 def load_run(path, device) -> RunState:
     """The run ``save_run`` wrote, rebuilt on ``device``.  ``trainer.pt`` is read with ``weights_only=True``."""
     from .replay import TensorGameData
-    from .train import FusedTrainer
+    from .train import FusedTrainer, SlicedTrainer
 
     dev = _gpu(device, "load_run")
     path = Path(path)
@@ -318,5 +318,7 @@ def load_run(path, device) -> RunState:
     for name, state in d["generators"].items():
         gens[name] = torch.Generator(device=dev)
         gens[name].set_state(state)
-    return RunState(FusedTrainer.from_checkpoint(d["trainer"], dev), d["optimizer"],
+    # the class the checkpoint names; a file without the key is a FusedTrainer's
+    cls = {"fused": FusedTrainer, "sliced": SlicedTrainer}[d["trainer"].get("kind", "fused")]
+    return RunState(cls.from_checkpoint(d["trainer"], dev), d["optimizer"],
                     TensorGameData.load(path / "data.tgd", dev), gens, d["extra"])

@@ -27,7 +27,7 @@ from . import ops
 from ._lib import TensorGameError
 from .net import _P, CONFIG_FIELDS, FusedAlphaTensor, check_config, infer_config, pack_weights
 
-__all__ = ["FusedTrainer", "unpack_weights", "blob_layout"]
+__all__ = ["FusedTrainer", "SlicedTrainer", "unpack_weights", "blob_layout"]
 
 
 def _mha_layout(p: str, c1: int, c2: int, H: int, d: int, ff: int, out: list) -> None:
@@ -109,11 +109,16 @@ def unpack_weights(blob, cfg: Mapping[str, int], pos_fix, folded: bool = False) 
 class FusedTrainer:
     """The training step of a reference ``AlphaTensor`` on one flat float32 parameter vector on the device."""
 
+    # the library entries a trainer calls (a subclass names others): the family check, the workspace size, the loss
+    _check = staticmethod(ops.net_train_check)
+    _workspace_size = staticmethod(ops.net_train_workspace_size)
+    _loss_grad = staticmethod(ops.net_loss_grad)
+
     def __init__(self, cfg: Mapping[str, int], theta: torch.Tensor, pos_fix: torch.Tensor, dropout_p: float = 0.5,
                  weight_pol: float = 1.0, weight_val: float = 1000.0, n_samples: int = 4, seed: int = 0):
         self.config = {k: int(cfg[k]) for k in CONFIG_FIELDS}
         self.c = check_config(self.config)
-        ops.net_train_check(self.c)
+        self._check(self.c)
         n = ops.net_weights_size(self.c)
         if theta.numel() != n or theta.dtype != torch.float32 or not theta.is_cuda:
             raise TensorGameError("FusedTrainer", -1, f"theta must be {n} float32 on a ROCm device, got {theta.dtype} "
@@ -161,7 +166,7 @@ class FusedTrainer:
     def workspace(self, B: int) -> torch.Tensor:
         ws = self._ws.get(B)
         if ws is None:
-            self._ws = {B: torch.empty(ops.net_train_workspace_size(self.c, B), dtype=torch.uint8, device=self.device)}
+            self._ws = {B: torch.empty(self._workspace_size(self.c, B), dtype=torch.uint8, device=self.device)}
             ws = self._ws[B]
         return ws
 
@@ -180,10 +185,10 @@ class FusedTrainer:
         if dropout_p > 0 or keep_in is not None:
             self.calls += 1
         losses = torch.empty(2, dtype=torch.float32, device=self.device)
-        ops.net_loss_grad(self.c, self.params.detach(), self.pos_fix, state, scalar, action, reward,
-                          self.workspace(state.shape[0]), grad=grad, losses=losses, status=self.status,
-                          weight_pol=self.weight_pol, weight_val=self.weight_val, dropout_p=dropout_p, seed=self.seed,
-                          call_idx=call, keep_in=keep_in, keep_out=keep_out)
+        self._loss_grad(self.c, self.params.detach(), self.pos_fix, state, scalar, action, reward,
+                        self.workspace(state.shape[0]), grad=grad, losses=losses, status=self.status,
+                        weight_pol=self.weight_pol, weight_val=self.weight_val, dropout_p=dropout_p, seed=self.seed,
+                        call_idx=call, keep_in=keep_in, keep_out=keep_out)
         return losses[0], losses[1]
 
     def loss_and_grad(self, state, scalar, action, reward, keep_in=None, keep_out=None):
@@ -242,3 +247,17 @@ class FusedTrainer:
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference-format weights (float32 CPU tensors; a host copy)."""
         return unpack_weights(self.params.detach(), self.config, self.pos_fix)
+
+
+class SlicedTrainer(FusedTrainer):
+    """``FusedTrainer`` at the 4x4 matmul tensor (dim_3d = 16), the size ``FusedTrainer`` refuses: the same constructor,
+    classmethods and methods on include/tensor_game_train_sliced.h's entries (``tg_net_loss_grad_sliced``), which cut
+    the torso by slices and the decoder's cross-attention by chunks of positions.  Every other size is refused here."""
+
+    _check = staticmethod(ops.net_train_sliced_check)
+    _workspace_size = staticmethod(ops.net_train_sliced_workspace_size)
+    _loss_grad = staticmethod(ops.net_loss_grad_sliced)
+
+    def checkpoint(self) -> dict:
+        """``FusedTrainer.checkpoint`` with ``"kind": "sliced"``, by which ``replay_io.load_run`` builds this class."""
+        return dict(super().checkpoint(), kind="sliced")

@@ -9,7 +9,9 @@ One process, one GPU.  Per B in {256, 1024, 4096}: FusedTrainer.loss_and_grad, t
 events around the call after warm-up; median, p10 and p90 in microseconds.  --fused-only runs the fused calls alone (for
 a kernel-trace run); --kernel-stats merges a rocprofv3 --stats CSV into an existing OUT_DIR/r09_train.json.
 Writes OUT_DIR/r09_train.json.  --config picks another configuration of net_ref.CONFIGS or tests/net_s9_ref.CONFIGS
-(a9, b9: S = 9); the file is then OUT_DIR/r09_train_<config>.json.
+(a9, b9: S = 9); the file is then OUT_DIR/r09_train_<config>.json.  --config a16 or b16 (tests/net_s16_ref.CONFIGS,
+S = 16) times SlicedTrainer (include/tensor_game_train_sliced.h) at B in {16, 256} and writes
+OUT_DIR/r13_train_<config>.json.
 """
 from __future__ import annotations
 
@@ -27,9 +29,10 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from mat_mul_amd import FusedTrainer  # noqa: E402
+from mat_mul_amd import FusedTrainer, SlicedTrainer  # noqa: E402
 from net_ref import CONFIGS, make_weights  # noqa: E402
 from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
+from net_s16_ref import CONFIGS as CONFIGS_S16  # noqa: E402
 from train_ref import TrainRef, keep_mask, make_batch, multipliers  # noqa: E402
 
 DEV = "cuda:0"
@@ -74,22 +77,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--kernel-stats")
-    ap.add_argument("--config", default="a", choices=sorted({**CONFIGS, **CONFIGS_S9}))
+    ap.add_argument("--config", default="a", choices=sorted({**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}))
     args = ap.parse_args()
-    out = Path(args.out) / ("r09_train.json" if args.config == "a" else f"r09_train_{args.config}.json")
+    sliced = args.config in CONFIGS_S16
+    out = Path(args.out) / ("r09_train.json" if args.config == "a" else
+                            f"{'r13' if sliced else 'r09'}_train_{args.config}.json")
     if args.kernel_stats:
         res = json.loads(out.read_text())
         res["kernel_stats"] = kernel_stats(args.kernel_stats)
         out.write_text(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res["kernel_stats"], indent=1))
         return
-    cfg = {**CONFIGS, **CONFIGS_S9}[args.config]
+    cfg = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}[args.config]
     sd = make_weights(cfg, 1)
-    tr = FusedTrainer.from_state_dict(sd, dropout_p=P_DROP, device=DEV)
+    tr = (SlicedTrainer if sliced else FusedTrainer).from_state_dict(sd, dropout_p=P_DROP, device=DEV)
     opt = torch.optim.AdamW([tr.params], lr=1e-4)
     res = {"config": args.config, "dropout_p": P_DROP, "torch": torch.__version__,
            "device": torch.cuda.get_device_name(0), "rows": []}
-    for B in (256, 1024, 4096):
+    for B in ((16, 256) if sliced else (256, 1024, 4096)):
         batch = tuple(torch.from_numpy(x).to(DEV) for x in make_batch(cfg, B, B))
         row = {"B": B}
         row["fused_loss_grad"] = timed(lambda: tr.loss_and_grad(*batch), args.reps, args.warmup)
