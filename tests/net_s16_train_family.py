@@ -11,6 +11,8 @@ tests.
 * ``sliced_bytes``: the (torso, decoder) byte counts tg_net_train_sliced_check compares with 160 KiB (the decoder at
   nq = 1) and prints when it refuses;
 * ``workspace_bytes(m, B)``: the header's workspace formula, each part rounded up to 256 bytes;
+* ``torso_runs(B)`` and ``decoder_runs(B)``: the runs of (game, slice) units of launch 3's Pt workgroups and the runs of
+  games of launch 2's Pd workgroups;
 * ``ROWS``: name -> configuration of every accepted row the tests use: a16 and b16 of net_s16_ref, ones16, odd16, c13
   and t8 of net_s16_family.FAMILY16 (all four fit), and ``tail16``, added here because none of the others reaches the one
   plan-derived loop, the cross-attention's chunks, with a partial last chunk: a16 and b16 run six chunks of 8, and
@@ -94,5 +96,20 @@ def workspace_bytes(m, B):
     return sum(-(-4 * p // 256) * 256 for p in parts)
 
 
+def runs(n, P):
+    """[n*p/P, n*(p+1)/P) for p < P: the contiguous runs the kernels cut n items into."""
+    return [(n * p // P, n * (p + 1) // P) for p in range(P)]
+
+
+def torso_runs(B, S=16):
+    """(u0, u1) per workgroup of launch 3: the units u = g * S + i of Pt = min(B * S, PARTIALS) workgroups."""
+    return runs(B * S, min(B * S, PARTIALS))
+
+
+def decoder_runs(B):
+    """(g0, g1) per workgroup of launch 2: the games of Pd = min(B, PARTIALS) workgroups."""
+    return runs(B, min(B, PARTIALS))
+
+
 __all__ = ["ROWS", "LDS", "PARTIALS", "dims", "slice_tplan", "sliced_dplan", "decoder_chunk", "chunks", "sliced_bytes",
-           "n_theta", "workspace_bytes"]
+           "n_theta", "workspace_bytes", "torso_runs", "decoder_runs"]

@@ -25,7 +25,9 @@ from mat_mul_amd.train import unpack_weights
 import guarded_buffers as G
 import net_family as F
 from net_ref import P, Ref, dims
-from train_ref import TrainRef, bad_tokens, err, keep_mask, multipliers, two_sided_batch, value_branches, within
+from train_ref import GuardedCall as Call
+from train_ref import (TrainRef, bad_tokens, compare_grads, err, keep_mask, multipliers, two_sided_batch,
+                       value_branches, within)
 from test_train_paths_cpu import B, ROWS_BRANCH, ROWS_WEIGHTS, SEED_BATCH, SEED_BRANCH, weights
 
 pytestmark = pytest.mark.gpu
@@ -54,19 +56,7 @@ def compare(name, what, got, batch, **kw):
     cfg = F.train_config(name)
     ref = TrainRef(weights(name), cfg, device=DEV).loss_grad(*batch, **kw)
     ref32 = TrainRef(weights(name), cfg, device=DEV, dtype=torch.float32).loss_grad(*batch, **kw)
-    assert sorted(ref[2]) == sorted(got[2])
-    pairs = [("l_pol", got[0], ref[0], ref32[0]), ("l_val", got[1], ref[1], ref32[1])]
-    pairs += [(k, got[2][k], g, ref32[2][k]) for k, g in ref[2].items()]
-    bad, own, own32 = {}, 0.0, 0.0
-    for key, value, want, want32 in pairs:
-        e, e32 = err(value, want), err(want32, want)
-        top = float(np.abs(want).max())
-        if top > 0.0:
-            own, own32 = max(own, e / top), max(own32, e32 / top)
-        if not within(e, TOL_TRAIN, want, lambda: e32, f"{name} {what} {key}"):
-            bad[key] = e
-    print(f"TRAIN-PATHS-ERR {name} {what} fused {own:.3g} eager32 {own32:.3g}")
-    assert not bad, bad
+    compare_grads("TRAIN-PATHS-ERR", f"{name} {what}", got, ref, ref32, TOL_TRAIN)
     return ref
 
 
@@ -172,43 +162,8 @@ def test_float32_frames_equal_int8_frames_bit_for_bit(name):
 
 
 # ---- 6. the workspace and the output buffers -------------------------------------------------------------------------
-class Call:
-    """ops.net_loss_grad on a trainer's weights with the workspace, grad, losses, status and keep_out each between
-    guard bytes; ``ws_bytes`` defaults to exactly net_train_workspace_size."""
-
-    def __init__(self, tr, batch, ws=None, fill=0):
-        self.tr, self.batch, m = tr, batch, tr.config
-        b = batch[0].shape[0]
-        self.bufs = {}
-        if ws is None:
-            ws = self.guarded("workspace", (ops.net_train_workspace_size(tr.c, b),), torch.uint8)
-            ws.fill_(fill)
-        self.ws = ws
-        self.grad = self.guarded("grad", tuple(tr.params.shape), torch.float32)
-        self.losses = self.guarded("losses", (2,), torch.float32)
-        self.status = self.guarded("status", (1,), torch.int32)
-        self.keep = self.guarded("keep_out", (b, m["blocks"], 2, m["n_steps"], m["W"]), torch.uint8)
-
-    def guarded(self, what, shape, dtype):
-        self.bufs[what], t = G.guarded(shape, dtype)
-        return t
-
-    def run(self, grad=True):
-        """(grad or None, losses) of one call; the outputs start as NaN."""
-        self.grad.fill_(float("nan"))
-        self.losses.fill_(float("nan"))
-        tr = self.tr
-        ops.net_loss_grad(tr.c, tr.params.detach(), tr.pos_fix, *self.batch, self.ws, grad=self.grad if grad else None,
-                          losses=self.losses, status=self.status, dropout_p=0.5, seed=3, call_idx=4,
-                          keep_out=self.keep)
-        torch.cuda.synchronize()
-        for what, buf in self.bufs.items():
-            G.check_flat(buf, what)
-        assert int(self.status[0]) == 0 and torch.isfinite(self.losses).all()
-        assert not grad or torch.isfinite(self.grad).all()
-        return self.grad.clone() if grad else None, self.losses.clone()
-
-
+# Call: ops.net_loss_grad on a trainer's weights with the workspace, grad, losses, status and keep_out each between guard
+# bytes; the workspace defaults to exactly net_train_workspace_size bytes.
 @pytest.mark.parametrize("name", ["odd", "c5"])
 def test_exact_workspace_between_guards_and_a_workspace_of_nans(name):
     tr = trainer(name)

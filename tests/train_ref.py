@@ -8,11 +8,13 @@
   ``two_sided_batch``: rewards on both sides of the random networks' quantiles, inside and outside the Huber kink;
   ``bad_tokens``: a batch's actions with out-of-range entries and the rows that hold them;
 * ``value_branches``: how a batch's (game, quantile) pairs fall on the quantile loss's four branches;
-* ``err`` and ``within``: the suite's per-tensor bound.
+* ``err`` and ``within``: the suite's per-tensor bound; ``compare_grads``: losses and every gradient tensor under it;
+* ``GuardedCall``: a trainer's loss entry with the workspace and every output between guard bytes.
 """
 import numpy as np
 import torch
 
+import guarded_buffers as G
 from net_ref import P, Ref, dims
 from oracle import tensor_game as O
 
@@ -201,5 +203,62 @@ def within(e, tol, ref, f32_err, what):
     return e <= 2.0 * e32
 
 
+def compare_grads(tag, what, got, ref, ref32, tol):
+    """got = (l_pol, l_val, {name: gradient}) of the fused kernels against ref, the same of a float64 TrainRef, under the
+    suite's bound (``within``, with ref32, the same of a float32 TrainRef, as the eager float32 restatement).  Prints
+    ``tag what fused .. eager32 ..``: the worst error of a tensor over that tensor's own max |ref| (no floor of 1)."""
+    assert sorted(ref[2]) == sorted(got[2])
+    pairs = [("l_pol", got[0], ref[0], ref32[0]), ("l_val", got[1], ref[1], ref32[1])]
+    pairs += [(k, got[2][k], g, ref32[2][k]) for k, g in ref[2].items()]
+    bad, own, own32 = {}, 0.0, 0.0
+    for key, value, want, want32 in pairs:
+        e, e32 = err(value, want), err(want32, want)
+        top = float(np.abs(want).max())
+        if top > 0.0:
+            own, own32 = max(own, e / top), max(own32, e32 / top)
+        if not within(e, tol, want, lambda: e32, f"{what} {key}"):
+            bad[key] = e
+    print(f"{tag} {what} fused {own:.3g} eager32 {own32:.3g}")
+    assert not bad, bad
+
+
+class GuardedCall:
+    """The loss entry of a trainer (FusedTrainer: ops.net_loss_grad, SlicedTrainer: ops.net_loss_grad_sliced) on the
+    trainer's weights with the workspace, grad, losses, status and keep_out each between guard bytes (guarded_buffers);
+    the workspace defaults to exactly the entry's workspace size for the batch, filled with ``fill`` bytes.  Dropout
+    0.5 with the internal keep rule (seed 3, call 4)."""
+
+    def __init__(self, tr, batch, ws=None, fill=0):
+        self.tr, self.batch, m = tr, batch, tr.config
+        b = batch[0].shape[0]
+        self.bufs = {}
+        if ws is None:
+            ws = self.guarded("workspace", (tr._workspace_size(tr.c, b),), torch.uint8)
+            ws.fill_(fill)
+        self.ws = ws
+        self.grad = self.guarded("grad", tuple(tr.params.shape), torch.float32)
+        self.losses = self.guarded("losses", (2,), torch.float32)
+        self.status = self.guarded("status", (1,), torch.int32)
+        self.keep = self.guarded("keep_out", (b, m["blocks"], 2, m["n_steps"], m["W"]), torch.uint8)
+
+    def guarded(self, what, shape, dtype):
+        self.bufs[what], t = G.guarded(shape, dtype)
+        return t
+
+    def run(self, grad=True):
+        """(grad or None, losses) of one call; the outputs start as NaN."""
+        self.grad.fill_(float("nan"))
+        self.losses.fill_(float("nan"))
+        tr = self.tr
+        tr._loss_grad(tr.c, tr.params.detach(), tr.pos_fix, *self.batch, self.ws, grad=self.grad if grad else None,
+                      losses=self.losses, status=self.status, dropout_p=0.5, seed=3, call_idx=4, keep_out=self.keep)
+        torch.cuda.synchronize()
+        for what, buf in self.bufs.items():
+            G.check_flat(buf, what)
+        assert int(self.status[0]) == 0 and torch.isfinite(self.losses).all()
+        assert not grad or torch.isfinite(self.grad).all()
+        return self.grad.clone() if grad else None, self.losses.clone()
+
+
 __all__ = ["TrainRef", "keep_mask", "multipliers", "make_batch", "two_sided_rewards", "two_sided_batch", "bad_tokens",
-           "value_branches", "rel_err", "err", "bound", "within"]
+           "value_branches", "rel_err", "err", "bound", "within", "compare_grads", "GuardedCall"]
