@@ -100,11 +100,11 @@ print("STEP_OK")
 '''
 
 
-def _run(script_text, tmp_path, marker, extra_env=None):
+def _run(script_text, tmp_path, marker, extra_env=None, args=()):
     script = tmp_path / "ab_case.py"
     script.write_text(script_text)
     env = dict(os.environ, TG_LIB_VARIANT="ab", **(extra_env or {}))
-    res = subprocess.run([sys.executable, str(script), str(ROOT)], env=env, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, str(script), str(ROOT), *args], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and marker in res.stdout, (res.stdout[-1000:], res.stderr[-3000:])
 
 
@@ -280,10 +280,84 @@ print("LANES_OK")
 def test_stream_lane_kernel_forced_at_small_batches(env_name, tmp_path):
     """Round 4: s4_stream_kernel_lanes (one game per lane, tokens double-buffered, counted waits over an exact number of
     stores) serves tg_step_stream_i8 from 57 344 games on; TG_STREAM_LANES forces it at every batch -- single games, ragged
-    units, shifts 1 / 2 / -1 (the last two leave the digit form: the whole wavefront takes the general form on its LDS
-    image), overflow, full-range tokens, ready words pre-set, released one by one and in bursts.  TG_STREAM_NO_LANES: the
-    four-lanes-per-game kernels on the same cases."""
+    units, shifts 1 / 2 / -1 (only -1 leaves the digit form -- shift 2 has the same limit of 119 as shift 1 --: there the
+    whole wavefront takes the general form on its LDS image), overflow, full-range tokens, ready words pre-set, released
+    one by one and in bursts.  TG_STREAM_NO_LANES: the four-lanes-per-game kernels on the same cases."""
     _run(LANES_SCRIPT, tmp_path, "LANES_OK", {env_name: "1"})
+
+
+WALK_SCRIPT = r'''
+import os, sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+from mat_mul_amd import ops, _lib
+import stream_walk as W
+from oracle.c_oracle import COracle
+assert _lib.AB_VARIANT
+DEV, S, mode = "cuda:0", 4, sys.argv[2]
+CO = COracle()
+def launch(st, ac, shift, want, want_done, want_ovf, gpu, what, pad=16):
+    B, K = st.shape[0], ac.shape[0]
+    n_units = -(-B // gpu)
+    try:
+        assert ops.step_stream_layout(B, S, DEV) == (n_units, gpu), what
+    except ops.TensorGameError:
+        assert mode == "lanes" and B > ops.step_stream_capacity(S, DEV)       # in rounds: units of 64 games
+    t = ops.alloc_states(B, S, DEV, pad_to=pad); t.copy_(torch.from_numpy(np.ascontiguousarray(st)))
+    ovf = torch.zeros(B, dtype=torch.uint8, device=DEV)
+    prog = torch.zeros(n_units, dtype=torch.int32, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    _, done = ops.step_stream(t, torch.from_numpy(np.ascontiguousarray(ac)).to(DEV), overflow=ovf, progress=prog, status=status, shift=shift)
+    torch.cuda.synchronize()
+    assert int(status[0]) == 0 and bool((prog == K).all()), what
+    for name, got, ref in (("state", t, want), ("done", done.T, want_done.T), ("overflow", ovf, want_ovf)):
+        bad = np.flatnonzero((got.cpu().numpy() != ref).reshape(B, -1).any(axis=1))
+        assert bad.size == 0, f"{what}: {name} of games {bad[:8].tolist()} ({bad.size} in all)"
+def tiled(a, B, axis):
+    return np.take(a, np.arange(B) % a.shape[axis], axis=axis)
+if mode in ("lanes", "teams"):
+    gpu, K, B0 = (64 if mode == "lanes" else 16), 19, 200
+    for shift in W.SHIFTS:
+        for lanes in (True, False):   # events placed by the whole-game norm, one trigger per wavefront; and the tiled kinds
+            st, ac = W.make_walk(S, B0, K, shift, W.walk_seed(S, shift), lanes=lanes)
+            want, want_done, want_ovf = W.trajectory(st, ac, shift)
+            for B in (1, 63, 64, 65, 200):   # (games are independent: a prefix of the batch has the prefix of its trajectory)
+                for pad in ((16, 48) if B == 200 else (16,)):
+                    launch(st[:B], ac[:, :B], shift, want[:B], want_done[:, :B], want_ovf[:B], gpu, (mode, shift, lanes, B, pad), pad)
+    if mode == "lanes":   # beyond every resident layout the lane kernel runs its units in rounds: the walk tiled across the batch
+        B, shift = ops.step_stream_capacity(S, DEV) + 37, 2
+        st, ac = W.make_walk(S, B0, K, shift, W.walk_seed(S, shift), lanes=True)
+        want, want_done, want_ovf = W.trajectory(st, ac, shift)
+        launch(tiled(st, B, 0), tiled(ac, B, 1), shift, tiled(want, B, 0), tiled(want_done, B, 1), tiled(want_ovf, B, 0), 64, "rounds")
+else:
+    # s4_stream_kernel<2>: the smallest batch the layout call gives 32 games per unit, made ragged in its last unit
+    lo, hi = 1, ops.step_stream_capacity(S, DEV)
+    assert ops.step_stream_layout(lo, S, DEV)[1] == 16 and ops.step_stream_layout(hi, S, DEV)[1] == 32
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if ops.step_stream_layout(mid, S, DEV)[1] == 16 else (lo, mid)
+    B = hi + 37 + (1 if (hi + 37) % 32 == 0 else 0)
+    assert ops.step_stream_layout(B, S, DEV) == (-(-B // 32), 32) and B % 32
+    K, B0 = 11, 203                                         # blocks of 4, 4, 3
+    for shift in (1, 0):
+        st, ac = W.make_walk(S, B0, K, shift, W.walk_seed(S, shift))
+        short = W.census_shortfalls(S, shift, W.census(S, shift, st, ac))
+        assert short == [], short                           # (on the CPU, before the launch)
+        st, ac = tiled(st, B, 0), tiled(ac, B, 1)
+        want, want_done, want_ovf = W.trajectory(st, ac, shift, step=CO.step_i8)
+        launch(st, ac, shift, want, want_done, want_ovf, 32, ("ng2", shift))
+print("WALK_OK")
+'''
+
+
+@pytest.mark.parametrize("env_name,mode", [("TG_STREAM_LANES", "lanes"), ("TG_STREAM_NO_LANES", "teams"), ("TG_STREAM_NO_LANES", "ng2")])
+def test_stream_walk_on_the_layouts_the_product_does_not_reach_at_small_batches(env_name, mode, tmp_path):
+    """The walks of tests/stream_walk.py (edges of the digit form across K steps) on the S = 4 kernels that the product
+    picks only at large batches.  lanes: s4_stream_kernel_lanes at B = 1 / 63 / 64 / 65 / 200 and six shifts, the events placed by
+    the whole-game norm with one game per wavefront that drags its 63 neighbours through the general form and back, and
+    once beyond every resident layout (units in rounds).  teams: the same cases on the four-lanes-per-game kernel.  ng2:
+    s4_stream_kernel<2>, which serves only what s4_stream_kernel<1> cannot keep resident and only under TG_STREAM_NO_LANES
+    -- the batch size comes from the layout call, K = 11 gives blocks of 4, 4, 3, the reference is the C oracle."""
+    _run(WALK_SCRIPT, tmp_path, "WALK_OK", {env_name: "1"}, args=(mode,))
 
 
 ROUNDS_SCRIPT = r'''
