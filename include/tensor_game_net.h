@@ -82,7 +82,9 @@ extern "C" {
  * rows or the 3S input rows, one head's 2S x 2S scores); the decoder term is the same plan as at every size, with
  * J = 768 keys in the cross-attention.  The training app's configuration at S = 16 (c 8, W 32, T 2, 8 torso layers,
  * n_steps 48) takes 21.5 KiB per slice and 158 KiB in the decoder (R = 4 samples per workgroup; 76 KiB at R = 1).  With
- * J > 256 keys the decoder's cross-attention softmax runs a 32-lane team per row, its partial sums in a fixed order. */
+ * J > 256 keys the decoder's cross-attention softmax runs a 32-lane team per row, its partial sums in a fixed order.
+ * The 5x5 matmul tensor, S = 25, is not in this family (tg_net_check refuses it): it has entries of its own in
+ * tensor_game_net_s25.h, with this header's conventions, configuration, blob and sampling rule. */
 #define TG_NET_WIDE2_S 16
 #define TG_NET_WIDE2_MAX_STEPS 48
 

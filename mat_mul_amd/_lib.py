@@ -128,6 +128,16 @@ NET_SIGNATURES = {
     "tg_net_logits": [_p, _p, _p, _p, _i64, _p, _p, _p, _p],
 }
 
+# name -> argtypes; every symbol include/tensor_game_net_s25.h declares (the same at S = TG_NET_WIDE3_S; torso and sample
+# are the masked forms)
+NET_S25_SIGNATURES = {
+    "tg_net_s25_check": NET_SIGNATURES["tg_net_check"],
+    "tg_net_s25_weights_size": NET_SIGNATURES["tg_net_weights_size"],
+    "tg_net_s25_torso": NET_SIGNATURES["tg_net_torso_masked"],
+    "tg_net_s25_sample": NET_SIGNATURES["tg_net_sample_masked"],
+    "tg_net_s25_logits": NET_SIGNATURES["tg_net_logits"],
+}
+
 # name -> argtypes; every symbol include/tensor_game_train.h declares
 TRAIN_SIGNATURES = {
     "tg_net_train_check": [_p],
@@ -170,6 +180,8 @@ TG_NET_MAX_SAMPLES = 64
 TG_NET_WIDE_S, TG_NET_WIDE_MAX_STEPS = 9, 27
 # and the second: the 4x4 matmul tensor (the torso runs by slices there; training through tensor_game_train_sliced.h)
 TG_NET_WIDE2_S, TG_NET_WIDE2_MAX_STEPS = 16, 48
+# the 5x5 matmul tensor has entries of its own (include/tensor_game_net_s25.h); tg_net_check refuses the size
+TG_NET_WIDE3_S, TG_NET_WIDE3_MAX_STEPS = 25, 75
 
 
 class NetConfig(C.Structure):
@@ -208,8 +220,8 @@ def _load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
                            **REPLAY_IO_SIGNATURES,
-                           **NET_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES, **ROLLOUT_SIGNATURES,
-                           **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
+                           **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
+                           **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -19,6 +19,10 @@
 //     that holds sample 0, on the position-0 output.
 //     At S = TG_NET_WIDE2_S (J = 768 keys) the cross-attention's softmax runs a 32-lane team per row
 //     (net_decode_kernel<true>); every other size keeps one thread per row and its token-order sums.
+//     At S = TG_NET_WIDE3_S (J = 1875 keys, include/tensor_game_net_s25.h) ln2(ee) once per block does not fit: there
+//     net_decode_kernel<true, true> keeps one copy of ee normalised without scale and bias and applies each block's where
+//     a row is consumed (the scale folded into the QK row, the bias constant over the keys of a softmax; the weighted sum
+//     of the copy by 32-lane teams, scale and bias at its end).  The torso runs by slices there as well.
 // Row mask (tg_net_torso_masked, tg_net_sample_masked): every workgroup of a game whose flags byte lacks one of the `need`
 // bits (net::active) returns before its first barrier and before any load of the game's inputs, and writes nothing.  The
 // test is uniform over the workgroup, and over the S slice workgroups / the `chunks` decoder workgroups of a game.
@@ -30,6 +34,7 @@
 
 #include "../../include/tensor_game.h"
 #include "../../include/tensor_game_net.h"
+#include "../../include/tensor_game_net_s25.h"
 #include "tg_device.h"
 #include "tg_host.h"
 #include "tg_net_common.h"
@@ -66,13 +71,15 @@ struct DecPlan {
   int wq, nsc;  // per-head strides of QK / YB and SC
 };
 
-__host__ __device__ inline DecPlan dec_plan(const tg_net_config& c, int R) {
+// shared_ln: ONE normalised copy of the game's ee for every policy block (net_decode_kernel<true, true>), J x c floats
+// where the plan otherwise holds ln2(ee) once per block
+__host__ __device__ inline DecPlan dec_plan(const tg_net_config& c, int R, bool shared_ln = false) {
   const int J = 3 * c.S * c.S, hd = c.heads * c.d;
   DecPlan p;
   p.wq = c.W > c.c ? c.W : c.c;
   p.nsc = J > c.n_steps ? J : c.n_steps;
   p.EEN = 0;
-  p.CACHE = p.EEN + c.blocks * J * c.c;
+  p.CACHE = p.EEN + (shared_ln ? 1 : c.blocks) * J * c.c;
   p.X = p.CACHE + R * c.blocks * c.n_steps * c.W;
   p.XB = p.X + R * c.W;
   p.XN = p.XB + R * c.W;
@@ -233,6 +240,44 @@ __device__ inline void softmax_rows_team(float* A, int rows, int n, int ld) {
   }
 }
 
+// The rows of X without a LayerNorm's scale and bias, z = (x - mean) * rstd: layernorm()'s two passes and its lanes.
+__device__ inline void normalise_rows(const float* X, int ldx, int R, int n, float* Y, int ldy) {
+  const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
+  for (int r = team; r < R; r += NT / 32) {
+    const float* x = X + r * ldx;
+    const float x0 = lane < n ? x[lane] : 0.f, x1 = lane + 32 < n ? x[lane + 32] : 0.f;
+    float s = x0 + x1;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) s += __shfl_xor(s, m, 32);
+    const float mean = s / static_cast<float>(n);
+    const float d0 = lane < n ? x0 - mean : 0.f, d1 = lane + 32 < n ? x1 - mean : 0.f;
+    float v = d0 * d0 + d1 * d1;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
+    const float rstd = 1.f / sqrtf(v / static_cast<float>(n) + 1e-5f);
+    if (lane < n) Y[r * ldy + lane] = d0 * rstd;
+    if (lane + 32 < n) Y[r * ldy + lane + 32] = d1 * rstd;
+  }
+}
+
+// Y[rh][i] = w[i] * (sum_j A[rh][j] * Z[j][i]) + b[i] for rh < rows, i < C: the cross-attention's weighted sum over the
+// shared normalised copy Z (J x C) with the block's LayerNorm scale and bias applied to the sum (the A[rh][.] sum to one).
+// A team of 32 lanes per (rh, i), the partial sums in the order of softmax_rows_team, so neither R nor the launch shape
+// reaches a row's result.
+__device__ inline void weighted_sum_team(const float* A, int lda, int rows, int J, const float* Z, int C,
+                                         const float* __restrict__ w, const float* __restrict__ b, float* Y, int ldy) {
+  const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
+  for (int o = team; o < rows * C; o += NT / 32) {
+    const int i = o % C, rh = o / C;
+    const float* a = A + rh * lda;
+    float s = 0.f;
+    for (int j = lane; j < J; j += 32) s = fmaf(a[j], Z[j * C + i], s);
+#pragma unroll
+    for (int x = 16; x >= 1; x >>= 1) s += __shfl_xor(s, x, 32);
+    if (lane == 0) Y[rh * ldy + i] = fmaf(w[i], s, b[i]);
+  }
+}
+
 // The tail of an attention block, from the heads' output O and the block's input XB (R rows):
 // H1 = XB + li1(O); X = XB + (H1 + li3(gelu(li2(ln3(H1))))).  Ends with a barrier.
 __device__ inline void att_tail(const Mha& m, int R, int W, int hd, int ff, const float* O, const float* XB, float* H1,
@@ -269,8 +314,12 @@ struct DecArgs {
 
 // kTeam: the cross-attention's softmax by teams (the host takes it for J > kTeamSoftmaxFrom); the other instantiation is
 // the kernel of every other size, whose registers the team code then does not touch.
-template <bool kTeam>
+// kSharedLn (with kTeam; tensor_game_net_s25.h): EEN holds one copy z of the game's ee, normalised without scale and bias,
+// for every block.  Block b's ln2 scale is folded into the QK rows before the scores, its bias adds the same to every
+// score of a (row, head) and is left out, and the weighted sum of z takes scale and bias at the end (weighted_sum_team).
+template <bool kTeam, bool kSharedLn = false>
 __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
+  static_assert(kTeam || !kSharedLn, "the shared-normalisation decoder runs the team softmax");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
   const int64_t g = blockIdx.x / a.chunks;
@@ -279,7 +328,7 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
   const int R = a.k - s0 < a.R ? a.k - s0 : a.R;  // rows of this workgroup: samples s0 .. s0+R-1
   const int W = c.W, C = c.c, H = c.heads, d = c.d, hd = H * d, ff = c.ff, J = 3 * c.S * c.S, NS = c.n_steps;
   const int NL = c.n_logits;
-  const DecPlan P = dec_plan(c, a.R);
+  const DecPlan P = dec_plan(c, a.R, kSharedLn);
   float *EEN = lds + P.EEN, *CACHE = lds + P.CACHE, *X = lds + P.X, *XB = lds + P.XB, *XN = lds + P.XN,
         *Q = lds + P.Q, *QK = lds + P.QK, *SC = lds + P.SC, *YB = lds + P.YB, *O = lds + P.O, *H1 = lds + P.H1,
         *M = lds + P.M, *F = lds + P.F, *LG = lds + P.LG, *Z0 = lds + P.Z0, *V1 = lds + P.V1, *V2 = lds + P.V2;
@@ -294,10 +343,14 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
 
   // ln2 of each block's cross-attention over the game's ee
   const float* eeg = a.ee + g * J * C;
-  for (int b = 0; b < c.blocks; ++b) {
-    const float* bp = wb + a.off.blk0 + b * a.off.blk;
-    const Mha a2 = mha_at(bp + 2 * W + mha_size(W, W, H, d, ff) + 2 * W, W, C, H, d, ff);
-    layernorm(eeg, C, J, C, a2.ln2w, a2.ln2b, EEN + b * J * C, C);
+  if (kSharedLn) {
+    normalise_rows(eeg, C, J, C, EEN, C);
+  } else {
+    for (int b = 0; b < c.blocks; ++b) {
+      const float* bp = wb + a.off.blk0 + b * a.off.blk;
+      const Mha a2 = mha_at(bp + 2 * W + mha_size(W, W, H, d, ff) + 2 * W, W, C, H, d, ff);
+      layernorm(eeg, C, J, C, a2.ln2w, a2.ln2b, EEN + b * J * C, C);
+    }
   }
   for (int it = threadIdx.x; it < R * W; it += NT) X[it] = emb[NL * W + it % W] + pos[it % W];
   for (int r = threadIdx.x; r < R; r += NT) PP[r] = 1.f;
@@ -354,7 +407,11 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
       __syncthreads();
       for (int h = 0; h < H; ++h) mm(Q + h * d, hd, R, d, a2.k + h * d * C, C, C, nullptr, QK + h * wq, H * wq);
       __syncthreads();
-      const float* een = EEN + b * J * C;
+      if (kSharedLn) {  // QK[r][h][i] *= w_b[i]
+        for (int it = threadIdx.x; it < R * H * C; it += NT) QK[(it / C) * wq + it % C] *= a2.ln2w[it % C];
+        __syncthreads();
+      }
+      const float* een = kSharedLn ? EEN : EEN + b * J * C;
       for (int it = threadIdx.x; it < R * H * J; it += NT) {
         const int j = it % J, rh = it / J;
         const float* qk = QK + rh * wq;
@@ -367,12 +424,16 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
       if (kTeam) softmax_rows_team(SC, R * H, J, nsc);
       else softmax_rows(SC, R * H, J, nsc);
       __syncthreads();
-      for (int it = threadIdx.x; it < R * H * C; it += NT) {
-        const int i = it % C, rh = it / C;
-        const float* sc = SC + rh * nsc;
-        float s = 0.f;
-        for (int j = 0; j < J; ++j) s = fmaf(sc[j], een[j * C + i], s);
-        YB[rh * wq + i] = s;
+      if (kSharedLn) {
+        weighted_sum_team(SC, nsc, R * H, J, een, C, a2.ln2w, a2.ln2b, YB, wq);
+      } else {
+        for (int it = threadIdx.x; it < R * H * C; it += NT) {
+          const int i = it % C, rh = it / C;
+          const float* sc = SC + rh * nsc;
+          float s = 0.f;
+          for (int j = 0; j < J; ++j) s = fmaf(sc[j], een[j * C + i], s);
+          YB[rh * wq + i] = s;
+        }
       }
       __syncthreads();
       for (int h = 0; h < H; ++h) mm(YB + h * wq, H * wq, R, C, a2.v + h * d, hd, d, nullptr, O + h * d, hd);
@@ -466,7 +527,9 @@ __global__ void __launch_bounds__(NT) net_decode_kernel(DecArgs a) {
 
 namespace {
 
-int check_cfg(const char* fn, const tg_net_config* c) {
+// s25: the family of tensor_game_net_s25.h (S = TG_NET_WIDE3_S exactly, its n_steps bound, the slice plan and the
+// shared-normalisation decoder plan) instead of tensor_game_net.h's
+int check_cfg(const char* fn, const tg_net_config* c, bool s25 = false) {
   if (!c) return tg_internal_fail(TG_ERR_INVALID, "%s: null config", fn);
 #define TG_LIM(v, name, M) {c->v, name, M, #M}
   const struct { int32_t v; const char* name; int32_t max; const char* bound; } t[] = {
@@ -482,8 +545,14 @@ int check_cfg(const char* fn, const tg_net_config* c) {
   for (const auto& e : t)
     if (e.v < 1) return tg_internal_fail(TG_ERR_INVALID, "%s: %s=%d < 1", fn, e.name, e.v);
   // S <= TG_NET_MAX_S as for every bound, or exactly TG_NET_WIDE_S or TG_NET_WIDE2_S with their own n_steps bounds instead
-  const bool wide1 = c->S == TG_NET_WIDE_S, wide2 = c->S == TG_NET_WIDE2_S, wide = wide1 || wide2;
-  if (c->S > TG_NET_MAX_S && !wide)
+  const bool wide1 = !s25 && c->S == TG_NET_WIDE_S, wide2 = !s25 && c->S == TG_NET_WIDE2_S, wide = wide1 || wide2;
+  if (s25 && c->S != TG_NET_WIDE3_S)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: dim_3d=%d is not TG_NET_WIDE3_S=%d (tg_net_check serves the other sizes)",
+                            fn, c->S, TG_NET_WIDE3_S);
+  if (s25 && c->n_steps > TG_NET_WIDE3_MAX_STEPS)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE3_MAX_STEPS=%d (dim_3d=%d)", fn,
+                            c->n_steps, TG_NET_WIDE3_MAX_STEPS, c->S);
+  if (!s25 && c->S > TG_NET_MAX_S && !wide)
     return tg_internal_fail(TG_ERR_UNSUPPORTED,
                             "%s: dim_3d=%d above TG_NET_MAX_S=%d, and not exactly TG_NET_WIDE_S=%d or TG_NET_WIDE2_S=%d",
                             fn, c->S, TG_NET_MAX_S, TG_NET_WIDE_S, TG_NET_WIDE2_S);
@@ -494,21 +563,22 @@ int check_cfg(const char* fn, const tg_net_config* c) {
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE2_MAX_STEPS=%d (dim_3d=%d)", fn,
                             c->n_steps, TG_NET_WIDE2_MAX_STEPS, c->S);
   for (int i = 1; i < 17; ++i) {
-    if (wide && i == 13) continue;  // n_steps: its bound at a wide S is above
+    if ((wide || s25) && i == 13) continue;  // n_steps: its bound at a wide S is above
     if (t[i].v > t[i].max)
       return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: %s=%d above %s=%d", fn, t[i].name, t[i].v, t[i].bound, t[i].max);
   }
-  // at S = TG_NET_WIDE2_S the torso runs by slices (net_torso_slice_kernel) and its term is one slice's plan
-  const size_t lt = tg::net::torso_plan(*c, wide2 ? 1 : c->S).total * sizeof(float),
-               ld = tg::net::dec_plan(*c, 1).total * sizeof(float);
+  // at S = TG_NET_WIDE2_S and TG_NET_WIDE3_S the torso runs by slices (net_torso_slice_kernel) and its term is one
+  // slice's plan
+  const size_t lt = tg::net::torso_plan(*c, wide2 || s25 ? 1 : c->S).total * sizeof(float),
+               ld = tg::net::dec_plan(*c, 1, s25).total * sizeof(float);
   if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: the LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB", fn,
                             lt, ld);
   return TG_OK;
 }
 
-int check_common(const char* fn, const tg_net_config* c, const float* w, int64_t B) {
-  if (int rc = check_cfg(fn, c)) return rc;
+int check_common(const char* fn, const tg_net_config* c, const float* w, int64_t B, bool s25) {
+  if (int rc = check_cfg(fn, c, s25)) return rc;
   if (B < 0 || B > (1LL << 30)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld out of range", fn, (long long)B);
   if (!w) return tg_internal_fail(TG_ERR_INVALID, "%s: null weights", fn);
   if (!aligned(w, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: weights not 4-byte aligned", fn);
@@ -528,17 +598,25 @@ tg::net::DecArgs dec_args(const tg_net_config* cfg, const float* w, const float*
   return a;
 }
 
-int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st) {
+// s25: the shared-normalisation decoder of tensor_game_net_s25.h; in the A/B library also where TG_NET_DEC_SHARED_LN is
+// set (the sizes of tensor_game_net.h, for comparison)
+int launch_decode(const char* fn, tg::net::DecArgs& a, hipStream_t st, bool s25) {
+  const bool shared_ln = s25 || TG_SWITCH("TG_NET_DEC_SHARED_LN");
   // rows per workgroup: up to 8 samples of one game, fewer when the plan would not fit in LDS
   int R = a.k < 8 ? a.k : 8;
-  while (R > 1 && tg::net::dec_plan(a.c, R).total * sizeof(float) > static_cast<size_t>(tg::kMaxDynamicLds)) --R;
+  while (R > 1 && tg::net::dec_plan(a.c, R, shared_ln).total * sizeof(float) > static_cast<size_t>(tg::kMaxDynamicLds))
+    --R;
   a.R = R;
   a.chunks = (a.k + R - 1) / R;
   if (a.B * a.chunks > INT32_MAX)
     return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn,
                             (long long)a.B, a.chunks);
-  const size_t lds = tg::net::dec_plan(a.c, R).total * sizeof(float);
+  const size_t lds = tg::net::dec_plan(a.c, R, shared_ln).total * sizeof(float);
   const unsigned grid = static_cast<unsigned>(a.B * a.chunks);
+  if (shared_ln) {
+    if (int rc = lds_opt_in<tg::net::net_decode_kernel<true, true>>(fn, lds)) return rc;
+    return launch(fn, tg::net::net_decode_kernel<true, true>, grid, tg::net::NT, lds, st, a);
+  }
   if (3 * a.c.S * a.c.S > tg::net::kTeamSoftmaxFrom) {
     if (int rc = lds_opt_in<tg::net::net_decode_kernel<true>>(fn, lds)) return rc;
     return launch(fn, tg::net::net_decode_kernel<true>, grid, tg::net::NT, lds, st, a);
@@ -555,10 +633,11 @@ int check_mask(const char* fn, const uint8_t* flags, int need) {
   return TG_OK;
 }
 
-// tg_net_torso and tg_net_torso_masked
+// tg_net_torso, tg_net_torso_masked and tg_net_s25_torso
 int torso_entry(const char* fn, const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8,
-                const float* scalars, float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream) {
-  if (int rc = check_common(fn, cfg, w, B)) return rc;
+                const float* scalars, float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream,
+                bool s25 = false) {
+  if (int rc = check_common(fn, cfg, w, B, s25)) return rc;
   if (frames_is_i8 != 0 && frames_is_i8 != 1)
     return tg_internal_fail(TG_ERR_INVALID, "%s: frames_is_i8=%d (0 float32, 1 int8)", fn, frames_is_i8);
   if (int rc = check_mask(fn, flags, need)) return rc;
@@ -568,8 +647,9 @@ int torso_entry(const char* fn, const tg_net_config* cfg, const float* w, const 
     return tg_internal_fail(TG_ERR_INVALID, "%s: frames, scalars or ee not aligned to their elements", fn);
   tg::net::TorsoArgs a{*cfg, tg::net::offsets(*cfg), w, frames, frames_is_i8, scalars, ee, B, flags,
                        static_cast<uint8_t>(flags ? need : 0)};
-  // by slices at S = TG_NET_WIDE2_S; in the A/B library also where TG_NET_TORSO_SLICES is set (any size, for comparison)
-  if (cfg->S == TG_NET_WIDE2_S || TG_SWITCH("TG_NET_TORSO_SLICES")) {
+  // by slices at S = TG_NET_WIDE2_S and TG_NET_WIDE3_S; in the A/B library also where TG_NET_TORSO_SLICES is set (any
+  // size, for comparison)
+  if (s25 || cfg->S == TG_NET_WIDE2_S || TG_SWITCH("TG_NET_TORSO_SLICES")) {
     if (B * cfg->S > INT32_MAX)
       return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld x %d workgroups per game is too large a grid", fn, (long long)B,
                               cfg->S);
@@ -583,11 +663,11 @@ int torso_entry(const char* fn, const tg_net_config* cfg, const float* w, const 
   return launch(fn, tg::net::net_torso_kernel, static_cast<unsigned>(B), tg::net::NT, lds, static_cast<hipStream_t>(stream), a);
 }
 
-// tg_net_sample and tg_net_sample_masked
+// tg_net_sample, tg_net_sample_masked and tg_net_s25_sample
 int sample_entry(const char* fn, const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B,
                  int k, uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
-                 const uint8_t* flags, int need, tg_stream_t stream) {
-  if (int rc = check_common(fn, cfg, w, B)) return rc;
+                 const uint8_t* flags, int need, tg_stream_t stream, bool s25 = false) {
+  if (int rc = check_common(fn, cfg, w, B, s25)) return rc;
   if (k < 1 || k > TG_NET_MAX_SAMPLES)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: k=%d outside [1, TG_NET_MAX_SAMPLES=%d]", fn, k, TG_NET_MAX_SAMPLES);
   if (int rc = check_mask(fn, flags, need)) return rc;
@@ -606,7 +686,30 @@ int sample_entry(const char* fn, const tg_net_config* cfg, const float* w, const
   a.q = q;
   a.flags = flags;
   a.need = static_cast<uint8_t>(flags ? need : 0);
-  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+  return launch_decode(fn, a, static_cast<hipStream_t>(stream), s25);
+}
+
+// tg_net_logits and tg_net_s25_logits
+int logits_entry(const char* fn, const tg_net_config* cfg, const float* w, const float* ee, const int64_t* g_action,
+                 int64_t B, float* oo, float* zz0, float* q, tg_stream_t stream, bool s25 = false) {
+  if (int rc = check_common(fn, cfg, w, B, s25)) return rc;
+  if (B == 0) return TG_OK;
+  if (!ee || !g_action) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee or g_action", fn);
+  if (!aligned(ee, 4) || !aligned(g_action, 8) || !aligned(oo, 4) || !aligned(zz0, 4) || !aligned(q, 4))
+    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, g_action, oo, zz0 or q not aligned to their elements", fn);
+  tg::net::DecArgs a = dec_args(cfg, w, ee, B, 1, 1);
+  a.q = q;
+  a.g_action = g_action;
+  a.oo = oo;
+  a.zz0 = zz0;
+  return launch_decode(fn, a, static_cast<hipStream_t>(stream), s25);
+}
+
+int weights_size(const char* fn, const tg_net_config* cfg, int64_t* floats, bool s25) {
+  if (int rc = check_cfg(fn, cfg, s25)) return rc;
+  if (!floats) return tg_internal_fail(TG_ERR_INVALID, "%s: null output", fn);
+  *floats = tg::net::offsets(*cfg).total;
+  return TG_OK;
 }
 
 }  // namespace
@@ -617,10 +720,7 @@ extern "C" {
 int tg_net_check(const tg_net_config* cfg) { return check_cfg("tg_net_check", cfg); }
 
 int tg_net_weights_size(const tg_net_config* cfg, int64_t* floats) {
-  if (int rc = check_cfg("tg_net_weights_size", cfg)) return rc;
-  if (!floats) return tg_internal_fail(TG_ERR_INVALID, "tg_net_weights_size: null output");
-  *floats = tg::net::offsets(*cfg).total;
-  return TG_OK;
+  return weights_size("tg_net_weights_size", cfg, floats, false);
 }
 
 // Torso.forward, model.py:97-123
@@ -652,18 +752,31 @@ int tg_net_sample_masked(const tg_net_config* cfg, const float* w, const float* 
 // the forward of PolicyHead.fwd_train, model.py:219-232, and ValueHead on its zz[:, 0] (AlphaTensor.fwd_train :335-338)
 int tg_net_logits(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* g_action, int64_t B,
                   float* oo, float* zz0, float* q, tg_stream_t stream) {
-  const char* fn = "tg_net_logits";
-  if (int rc = check_common(fn, cfg, w, B)) return rc;
-  if (B == 0) return TG_OK;
-  if (!ee || !g_action) return tg_internal_fail(TG_ERR_INVALID, "%s: null ee or g_action", fn);
-  if (!aligned(ee, 4) || !aligned(g_action, 8) || !aligned(oo, 4) || !aligned(zz0, 4) || !aligned(q, 4))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: ee, g_action, oo, zz0 or q not aligned to their elements", fn);
-  tg::net::DecArgs a = dec_args(cfg, w, ee, B, 1, 1);
-  a.q = q;
-  a.g_action = g_action;
-  a.oo = oo;
-  a.zz0 = zz0;
-  return launch_decode(fn, a, static_cast<hipStream_t>(stream));
+  return logits_entry("tg_net_logits", cfg, w, ee, g_action, B, oo, zz0, q, stream);
+}
+
+// ---- include/tensor_game_net_s25.h: the same at S = TG_NET_WIDE3_S, the decoder with one normalised copy of ee --------
+int tg_net_s25_check(const tg_net_config* cfg) { return check_cfg("tg_net_s25_check", cfg, true); }
+
+int tg_net_s25_weights_size(const tg_net_config* cfg, int64_t* floats) {
+  return weights_size("tg_net_s25_weights_size", cfg, floats, true);
+}
+
+int tg_net_s25_torso(const tg_net_config* cfg, const float* w, const void* frames, int frames_is_i8, const float* scalars,
+                     float* ee, int64_t B, const uint8_t* flags, int need, tg_stream_t stream) {
+  return torso_entry("tg_net_s25_torso", cfg, w, frames, frames_is_i8, scalars, ee, B, flags, need, stream, true);
+}
+
+int tg_net_s25_sample(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* rows, int64_t B, int k,
+                      uint64_t seed, uint64_t call, const float* uniforms, int8_t* tokens_i8, float* probs, float* q,
+                      const uint8_t* flags, int need, tg_stream_t stream) {
+  return sample_entry("tg_net_s25_sample", cfg, w, ee, rows, B, k, seed, call, uniforms, tokens_i8, probs, q, flags, need,
+                      stream, true);
+}
+
+int tg_net_s25_logits(const tg_net_config* cfg, const float* w, const float* ee, const int64_t* g_action, int64_t B,
+                      float* oo, float* zz0, float* q, tg_stream_t stream) {
+  return logits_entry("tg_net_s25_logits", cfg, w, ee, g_action, B, oo, zz0, q, stream, true);
 }
 
 }  // extern "C"

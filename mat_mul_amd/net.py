@@ -12,7 +12,9 @@ head) -- from one packed float32 weight blob.
 
 Supported: dim_3d <= 5, or exactly 9 (3x3 matmul) or 16 (4x4 matmul, n_steps <= 48: the torso then runs one
 workgroup per (game, slice) instead of one per game, and training goes through ``train.SlicedTrainer``), inside the TG_NET_MAX_* bounds and the LDS plans of the
-header; ``check_config`` names the bound otherwise.
+header; ``check_config`` names the bound otherwise.  The 5x5 matmul tensor, dim_3d = 25 (n_steps <= 75), has a class
+of its own, ``FusedAlphaTensor25``, on the entries of include/tensor_game_net_s25.h (the decoder keeps one normalised
+copy of the torso output for all policy blocks there); it takes that size only, and there is no training at it.
 
 The draws follow the header's sampling rule (Philox keyed by seed, counter (game, call, sample, step block)), not
 torch's generator: the distribution is the reference's, the individual draws are not.  There is no CPU path.
@@ -28,7 +30,7 @@ import torch
 from . import ops
 from ._lib import TG_NET_MAX_SAMPLES, NetConfig, TensorGameError
 
-__all__ = ["FusedAlphaTensor", "infer_config", "check_config", "pack_weights", "CONFIG_FIELDS"]
+__all__ = ["FusedAlphaTensor", "FusedAlphaTensor25", "infer_config", "check_config", "pack_weights", "CONFIG_FIELDS"]
 
 CONFIG_FIELDS = tuple(name for name, _ in NetConfig._fields_)
 
@@ -78,10 +80,11 @@ def infer_config(sd: Mapping) -> Dict[str, int]:
     return cfg
 
 
-def check_config(cfg: Mapping[str, int]) -> NetConfig:
-    """The C struct of ``cfg``; raises TensorGameError naming the bound unless tg_net_check accepts it."""
+def check_config(cfg: Mapping[str, int], check=ops.net_check) -> NetConfig:
+    """The C struct of ``cfg``; raises TensorGameError naming the bound unless tg_net_check (or the ``check`` of another
+    header's family) accepts it."""
     c = NetConfig(**{k: int(cfg[k]) for k in CONFIG_FIELDS})
-    ops.net_check(c)
+    check(c)
     return c
 
 
@@ -124,14 +127,21 @@ def pack_weights(sd: Mapping, cfg: Mapping[str, int], fold_pos: bool = True) -> 
 class FusedAlphaTensor:
     """Eval-mode inference of a reference ``AlphaTensor`` from its weights, packed once on the device."""
 
+    # the library entries (include/tensor_game_net.h); a subclass names another header's
+    _check = staticmethod(ops.net_check)
+    _weights_size = staticmethod(ops.net_weights_size)
+    _torso = staticmethod(ops.net_torso)
+    _sample = staticmethod(ops.net_sample)
+    _logits = staticmethod(ops.net_logits)
+
     def __init__(self, cfg: Mapping[str, int], blob: torch.Tensor, n_samples: int):
         if not 1 <= n_samples <= TG_NET_MAX_SAMPLES:
             raise TensorGameError("FusedAlphaTensor", -1, f"n_samples={n_samples} outside [1, {TG_NET_MAX_SAMPLES}]")
         self.config = {k: int(cfg[k]) for k in CONFIG_FIELDS}
-        self.c = check_config(self.config)
-        if blob.numel() != ops.net_weights_size(self.c):
+        self.c = check_config(self.config, self._check)
+        if blob.numel() != self._weights_size(self.c):
             raise TensorGameError("FusedAlphaTensor", -1, f"blob of {blob.numel()} floats, the configuration needs "
-                                  f"{ops.net_weights_size(self.c)}")
+                                  f"{self._weights_size(self.c)}")
         self.w = blob
         self.device = blob.device
         self.n_samples = int(n_samples)
@@ -144,7 +154,7 @@ class FusedAlphaTensor:
         if dev.type != "cuda":
             raise TensorGameError("FusedAlphaTensor", -1, "a ROCm device is required; there is no CPU path")
         cfg = infer_config(sd)
-        check_config(cfg)
+        check_config(cfg, cls._check)
         return cls(cfg, torch.from_numpy(pack_weights(sd, cfg)).to(dev), n_samples)
 
     @classmethod
@@ -157,9 +167,9 @@ class FusedAlphaTensor:
     def torso(self, xx: torch.Tensor, ss: torch.Tensor, out: Optional[torch.Tensor] = None,
               flags: Optional[torch.Tensor] = None, need: int = 0) -> torch.Tensor:
         """Torso.forward: xx (B,T,S,S,S) float32 or int8, ss float32 (B,dim_s) -> ee float32 (B,3S^2,c).  One launch at
-        every supported S (by slices at S = 16).  ``flags`` uint8 (B,) / ``need``: only the rows with
+        every supported S (by slices at S = 16 and 25).  ``flags`` uint8 (B,) / ``need``: only the rows with
         ``(flags & need) == need`` are computed; the others of ``out`` are left as they are (zeros without ``out``)."""
-        return ops.net_torso(self.c, self.w, xx, ss.to(torch.float32), out=out, flags=flags, need=need)
+        return self._torso(self.c, self.w, xx, ss.to(torch.float32), out=out, flags=flags, need=need)
 
     def sample(self, ee: torch.Tensor, rows: Optional[torch.Tensor] = None, seed: int = 0, call: Optional[int] = None,
                uniforms: Optional[torch.Tensor] = None, k: Optional[int] = None, tokens: Optional[torch.Tensor] = None,
@@ -174,9 +184,9 @@ class FusedAlphaTensor:
         if call is None:
             call = self.calls
         self.calls += 1
-        return ops.net_sample(self.c, self.w, ee.contiguous(), rows.to(self.device, torch.int64).contiguous(),
-                              k or self.n_samples, seed, call, uniforms=uniforms, tokens=tokens, probs=probs, q=q,
-                              flags=flags, need=need)
+        return self._sample(self.c, self.w, ee.contiguous(), rows.to(self.device, torch.int64).contiguous(),
+                            k or self.n_samples, seed, call, uniforms=uniforms, tokens=tokens, probs=probs, q=q,
+                            flags=flags, need=need)
 
     @torch.no_grad()
     def fwd_infer(self, xx: torch.Tensor, ss: torch.Tensor, seed: int = 0, call: Optional[int] = None,
@@ -190,7 +200,7 @@ class FusedAlphaTensor:
     def logits(self, xx: torch.Tensor, ss: torch.Tensor, g_action: torch.Tensor, with_q: bool = False):
         """The forward of PolicyHead.fwd_train: (oo float32 (B,n_steps,n_logits), zz0 float32 (B,W)), and the value
         head's quantiles q float32 (B,n_quantile) on zz0 when ``with_q``."""
-        oo, zz0, q = ops.net_logits(self.c, self.w, self.torso(xx, ss), g_action.to(self.device))
+        oo, zz0, q = self._logits(self.c, self.w, self.torso(xx, ss), g_action.to(self.device))
         return (oo, zz0, q) if with_q else (oo, zz0)
 
     def policy(self, seed: int = 0, masked: bool = False):
@@ -291,3 +301,16 @@ class FusedAlphaTensor:
         policy.takes_slots = True
         policy.seed = seed
         return policy
+
+
+class FusedAlphaTensor25(FusedAlphaTensor):
+    """``FusedAlphaTensor`` at the 5x5 matmul tensor, dim_3d = 25 exactly (n_steps <= 75): the same constructor,
+    classmethods and methods on include/tensor_game_net_s25.h's entries.  The torso runs one workgroup per (game, slice);
+    the decoder keeps one normalised copy of the game's 1875 torso rows for every policy block, which is what lets the
+    training app's configuration fit (one sample per workgroup).  Inference only."""
+
+    _check = staticmethod(ops.net_s25_check)
+    _weights_size = staticmethod(ops.net_s25_weights_size)
+    _torso = staticmethod(ops.net_s25_torso)
+    _sample = staticmethod(ops.net_s25_sample)
+    _logits = staticmethod(ops.net_s25_logits)

@@ -24,6 +24,7 @@ __all__ = [
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
     "replay_pack", "replay_add_packed",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
+    "net_s25_check", "net_s25_weights_size", "net_s25_torso", "net_s25_sample", "net_s25_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
     "net_train_sliced_check", "net_train_sliced_workspace_size", "net_loss_grad_sliced",
     "rollout_check", "rollout_records", "rollout_advance",
@@ -833,14 +834,18 @@ def net_check(cfg) -> None:
 
 def net_weights_size(cfg) -> int:
     """Floats in the packed weight blob of ``cfg`` (tg_net_weights_size)."""
+    return _weights_size("tg_net_weights_size", cfg)
+
+
+def _weights_size(symbol: str, cfg) -> int:
     out = C.c_int64(0)
-    call("tg_net_weights_size", C.byref(cfg), C.byref(out))
+    call(symbol, C.byref(cfg), C.byref(out))
     return int(out.value)
 
 
-def _net_blob(cfg, w: torch.Tensor) -> torch.device:
+def _net_blob(cfg, w: torch.Tensor, size_symbol: str = "tg_net_weights_size") -> torch.device:
     _need_gpu(w, "weights")
-    n = net_weights_size(cfg)
+    n = _weights_size(size_symbol, cfg)
     if w.dtype != torch.float32 or tuple(w.shape) != (n,) or not w.is_contiguous():
         raise TensorGameError("weights", -1, f"weights must be a contiguous float32 blob of {n} floats, got {w.dtype} "
                               f"{tuple(w.shape)}")
@@ -866,23 +871,48 @@ def _net_frames(cfg, frames, dev, fn: str) -> int:
     return B
 
 
+# The C symbols of one header's inference entries.  ``torso`` / ``sample`` None: the header has the masked forms only,
+# which take flags = NULL for every row.
+@dataclass(frozen=True)
+class _NetEntries:
+    size: str
+    torso: Optional[str]
+    torso_masked: str
+    sample: Optional[str]
+    sample_masked: str
+    logits: str
+
+
+_NET = _NetEntries("tg_net_weights_size", "tg_net_torso", "tg_net_torso_masked", "tg_net_sample", "tg_net_sample_masked",
+                   "tg_net_logits")
+_NET_S25 = _NetEntries("tg_net_s25_weights_size", None, "tg_net_s25_torso", None, "tg_net_s25_sample", "tg_net_s25_logits")
+
+
+def _masked_launch(dev, plain: Optional[str], masked: str, args, flags, need: int) -> None:
+    if flags is None and plain is not None:
+        _launch(dev, plain, *args)
+    else:
+        _launch(dev, masked, *args, _ptr(flags), int(need) if flags is not None else 0)
+
+
 def net_torso(cfg, w, frames, scalars, out=None, flags=None, need: int = 0) -> torch.Tensor:
     """Torso.forward (tg_net_torso): frames (B,T,S,S,S) float32 or int8, scalars float32 (B,dim_s) -> ee float32
     (B,3S^2,c).  With ``flags`` uint8 (B,) only the rows with ``(flags & need) == need`` are computed
     (tg_net_torso_masked): a given ``out`` keeps its other rows, an allocated one holds zeros there."""
-    dev = _net_blob(cfg, w)
+    return _torso(_NET, "net_torso", cfg, w, frames, scalars, out, flags, need)
+
+
+def _torso(sym: _NetEntries, fn: str, cfg, w, frames, scalars, out, flags, need) -> torch.Tensor:
+    dev = _net_blob(cfg, w, sym.size)
     _need_gpu(frames, "frames")
-    B = _net_frames(cfg, frames, dev, "net_torso")
+    B = _net_frames(cfg, frames, dev, fn)
     frames = frames.contiguous()
     scalars = _flag(scalars.contiguous(), (B, cfg.dim_s), torch.float32, dev, "scalars")
     shape = (B, 3 * cfg.S * cfg.S, cfg.c)
-    flags = _net_mask(flags, need, B, dev, "net_torso")
+    flags = _net_mask(flags, need, B, dev, fn)
     out = _out(out, shape, torch.float32, dev, "out", torch.empty if flags is None else torch.zeros)
     args = (C.byref(cfg), _ptr(w), _ptr(frames), 1 if frames.dtype == torch.int8 else 0, _ptr(scalars), _ptr(out), B)
-    if flags is None:
-        _launch(dev, "tg_net_torso", *args)
-    else:
-        _launch(dev, "tg_net_torso_masked", *args, _ptr(flags), int(need))
+    _masked_launch(dev, sym.torso, sym.torso_masked, args, flags, need)
     return out
 
 
@@ -893,9 +923,13 @@ def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None
     ``call_idx``; ``uniforms`` float32 (B,k,n_steps) replaces the stream when given.  With ``flags`` uint8 (B,)
     only the rows with ``(flags & need) == need`` are decoded (tg_net_sample_masked): given outputs keep their other
     rows, allocated ones hold zeros there."""
-    dev = _net_blob(cfg, w)
+    return _sample(_NET, "net_sample", cfg, w, ee, rows, k, seed, call_idx, uniforms, tokens, probs, q, flags, need)
+
+
+def _sample(sym: _NetEntries, fn: str, cfg, w, ee, rows, k, seed, call_idx, uniforms, tokens, probs, q, flags, need):
+    dev = _net_blob(cfg, w, sym.size)
     B = ee.shape[0]
-    flags = _net_mask(flags, need, B, dev, "net_sample")
+    flags = _net_mask(flags, need, B, dev, fn)
     new = torch.empty if flags is None else torch.zeros
     ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
     rows = _flag(rows, (B,), torch.int64, dev, "rows")
@@ -905,10 +939,7 @@ def net_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None
     q = _out(q, (B,), torch.float32, dev, "q", new)
     args = (C.byref(cfg), _ptr(w), _ptr(ee), _ptr(rows), B, int(k), _u64(seed), _u64(call_idx), _ptr(uniforms),
             _ptr(tokens), _ptr(probs), _ptr(q))
-    if flags is None:
-        _launch(dev, "tg_net_sample", *args)
-    else:
-        _launch(dev, "tg_net_sample_masked", *args, _ptr(flags), int(need))
+    _masked_launch(dev, sym.sample, sym.sample_masked, args, flags, need)
     return tokens, probs, q
 
 
@@ -916,19 +947,51 @@ def net_logits(cfg, w, ee, g_action):
     """The forward of PolicyHead.fwd_train and the ValueHead on zz[:, 0] (tg_net_logits): ee float32 (B,3S^2,c),
     g_action (B,n_steps) integer tokens -> oo float32 (B,n_steps,n_logits), zz0 float32 (B,W), q float32
     (B,n_quantile)."""
-    dev = _net_blob(cfg, w)
+    return _logits(_NET, "net_logits", cfg, w, ee, g_action)
+
+
+def _logits(sym: _NetEntries, fn: str, cfg, w, ee, g_action):
+    dev = _net_blob(cfg, w, sym.size)
     B = ee.shape[0]
     ee = _flag(ee, (B, 3 * cfg.S * cfg.S, cfg.c), torch.float32, dev, "ee")
     _need_gpu(g_action, "g_action")
     if tuple(g_action.shape) != (B, cfg.n_steps) or g_action.dtype.is_floating_point:
-        raise TensorGameError("net_logits", -1, f"g_action must be integer (B,n_steps) = {(B, cfg.n_steps)}, got "
+        raise TensorGameError(fn, -1, f"g_action must be integer (B,n_steps) = {(B, cfg.n_steps)}, got "
                               f"{g_action.dtype} {tuple(g_action.shape)}")
     g_action = g_action.to(dev, torch.int64).contiguous()
     oo = torch.empty((B, cfg.n_steps, cfg.n_logits), dtype=torch.float32, device=dev)
     zz0 = torch.empty((B, cfg.W), dtype=torch.float32, device=dev)
     q = torch.empty((B, cfg.n_quantile), dtype=torch.float32, device=dev)
-    _launch(dev, "tg_net_logits", C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q))
+    _launch(dev, sym.logits, C.byref(cfg), _ptr(w), _ptr(ee), _ptr(g_action), B, _ptr(oo), _ptr(zz0), _ptr(q))
     return oo, zz0, q
+
+
+# ---- include/tensor_game_net_s25.h: the same entries at S = TG_NET_WIDE3_S --------------------------------------------
+def net_s25_check(cfg) -> None:
+    """Raise TensorGameError (naming the bound) unless ``cfg`` is in the S = 25 inference family (tg_net_s25_check)."""
+    call("tg_net_s25_check", C.byref(cfg))
+
+
+def net_s25_weights_size(cfg) -> int:
+    """Floats in the packed weight blob of ``cfg`` (tg_net_s25_weights_size; the layout of every size)."""
+    return _weights_size("tg_net_s25_weights_size", cfg)
+
+
+def net_s25_torso(cfg, w, frames, scalars, out=None, flags=None, need: int = 0) -> torch.Tensor:
+    """net_torso at S = 25 (tg_net_s25_torso): the same arguments and results."""
+    return _torso(_NET_S25, "net_s25_torso", cfg, w, frames, scalars, out, flags, need)
+
+
+def net_s25_sample(cfg, w, ee, rows, k: int, seed: int, call_idx: int, uniforms=None, tokens=None, probs=None, q=None,
+                   flags=None, need: int = 0):
+    """net_sample at S = 25 (tg_net_s25_sample): the same arguments and results."""
+    return _sample(_NET_S25, "net_s25_sample", cfg, w, ee, rows, k, seed, call_idx, uniforms, tokens, probs, q, flags,
+                   need)
+
+
+def net_s25_logits(cfg, w, ee, g_action):
+    """net_logits at S = 25 (tg_net_s25_logits): the same arguments and results."""
+    return _logits(_NET_S25, "net_s25_logits", cfg, w, ee, g_action)
 
 
 # ---- include/tensor_game_train.h ---------------------------------------------------------------------------------------

@@ -17,6 +17,9 @@ TG_LIB_VARIANT=ab, TG_NET_TORSO_SLICES=1 forces net_torso_slice_kernel at any si
 --masked times torso + sample through the row mask (tg_net_torso_masked, tg_net_sample_masked) with a share f = 1, 0.75,
 0.5, 0.25 and 1/B of the rows active (seeded random flags) next to the plain call, the calls alternating in one process,
 at B = 256 and 4096 (B = 16 and 256 at S = 16); it merges its result into OUT_DIR/r13_masked.json under net_<config>.
+At S = 25 (tests/net_s25_ref.CONFIGS: a25, b25, c25; FusedAlphaTensor25, include/tensor_game_net_s25.h) the sizes are
+B = 16 and 256, each with the torso alone, sample on its output at k = 1 and at k = n_samples, and fwd_infer next to the
+eager restatement (which is timed max(2, reps / 8) times there: a call takes seconds); no self-play figure.
 """
 from __future__ import annotations
 
@@ -36,12 +39,13 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from mat_mul_amd import FusedAlphaTensor, search  # noqa: E402
+from mat_mul_amd import FusedAlphaTensor, FusedAlphaTensor25, search  # noqa: E402
 from net_ref import CONFIGS, Ref, dims, make_inputs, make_weights  # noqa: E402
 from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
 from net_s16_ref import CONFIGS as CONFIGS_S16  # noqa: E402
+from net_s25_ref import CONFIGS as CONFIGS_S25  # noqa: E402
 
-CONFIGS = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}
+CONFIGS = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16, **CONFIGS_S25}
 
 DEV = "cuda:0"
 FP32_PEAK = 157.3e12  # MI355X vector FP32, FLOP/s (FMA = 2)
@@ -108,12 +112,13 @@ def main():
     m = dims(cfg)
     k = cfg["n_samples"]
     sd = make_weights(cfg, 11)
-    net = FusedAlphaTensor.from_state_dict(sd, k, device=DEV)
+    wide25 = m["S"] == 25
+    net = (FusedAlphaTensor25 if wide25 else FusedAlphaTensor).from_state_dict(sd, k, device=DEV)
     ref = Ref(sd, cfg, device=DEV, dtype=torch.float32)
     res = {"config": m, "k": k, "fp32_peak_flops": FP32_PEAK, "sizes": []}
     if args.torso_only:
         slices = os.environ.get("TG_LIB_VARIANT") == "ab" and "TG_NET_TORSO_SLICES" in os.environ
-        res = {"config": m, "kernel": "net_torso_slice_kernel" if slices or m["S"] == 16 else "net_torso_kernel",
+        res = {"config": m, "kernel": "net_torso_slice_kernel" if slices or m["S"] in (16, 25) else "net_torso_kernel",
                "sizes": []}
         for B in (16, 256):
             xx, ss = make_inputs(cfg, B, B)
@@ -132,7 +137,7 @@ def main():
     wide16 = m["S"] == 16
     if args.masked:
         res = {"config": m, "k": k, "need": 129, "sizes": [], "command": " ".join(sys.argv)}
-        for B in ((16, 256) if wide16 else (256, 4096)):
+        for B in ((16, 256) if wide16 or wide25 else (256, 4096)):
             xx, ss = make_inputs(cfg, B, B)
             xx, ss = torch.from_numpy(xx).to(DEV).float(), torch.from_numpy(ss).to(DEV)
             rows = torch.arange(B, device=DEV, dtype=torch.int64)
@@ -174,26 +179,39 @@ def main():
         path.write_text(json.dumps(whole, indent=1) + "\n")
         print(f"wrote {path}")
         return
-    for B in ((16, 256, 1024) if wide16 else (256, 1024, 4096)):
+    eager_reps = max(2, args.reps // 8) if wide25 else args.reps
+    for B in ((16, 256) if wide25 else (16, 256, 1024) if wide16 else (256, 1024, 4096)):
         xx, ss = make_inputs(cfg, B, B)
         xx = torch.from_numpy(xx).to(DEV).float()
         ss = torch.from_numpy(ss).to(DEV)
         fused = lambda: net.fwd_infer(xx, ss, seed=1)  # noqa: E731
         eager = lambda: ref.fwd_infer(xx, ss, k)  # noqa: E731
         with torch.no_grad():
-            for _ in range(args.warmup):
+            for i in range(args.warmup):
                 fused()
-                if not args.fused_only:
+                if not args.fused_only and i < eager_reps:
                     eager()
             torch.cuda.synchronize()
             tf, te = [], []
-            for _ in range(args.reps):
+            for i in range(args.reps):
                 tf.append(timed(fused))
-                if not args.fused_only:
+                if not args.fused_only and i < eager_reps:
                     te.append(timed(eager))
         f = flops(m, B, k)
         row = {"B": B, "fused": stats(tf), "flops": f,
                "fused_share_of_fp32_peak": f / (statistics.median(tf) * 1e-6) / FP32_PEAK}
+        if wide25:  # the two launches of fwd_infer apart, and the decoder with one sample per game
+            ee = net.torso(xx, ss)
+            parts = {"torso": lambda: net.torso(xx, ss), "sample_k1": lambda: net.sample(ee, seed=1, k=1),
+                     f"sample_k{k}": lambda: net.sample(ee, seed=1)}
+            for fn in parts.values():
+                fn()
+            torch.cuda.synchronize()
+            ts = {name: [] for name in parts}
+            for _ in range(args.reps):
+                for name, fn in parts.items():
+                    ts[name].append(timed(fn))
+            row.update({name: stats(t) for name, t in ts.items()})
         if te:
             row["eager_restatement_fp32"] = stats(te)
             row["eager_over_fused"] = statistics.median(te) / statistics.median(tf)
