@@ -4,7 +4,7 @@
  *
  * tensor_game_net.h's entries keep their family (S <= TG_NET_MAX_S, 9 and 16) and refuse this size; the entries here take
  * this size only.  Conventions, configuration struct, weight blob and sampling rule are tensor_game_net.h's, unchanged
- * (mat_mul_amd/net.py's pack_weights serves as it is).  Inference only: training at S = 25 is not built.
+ * (mat_mul_amd/net.py's pack_weights serves as it is).  Inference only: training at S = 25 is tensor_game_train_s25.h's.
  *
  * What differs from the other sizes is the decoder's LDS plan.  The torso runs by slices as at S = 16
  * (net_torso_slice_kernel, one workgroup per (game, slice i), B * 25 workgroups; 37.1 KiB at the training app's

@@ -15,7 +15,7 @@ import importlib
 __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
-           "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "train", "rollout", "sample_rollouts", "RolloutResult",
+           "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run"]
 
 _SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io"}
@@ -32,6 +32,7 @@ _ATTRS = {
     "FusedAlphaTensor25": "net",
     "FusedTrainer": "train",
     "SlicedTrainer": "train",
+    "SlicedTrainer25": "train",
     "sample_rollouts": "rollout",
     "RolloutResult": "rollout",
     "solve_states": "rollout",

@@ -151,6 +151,12 @@ TRAIN_SLICED_SIGNATURES = {
     "tg_net_train_sliced_workspace_size": TRAIN_SIGNATURES["tg_net_train_workspace_size"],
     "tg_net_loss_grad_sliced": TRAIN_SIGNATURES["tg_net_loss_grad"],
 }
+# name -> argtypes; every symbol include/tensor_game_train_s25.h declares (the same three at S = TG_NET_WIDE3_S)
+TRAIN_S25_SIGNATURES = {
+    "tg_net_train_s25_check": TRAIN_SIGNATURES["tg_net_train_check"],
+    "tg_net_train_s25_workspace_size": TRAIN_SIGNATURES["tg_net_train_workspace_size"],
+    "tg_net_loss_grad_s25": TRAIN_SIGNATURES["tg_net_loss_grad"],
+}
 # name -> argtypes; every symbol include/tensor_game_rollout.h declares
 ROLLOUT_SIGNATURES = {
     "tg_rollout_advance": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -180,7 +186,8 @@ TG_NET_MAX_SAMPLES = 64
 TG_NET_WIDE_S, TG_NET_WIDE_MAX_STEPS = 9, 27
 # and the second: the 4x4 matmul tensor (the torso runs by slices there; training through tensor_game_train_sliced.h)
 TG_NET_WIDE2_S, TG_NET_WIDE2_MAX_STEPS = 16, 48
-# the 5x5 matmul tensor has entries of its own (include/tensor_game_net_s25.h); tg_net_check refuses the size
+# the 5x5 matmul tensor has entries of its own (include/tensor_game_net_s25.h, training through
+# tensor_game_train_s25.h); tg_net_check refuses the size
 TG_NET_WIDE3_S, TG_NET_WIDE3_MAX_STEPS = 25, 75
 
 
@@ -221,6 +228,7 @@ def _load() -> C.CDLL:
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
                            **REPLAY_IO_SIGNATURES,
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
+                           **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)

@@ -41,6 +41,7 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "tensor_game.h", 
                                             PKG.parent / "include" / "tensor_game_net_s25.h",
                                             PKG.parent / "include" / "tensor_game_train.h",
                                             PKG.parent / "include" / "tensor_game_train_sliced.h",
+                                            PKG.parent / "include" / "tensor_game_train_s25.h",
                                             PKG.parent / "include" / "tensor_game_rollout.h",
                                             PKG.parent / "include" / "tensor_game_rollout_masked.h",
                                             PKG.parent / "include" / "tensor_game_rollout_slots.h"]

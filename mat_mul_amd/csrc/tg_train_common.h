@@ -1,4 +1,5 @@
-// Shared by tg_train.hip (training, whole games) and tg_train_sliced.hip (training at S = TG_NET_WIDE2_S): one attention
+// Shared by tg_train.hip (training, whole games), tg_train_sliced.hip (training at S = TG_NET_WIDE2_S) and
+// tg_train_s25.hip (training at S = TG_NET_WIDE3_S): one attention
 // block's geometry, LDS scratch, forward and backward; the kernels' arguments, workspace and LDS plans; the decoder's
 // body (forward, losses, backward) over a policy that says where ee, dL/dee and the saved block inputs live and how the
 // cross-attention block runs; and the fixed-order reduction.
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/tensor_game.h"
 #include "../../include/tensor_game_net.h"
@@ -27,7 +29,8 @@ using net::Off;
 using GMha = MhaT<float*>;
 
 // ---- one attention block: geometry and LDS scratch ------------------------------------------------------------------
-// nseq independent sequences; x rows s*Lx + a (c1 wide), y rows s*Ly + b (c2 wide).
+// nseq independent sequences; x rows s*Lx + a (c1 wide), y rows s*Ly + b (c2 wide).  causal: the x rows are the last Lx
+// of the Ly positions (all of them where Lx == Ly) and row a attends to the keys b <= a + Ly - Lx.
 struct Geo {
   int nseq, Lx, Ly, c1, c2, H, d, ff, causal;
 };
@@ -36,17 +39,21 @@ struct Scr {  // float offsets into an attention block's scratch
   int XN, YN, H1, MN, DH1, DXN, DYN, ST, F, DF, Q, K, V, O, DO, DQ, DK, DV, P, DS, total;
 };
 
+// YEXT: the caller holds the layer-normed y (it passes it as Y) and the accumulator of its gradient (it passes it as dY,
+// zeroes it and takes it through ln2's backward itself), so the scratch has neither and ST is for the x rows (the
+// cross-attention by chunks at S = TG_NET_WIDE3_S).
+template <bool YEXT = false>
 __host__ __device__ inline Scr scr_plan(const Geo& g) {
-  const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, NM = N > M ? N : M, PS = g.nseq * g.Lx * g.Ly;
+  const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, MY = YEXT ? 0 : M, NM = N > MY ? N : MY, PS = g.nseq * g.Lx * g.Ly;
   Scr s;
   s.XN = 0;
   s.YN = s.XN + N * g.c1;
-  s.H1 = s.YN + M * g.c2;
+  s.H1 = s.YN + MY * g.c2;
   s.MN = s.H1 + N * g.c1;
   s.DH1 = s.MN + N * g.c1;
   s.DXN = s.DH1 + N * g.c1;
   s.DYN = s.DXN + N * g.c1;
-  s.ST = s.DYN + M * g.c2;
+  s.ST = s.DYN + MY * g.c2;
   const int u = s.ST + 2 * NM;  // the MLP's (F, DF) and the head's buffers share the rest
   s.F = u;
   s.DF = s.F + N * g.ff;
@@ -73,8 +80,9 @@ struct ScrKV {
   int Q, O, QK, YB, DYB, DQK, P, DS, total;
 };
 
+template <bool YEXT = false>
 __host__ __device__ inline ScrKV scr_plan_kv(const Geo& g) {
-  const Scr s = scr_plan(g);
+  const Scr s = scr_plan<YEXT>(g);
   const int N = g.nseq * g.Lx, PS = g.nseq * g.Lx * g.Ly;
   ScrKV k;
   k.Q = s.Q;
@@ -180,13 +188,23 @@ __device__ inline void ln_bwd(const float* X, int R, int n, const float* __restr
   }
 }
 
+// ln_bwd over tiles of `tile` rows, so that st holds 2 * tile floats whatever R is; the tiles add to gw and gb in row
+// order.  Ends with a barrier.
+__device__ inline void ln_bwd_tiles(const float* X, int R, int n, const float* __restrict__ w, const float* dY, float* dX,
+                                    float* gw, float* gb, float* st, int tile) {
+  for (int r0 = 0; r0 < R; r0 += tile) {
+    ln_bwd(X + r0 * n, R - r0 < tile ? R - r0 : tile, n, w, dY + r0 * n, dX + r0 * n, gw, gb, st);
+    __syncthreads();
+  }
+}
+
 // softmax in place over the rows of the scores P (nseq x Lx x Ly), one thread per row; when causal, row a takes its
 // first a + 1 entries and the rest become 0
 __device__ inline void softmax_masked(const Geo& g, float* P) {
   const int Lx = g.Lx, Ly = g.Ly;
   for (int row = threadIdx.x; row < g.nseq * Lx; row += NT) {
     float* p = P + row * Ly;
-    const int n = g.causal ? row % Lx + 1 : Ly;
+    const int n = g.causal ? row % Lx + 1 + (Ly - Lx) : Ly;
     float m = p[0];
     for (int j = 1; j < n; ++j) m = fmaxf(m, p[j]);
     float s = 0.f;
@@ -265,7 +283,7 @@ __device__ inline void head_fwd(const Geo& g, const Mha& w, int h, const float* 
   const float sd = sqrtf(static_cast<float>(d));
   for (int it = threadIdx.x; it < g.nseq * Lx * Ly; it += NT) {
     const int b = it % Ly, a = (it / Ly) % Lx, s = it / (Lx * Ly);
-    if (g.causal && b > a) continue;
+    if (g.causal && b > a + (Ly - Lx)) continue;
     const float* q = Q + (s * Lx + a) * d;
     const float* k = K + (s * Ly + b) * d;
     float acc = 0.f;
@@ -288,9 +306,9 @@ __device__ inline void head_fwd(const Geo& g, const Mha& w, int h, const float* 
 
 // One head's forward without keys and values (scr_plan_kv): Q (N x d), QK = Q Wk_h (N x c2), the attention P as in
 // head_fwd, YB = P YN (N x c2) and O = YB Wv_h (N x d).  TEAM: the softmax by teams of 32 lanes (softmax_team).
-template <bool TEAM = false>
+template <bool TEAM = false, bool YEXT = false>
 __device__ inline void head_fwd_kv(const Geo& g, const Mha& w, int h, const float* XN, const float* YN, float* sc) {
-  const ScrKV S = scr_plan_kv(g);
+  const ScrKV S = scr_plan_kv<YEXT>(g);
   const int N = g.nseq * g.Lx, d = g.d, hd = g.H * d, c2 = g.c2, Lx = g.Lx, Ly = g.Ly;
   float *Q = sc + S.Q, *QK = sc + S.QK, *YB = sc + S.YB, *P = sc + S.P, *O = sc + S.O;
   net::mm(XN, g.c1, N, g.c1, w.q + h * d, hd, d, nullptr, Q, d);
@@ -327,18 +345,19 @@ __device__ inline void head_fwd_kv(const Geo& g, const Mha& w, int h, const floa
 // MultiHeadAttention.forward (model.py:44-67) up to li2: XN, YN, H1 = X + li1(heads), MN = ln3(H1), F = li2(MN) (before
 // the GELU).  With OUT, also OUT = H1 + li3(gelu(F)) (F then holds gelu(F)).  KV: the heads without keys and values
 // (scr_plan_kv), TEAM: their softmax by teams.  Ends with a barrier.
-template <bool KV = false, bool TEAM = false>
+template <bool KV = false, bool TEAM = false, bool YEXT = false>
 __device__ inline void mha_fwd(const Geo& g, const Mha& w, const float* X, const float* Y, float* OUT, float* sc) {
-  const Scr S = scr_plan(g);
+  const Scr S = scr_plan<YEXT>(g);
   const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, c1 = g.c1, d = g.d;
-  float *XN = sc + S.XN, *YN = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *F = sc + S.F,
-        *O = sc + (KV ? scr_plan_kv(g).O : S.O);
+  float *XN = sc + S.XN, *YNS = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *F = sc + S.F,
+        *O = sc + (KV ? scr_plan_kv<YEXT>(g).O : S.O);
+  const float* YN = YEXT ? Y : YNS;
   net::layernorm(X, c1, N, c1, w.ln1w, w.ln1b, XN, c1);
-  net::layernorm(Y, g.c2, M, g.c2, w.ln2w, w.ln2b, YN, g.c2);
+  if constexpr (!YEXT) net::layernorm(Y, g.c2, M, g.c2, w.ln2w, w.ln2b, YNS, g.c2);
   for (int it = threadIdx.x; it < N * c1; it += NT) H1[it] = X[it] + w.li1b[it % c1];
   __syncthreads();
   for (int h = 0; h < g.H; ++h) {
-    if constexpr (KV) head_fwd_kv<TEAM>(g, w, h, XN, YN, sc);
+    if constexpr (KV) head_fwd_kv<TEAM, YEXT>(g, w, h, XN, YN, sc);
     else head_fwd(g, w, h, XN, YN, sc);
     __syncthreads();
     net::mm(O, d, N, d, w.li1w + h * d * c1, c1, c1, nullptr, H1, c1, net::ACT_NONE, H1, nullptr, c1);
@@ -358,15 +377,15 @@ __device__ inline void mha_fwd(const Geo& g, const Mha& w, const float* X, const
 // the gradients of li1's slice, Wq_h, Wk_h and Wv_h into gw, dL/dXN into DXN and dL/dYN into DYN.  Ends with a barrier.
 //   dO = DH1 li1_h^T;  dYB = dO Wv_h^T, dWv_h += YB^T dO;  dP_ab = dYB_a . yn_b;  dS = P (dP - rowsum(P dP)) / sqrt(d);
 //   dQK = dS YN, dWk_h += Q^T dQK, dQ = dQK Wk_h;  dYN_b += sum_a (P_ab dYB_a + dS_ab QK_a).
-template <bool TEAM = false>
+template <bool TEAM = false, bool YEXT = false>
 __device__ inline void head_bwd_kv(const Geo& g, const Mha& w, const GMha& gw, int h, const float* XN, const float* YN,
                                    const float* DH1, float* DXN, float* DYN, float* sc) {
-  const ScrKV S = scr_plan_kv(g);
+  const ScrKV S = scr_plan_kv<YEXT>(g);
   const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, c1 = g.c1, c2 = g.c2, d = g.d, hd = g.H * d, Lx = g.Lx, Ly = g.Ly;
   float *Q = sc + S.Q, *O = sc + S.O, *QK = sc + S.QK, *YB = sc + S.YB, *DYB = sc + S.DYB, *DQK = sc + S.DQK,
         *P = sc + S.P, *DS = sc + S.DS;
   float *DO = O, *DQ = Q;
-  head_fwd_kv<TEAM>(g, w, h, XN, YN, sc);
+  head_fwd_kv<TEAM, YEXT>(g, w, h, XN, YN, sc);
   __syncthreads();
   wgrad(O, d, DH1, c1, N, d, c1, gw.li1w + h * d * c1, c1, nullptr);
   __syncthreads();
@@ -416,18 +435,20 @@ __device__ inline void head_bwd_kv(const Geo& g, const Mha& w, const GMha& gw, i
 
 // The backward of OUT = MHA(X, Y) for dOut: dX += dOUT/dX^T dOut, dY += ..., weight gradients into gw (a partial slab).
 // dY may be dX (self-attention).  Recomputes the forward.  KV: the heads without keys and values, TEAM: their softmax by
-// teams.  X, Y, dX and dY may lie in global memory that only this workgroup writes.  Ends with a barrier.
-template <bool KV = false, bool TEAM = false>
+// teams.  X, Y, dX and dY may lie in global memory that only this workgroup writes.  With YEXT, Y is ln2(y) and dY the
+// accumulator of its gradient (see scr_plan).  Ends with a barrier.
+template <bool KV = false, bool TEAM = false, bool YEXT = false>
 __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const float* X, const float* Y,
                                const float* dOut, float* dX, float* dY, float* sc) {
-  const Scr S = scr_plan(g);
+  const Scr S = scr_plan<YEXT>(g);
   const int N = g.nseq * g.Lx, M = g.nseq * g.Ly, c1 = g.c1, c2 = g.c2, d = g.d, hd = g.H * d, ff = g.ff;
   const int Lx = g.Lx, Ly = g.Ly;
-  float *XN = sc + S.XN, *YN = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *DH1 = sc + S.DH1, *DXN = sc + S.DXN,
-        *DYN = sc + S.DYN, *ST = sc + S.ST, *F = sc + S.F, *DF = sc + S.DF;
+  float *XN = sc + S.XN, *YNS = sc + S.YN, *H1 = sc + S.H1, *MN = sc + S.MN, *DH1 = sc + S.DH1, *DXN = sc + S.DXN,
+        *DYN = YEXT ? dY : sc + S.DYN, *ST = sc + S.ST, *F = sc + S.F, *DF = sc + S.DF;
+  const float* YN = YEXT ? Y : YNS;
   float *Q = sc + S.Q, *K = sc + S.K, *V = sc + S.V, *O = sc + S.O, *DO = sc + S.DO, *DQ = sc + S.DQ, *DK = sc + S.DK,
         *DV = sc + S.DV, *P = sc + S.P, *DS = sc + S.DS;
-  mha_fwd<KV, TEAM>(g, w, X, Y, nullptr, sc);
+  mha_fwd<KV, TEAM, YEXT>(g, w, X, Y, nullptr, sc);
   // the MLP: dF = (dOut li3^T) * gelu'(F)
   for (int it = threadIdx.x; it < N * ff; it += NT) {
     const int j = it % ff, r = it / ff;
@@ -452,12 +473,13 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
     dX[it] += DH1[it];
     DXN[it] = 0.f;
   }
-  for (int it = threadIdx.x; it < M * c2; it += NT) DYN[it] = 0.f;
+  if constexpr (!YEXT)
+    for (int it = threadIdx.x; it < M * c2; it += NT) DYN[it] = 0.f;
   bgrad(DH1, c1, N, c1, gw.li1b);
   __syncthreads();
   for (int h = 0; h < g.H; ++h) {
     if constexpr (KV) {
-      head_bwd_kv<TEAM>(g, w, gw, h, XN, YN, DH1, DXN, DYN, sc);
+      head_bwd_kv<TEAM, YEXT>(g, w, gw, h, XN, YN, DH1, DXN, DYN, sc);
       continue;
     }
     head_fwd(g, w, h, XN, YN, sc);
@@ -509,6 +531,7 @@ __device__ inline void mha_bwd(const Geo& g, const Mha& w, const GMha& gw, const
   }
   ln_bwd(X, N, c1, w.ln1w, DXN, dX, gw.ln1w, gw.ln1b, ST);
   __syncthreads();
+  if constexpr (YEXT) return;
   ln_bwd(Y, M, c2, w.ln2w, DYN, dY, gw.ln2w, gw.ln2b, ST);
   __syncthreads();
 }
@@ -641,6 +664,12 @@ inline int torso_chunk(const tg_net_config& c) {
   return (c.S + chunks - 1) / chunks;
 }
 
+// Whether a game strategy of decode runs the self-attention block itself (self_fwd / self_bwd).
+template <class V, class = void>
+struct has_self_hooks : std::false_type {};
+template <class V>
+struct has_self_hooks<V, std::void_t<decltype(&V::self_fwd)>> : std::true_type {};
+
 __device__ inline void game_range(const Args& a, int64_t& g0, int64_t& g1) {
   g0 = a.B * blockIdx.x / a.P;
   g1 = a.B * (blockIdx.x + 1) / a.P;
@@ -652,6 +681,8 @@ __device__ inline void game_range(const Args& a, int64_t& g0, int64_t& g1) {
 //   DPlan plan(c)                            the LDS plan;
 //   float* xs(a, lds, L)                     the saved block inputs (blocks x 2 x n_steps x W), this workgroup's own;
 //   void game(a, g, lds, L, EE, DEE)         sets EE and DEE for game g (EE filled, DEE zero after the next barrier);
+//   void self_fwd / self_bwd                 optional: mha_fwd / mha_bwd of the self-attention block on all n_steps
+//                                            positions, where the plan has no room for scr_plan(self_geo(c));
 //   void cross_fwd / cross_bwd               mha_fwd / mha_bwd of the cross-attention block on all n_steps positions;
 //   void game_done(a, g, DEE)                leaves dL/dee of game g in a.dee.
 template <class V>
@@ -729,7 +760,8 @@ __device__ inline void decode(const Args& a, const V& v) {
       for (int it = threadIdx.x; it < N * W; it += NT) xin[it] = X[it];
       net::layernorm(X, W, N, W, bp, bp + W, XB, W);
       __syncthreads();
-      mha_fwd(g1, a1, XB, XB, MO, SCR);
+      if constexpr (has_self_hooks<V>::value) v.self_fwd(g1, a1, XB, MO, SCR);
+      else mha_fwd(g1, a1, XB, XB, MO, SCR);
       for (int it = threadIdx.x; it < N * W; it += NT) {
         const float v = XB[it] + (k1[it] ? a.scale : 0.f) * MO[it];
         X[it] = v;
@@ -836,7 +868,8 @@ __device__ inline void decode(const Args& a, const V& v) {
         DXB[it] = DX[it];
       }
       __syncthreads();
-      mha_bwd(g1, a1, ga1, XB, XB, MO, DXB, DXB, SCR);
+      if constexpr (has_self_hooks<V>::value) v.self_bwd(g1, a1, ga1, XB, MO, DXB, SCR);
+      else mha_bwd(g1, a1, ga1, XB, XB, MO, DXB, DXB, SCR);
       for (int it = threadIdx.x; it < N * W; it += NT) DX[it] = 0.f;
       __syncthreads();
       ln_bwd(xin, N, W, bp, DXB, DX, gp, gp + W, SCR);

@@ -14,7 +14,8 @@ Supported: dim_3d <= 5, or exactly 9 (3x3 matmul) or 16 (4x4 matmul, n_steps <= 
 workgroup per (game, slice) instead of one per game, and training goes through ``train.SlicedTrainer``), inside the TG_NET_MAX_* bounds and the LDS plans of the
 header; ``check_config`` names the bound otherwise.  The 5x5 matmul tensor, dim_3d = 25 (n_steps <= 75), has a class
 of its own, ``FusedAlphaTensor25``, on the entries of include/tensor_game_net_s25.h (the decoder keeps one normalised
-copy of the torso output for all policy blocks there); it takes that size only, and there is no training at it.
+copy of the torso output for all policy blocks there); it takes that size only, and training there goes through
+``train.SlicedTrainer25``.
 
 The draws follow the header's sampling rule (Philox keyed by seed, counter (game, call, sample, step block)), not
 torch's generator: the distribution is the reference's, the individual draws are not.  There is no CPU path.

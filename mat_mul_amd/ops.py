@@ -27,6 +27,7 @@ __all__ = [
     "net_s25_check", "net_s25_weights_size", "net_s25_torso", "net_s25_sample", "net_s25_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
     "net_train_sliced_check", "net_train_sliced_workspace_size", "net_loss_grad_sliced",
+    "net_train_s25_check", "net_train_s25_workspace_size", "net_loss_grad_s25",
     "rollout_check", "rollout_records", "rollout_advance",
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
 ]
@@ -1026,9 +1027,11 @@ def net_loss_grad(cfg, theta, pos_fix, frames, scalars, g_action, g_value, works
 
 
 def _loss_grad(fn, symbol, size_symbol, cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad, losses,
-               status, weight_pol, weight_val, dropout_p, seed, call_idx, keep_in, keep_out):
-    """The argument rules and the launch of net_loss_grad and net_loss_grad_sliced, which differ in the C symbols."""
-    dev = _net_blob(cfg, theta)
+               status, weight_pol, weight_val, dropout_p, seed, call_idx, keep_in, keep_out,
+               weights_symbol="tg_net_weights_size"):
+    """The argument rules and the launch of net_loss_grad, net_loss_grad_sliced and net_loss_grad_s25, which differ in
+    the C symbols."""
+    dev = _net_blob(cfg, theta, weights_symbol)
     B = _net_frames(cfg, frames, dev, fn)
     if B < 1:
         raise TensorGameError(fn, -1, "B must be at least 1")
@@ -1078,6 +1081,28 @@ def net_loss_grad_sliced(cfg, theta, pos_fix, frames, scalars, g_action, g_value
     return _loss_grad("net_loss_grad_sliced", "tg_net_loss_grad_sliced", "tg_net_train_sliced_workspace_size", cfg, theta,
                       pos_fix, frames, scalars, g_action, g_value, workspace, grad, losses, status, weight_pol, weight_val,
                       dropout_p, seed, call_idx, keep_in, keep_out)
+
+
+# ---- include/tensor_game_train_s25.h: the same three entries at S = TG_NET_WIDE3_S ------------------------------------
+def net_train_s25_check(cfg) -> None:
+    """Raise TensorGameError (naming the bound) unless ``cfg`` is in the S = 25 training family
+    (tg_net_train_s25_check): tg_net_s25_check's and the three LDS plans within 160 KiB."""
+    call("tg_net_train_s25_check", C.byref(cfg))
+
+
+def net_train_s25_workspace_size(cfg, B: int) -> int:
+    """Bytes of workspace tg_net_loss_grad_s25 needs for B games."""
+    return _workspace_size("tg_net_train_s25_workspace_size", cfg, B)
+
+
+def net_loss_grad_s25(cfg, theta, pos_fix, frames, scalars, g_action, g_value, workspace, grad=None, losses=None,
+                      status=None, weight_pol: float = 1.0, weight_val: float = 1000.0, dropout_p: float = 0.0,
+                      seed: int = 0, call_idx: int = 0, keep_in=None, keep_out=None):
+    """net_loss_grad at S = TG_NET_WIDE3_S (tg_net_loss_grad_s25): the same arguments and results, workspace of at
+    least net_train_s25_workspace_size bytes."""
+    return _loss_grad("net_loss_grad_s25", "tg_net_loss_grad_s25", "tg_net_train_s25_workspace_size", cfg, theta,
+                      pos_fix, frames, scalars, g_action, g_value, workspace, grad, losses, status, weight_pol, weight_val,
+                      dropout_p, seed, call_idx, keep_in, keep_out, weights_symbol="tg_net_s25_weights_size")
 
 
 # ---- sampled policy rollouts (include/tensor_game_rollout.h) --------------------------------------------------------

@@ -309,7 +309,7 @@ def save_run(path, trainer, optimizer, data, generators: Optional[Mapping[str, t
 def load_run(path, device) -> RunState:
     """The run ``save_run`` wrote, rebuilt on ``device``.  ``trainer.pt`` is read with ``weights_only=True``."""
     from .replay import TensorGameData
-    from .train import FusedTrainer, SlicedTrainer
+    from .train import FusedTrainer, SlicedTrainer, SlicedTrainer25
 
     dev = _gpu(device, "load_run")
     path = Path(path)
@@ -319,6 +319,7 @@ def load_run(path, device) -> RunState:
         gens[name] = torch.Generator(device=dev)
         gens[name].set_state(state)
     # the class the checkpoint names; a file without the key is a FusedTrainer's
-    cls = {"fused": FusedTrainer, "sliced": SlicedTrainer}[d["trainer"].get("kind", "fused")]
+    kinds = {"fused": FusedTrainer, "sliced": SlicedTrainer, "sliced25": SlicedTrainer25}
+    cls = kinds[d["trainer"].get("kind", "fused")]
     return RunState(cls.from_checkpoint(d["trainer"], dev), d["optimizer"],
                     TensorGameData.load(path / "data.tgd", dev), gens, d["extra"])

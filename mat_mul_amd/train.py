@@ -25,9 +25,9 @@ import torch
 
 from . import ops
 from ._lib import TensorGameError
-from .net import _P, CONFIG_FIELDS, FusedAlphaTensor, check_config, infer_config, pack_weights
+from .net import _P, CONFIG_FIELDS, FusedAlphaTensor, FusedAlphaTensor25, check_config, infer_config, pack_weights
 
-__all__ = ["FusedTrainer", "SlicedTrainer", "unpack_weights", "blob_layout"]
+__all__ = ["FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "unpack_weights", "blob_layout"]
 
 
 def _mha_layout(p: str, c1: int, c2: int, H: int, d: int, ff: int, out: list) -> None:
@@ -113,13 +113,17 @@ class FusedTrainer:
     _check = staticmethod(ops.net_train_check)
     _workspace_size = staticmethod(ops.net_train_workspace_size)
     _loss_grad = staticmethod(ops.net_loss_grad)
+    # the inference family's check, the blob's size and the inference class of net()
+    _net_check = staticmethod(ops.net_check)
+    _weights_size = staticmethod(ops.net_weights_size)
+    _net = FusedAlphaTensor
 
     def __init__(self, cfg: Mapping[str, int], theta: torch.Tensor, pos_fix: torch.Tensor, dropout_p: float = 0.5,
                  weight_pol: float = 1.0, weight_val: float = 1000.0, n_samples: int = 4, seed: int = 0):
         self.config = {k: int(cfg[k]) for k in CONFIG_FIELDS}
-        self.c = check_config(self.config)
+        self.c = check_config(self.config, self._net_check)
         self._check(self.c)
-        n = ops.net_weights_size(self.c)
+        n = self._weights_size(self.c)
         if theta.numel() != n or theta.dtype != torch.float32 or not theta.is_cuda:
             raise TensorGameError("FusedTrainer", -1, f"theta must be {n} float32 on a ROCm device, got {theta.dtype} "
                                   f"{tuple(theta.shape)} on {theta.device}")
@@ -147,7 +151,7 @@ class FusedTrainer:
         if dev.type != "cuda":
             raise TensorGameError("FusedTrainer", -1, "a ROCm device is required; there is no CPU path")
         cfg = infer_config(sd)
-        check_config(cfg)
+        check_config(cfg, cls._net_check)
         theta = torch.from_numpy(pack_weights(sd, cfg, fold_pos=False)).to(dev)
         fix = torch.as_tensor(np.asarray(sd[_P + "pos_enc_fix"].detach().cpu() if isinstance(
             sd[_P + "pos_enc_fix"], torch.Tensor) else sd[_P + "pos_enc_fix"], np.float32))
@@ -221,7 +225,7 @@ class FusedTrainer:
 
     def net(self, n_samples: Optional[int] = None) -> FusedAlphaTensor:
         """A ``FusedAlphaTensor`` on the trainer's inference blob (shared: every train_step updates it)."""
-        return FusedAlphaTensor(self.config, self._blob, n_samples or self.n_samples)
+        return self._net(self.config, self._blob, n_samples or self.n_samples)
 
     def checkpoint(self) -> dict:
         """Everything a resumed trainer needs, as host tensors and plain scalars (``torch.save`` it; it loads with
@@ -261,3 +265,21 @@ class SlicedTrainer(FusedTrainer):
     def checkpoint(self) -> dict:
         """``FusedTrainer.checkpoint`` with ``"kind": "sliced"``, by which ``replay_io.load_run`` builds this class."""
         return dict(super().checkpoint(), kind="sliced")
+
+
+class SlicedTrainer25(FusedTrainer):
+    """``FusedTrainer`` at the 5x5 matmul tensor (dim_3d = 25), the size ``FusedTrainer`` and ``SlicedTrainer`` refuse:
+    the same constructor, classmethods and methods on include/tensor_game_train_s25.h's entries
+    (``tg_net_loss_grad_s25``), which cut the torso by slices and both attention blocks of the decoder by chunks of
+    positions.  ``net()`` is a ``FusedAlphaTensor25``.  Every other size is refused here."""
+
+    _check = staticmethod(ops.net_train_s25_check)
+    _workspace_size = staticmethod(ops.net_train_s25_workspace_size)
+    _loss_grad = staticmethod(ops.net_loss_grad_s25)
+    _net_check = staticmethod(ops.net_s25_check)
+    _weights_size = staticmethod(ops.net_s25_weights_size)
+    _net = FusedAlphaTensor25
+
+    def checkpoint(self) -> dict:
+        """``FusedTrainer.checkpoint`` with ``"kind": "sliced25"``, by which ``replay_io.load_run`` builds this class."""
+        return dict(super().checkpoint(), kind="sliced25")

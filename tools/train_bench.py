@@ -11,7 +11,9 @@ a kernel-trace run); --kernel-stats merges a rocprofv3 --stats CSV into an exist
 Writes OUT_DIR/r09_train.json.  --config picks another configuration of net_ref.CONFIGS or tests/net_s9_ref.CONFIGS
 (a9, b9: S = 9); the file is then OUT_DIR/r09_train_<config>.json.  --config a16 or b16 (tests/net_s16_ref.CONFIGS,
 S = 16) times SlicedTrainer (include/tensor_game_train_sliced.h) at B in {16, 256} and writes
-OUT_DIR/r13_train_<config>.json.
+OUT_DIR/r13_train_<config>.json.  --config a25 or b25 (tests/net_s25_ref.CONFIGS, S = 25) times SlicedTrainer25
+(include/tensor_game_train_s25.h) at B in {16, 64, 256} (--batches picks others) and writes
+OUT_DIR/r18_train_<config>.json.
 """
 from __future__ import annotations
 
@@ -29,12 +31,15 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from mat_mul_amd import FusedTrainer, SlicedTrainer  # noqa: E402
+from mat_mul_amd import FusedTrainer, SlicedTrainer, SlicedTrainer25  # noqa: E402
 from net_ref import CONFIGS, make_weights  # noqa: E402
 from net_s9_ref import CONFIGS as CONFIGS_S9  # noqa: E402
 from net_s16_ref import CONFIGS as CONFIGS_S16  # noqa: E402
+from net_s25_ref import RECORDED as NAMES_S25  # noqa: E402
+from net_s25_ref import CONFIGS as CONFIGS_S25_ALL  # noqa: E402
 from train_ref import TrainRef, keep_mask, make_batch, multipliers  # noqa: E402
 
+CONFIGS_S25 = {k: CONFIGS_S25_ALL[k] for k in NAMES_S25}  # a25, b25
 DEV = "cuda:0"
 P_DROP = 0.5
 
@@ -77,24 +82,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--kernel-stats")
-    ap.add_argument("--config", default="a", choices=sorted({**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}))
+    ap.add_argument("--config", default="a", choices=sorted({**CONFIGS, **CONFIGS_S9, **CONFIGS_S16, **CONFIGS_S25}))
+    ap.add_argument("--batches", type=int, nargs="+", help="the batch sizes, in place of the configuration's")
     args = ap.parse_args()
-    sliced = args.config in CONFIGS_S16
+    sliced, s25 = args.config in CONFIGS_S16, args.config in CONFIGS_S25
     out = Path(args.out) / ("r09_train.json" if args.config == "a" else
-                            f"{'r13' if sliced else 'r09'}_train_{args.config}.json")
+                            f"{'r18' if s25 else 'r13' if sliced else 'r09'}_train_{args.config}.json")
     if args.kernel_stats:
         res = json.loads(out.read_text())
         res["kernel_stats"] = kernel_stats(args.kernel_stats)
         out.write_text(json.dumps(res, indent=1) + "\n")
         print(json.dumps(res["kernel_stats"], indent=1))
         return
-    cfg = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16}[args.config]
+    cfg = {**CONFIGS, **CONFIGS_S9, **CONFIGS_S16, **CONFIGS_S25}[args.config]
     sd = make_weights(cfg, 1)
-    tr = (SlicedTrainer if sliced else FusedTrainer).from_state_dict(sd, dropout_p=P_DROP, device=DEV)
+    cls = SlicedTrainer25 if s25 else SlicedTrainer if sliced else FusedTrainer
+    tr = cls.from_state_dict(sd, dropout_p=P_DROP, device=DEV)
     opt = torch.optim.AdamW([tr.params], lr=1e-4)
     res = {"config": args.config, "dropout_p": P_DROP, "torch": torch.__version__,
            "device": torch.cuda.get_device_name(0), "rows": []}
-    for B in ((16, 256) if sliced else (256, 1024, 4096)):
+    for B in args.batches or ((16, 64, 256) if s25 else (16, 256) if sliced else (256, 1024, 4096)):
         batch = tuple(torch.from_numpy(x).to(DEV) for x in make_batch(cfg, B, B))
         row = {"B": B}
         row["fused_loss_grad"] = timed(lambda: tr.loss_and_grad(*batch), args.reps, args.warmup)
