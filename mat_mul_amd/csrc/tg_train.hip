@@ -194,6 +194,11 @@ int check_train_cfg(const char* fn, const tg_net_config* c) {
   return TG_OK;
 }
 
+// the workspace: ee, dL/dee, the saved pair inputs, the per-game losses and flags, one slab per decoder workgroup
+tg::train::Ws ws_whole(const tg_net_config& c, int64_t B) {
+  return tg::train::ws_plan(c, B, tg::train::partials(B), false, false);
+}
+
 // The four launches of one call: the torso forward, the decoder, the torso backward when a gradient is wanted, the
 // reduction.  lt, ld: the LDS bytes of the torso kernels and of the decoder; chunk: the chunked torso kernels' argument.
 template <auto FWD, auto DEC, auto BWD, class... Chunk>
@@ -218,11 +223,7 @@ int tg_net_train_check(const tg_net_config* cfg) { return check_train_cfg("tg_ne
 
 int tg_net_train_workspace_size(const tg_net_config* cfg, int64_t B, int64_t* bytes) {
   const char* fn = "tg_net_train_workspace_size";
-  if (int rc = check_train_cfg(fn, cfg)) return rc;
-  if (B < 1 || B > (1LL << 24)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld outside [1, 2^24]", fn, (long long)B);
-  if (!bytes) return tg_internal_fail(TG_ERR_INVALID, "%s: null output", fn);
-  *bytes = tg::train::ws_plan(*cfg, B).total;
-  return TG_OK;
+  return tg::train::workspace_size(fn, check_train_cfg(fn, cfg), cfg, B, bytes, ws_whole);
 }
 
 // AlphaTensor.fwd_train (model.py:326-345) in train mode, the weighted loss and its backward (training.py:431-437)
@@ -231,35 +232,23 @@ int tg_net_loss_grad(const tg_net_config* cfg, const float* theta, const float* 
                      float weight_pol, float weight_val, float dropout_p, uint64_t seed, uint64_t call,
                      const uint8_t* keep_in, uint8_t* keep_out, void* workspace, int64_t workspace_bytes, float* grad,
                      float* losses, uint32_t* status, tg_stream_t stream) {
+  using namespace tg::train;
   const char* fn = "tg_net_loss_grad";
   if (int rc = check_train_cfg(fn, cfg)) return rc;
-  if (int rc = tg::train::check_call(fn, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B, weight_pol,
-                                     weight_val, dropout_p, workspace, grad, losses, status))
+  Call k;
+  if (int rc = prepare_call(fn, *cfg, ws_whole, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B,
+                            weight_pol, weight_val, dropout_p, seed, call, keep_in, keep_out, workspace, workspace_bytes,
+                            grad, losses, status, k))
     return rc;
-  const tg::train::Ws ws = tg::train::ws_plan(*cfg, B);
-  if (workspace_bytes < ws.total)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed", fn, (long long)workspace_bytes,
-                            (long long)ws.total);
-  tg::train::Args a = tg::train::call_args(*cfg, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B,
-                                           weight_pol, weight_val, dropout_p, seed, call, keep_in, keep_out, grad, losses,
-                                           status);
-  a.P = tg::train::partials(B);
-  char* base = static_cast<char*>(workspace);
-  a.ee = reinterpret_cast<float*>(base + ws.ee);
-  a.dee = reinterpret_cast<float*>(base + ws.dee);
-  a.act = reinterpret_cast<float*>(base + ws.act);
-  a.gl = reinterpret_cast<float*>(base + ws.gl);
-  a.flags = reinterpret_cast<int*>(base + ws.flags);
-  a.slabs = reinterpret_cast<float*>(base + ws.slabs);
+  k.a.P = partials(B);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  using namespace tg::train;
   if (wide(*cfg)) {
     const int chunk = torso_chunk(*cfg);
     return launch_all<train_torso_fwd_chunk_kernel, train_decode_kv_kernel, train_torso_bwd_chunk_kernel>(
-        fn, a, tplan(*cfg, chunk).total * sizeof(float), dplan_kv(*cfg).total * sizeof(float), st, chunk);
+        fn, k.a, tplan(*cfg, chunk).total * sizeof(float), dplan_kv(*cfg).total * sizeof(float), st, chunk);
   }
   return launch_all<train_torso_fwd_kernel, train_decode_kernel, train_torso_bwd_kernel>(
-      fn, a, tplan(*cfg).total * sizeof(float), dplan(*cfg).total * sizeof(float), st);
+      fn, k.a, tplan(*cfg).total * sizeof(float), dplan(*cfg).total * sizeof(float), st);
 }
 
 }  // extern "C"

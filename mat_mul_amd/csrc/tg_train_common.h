@@ -1,8 +1,8 @@
-// Shared by tg_train.hip (training, whole games), tg_train_sliced.hip (training at S = TG_NET_WIDE2_S) and
-// tg_train_s25.hip (training at S = TG_NET_WIDE3_S): one attention
-// block's geometry, LDS scratch, forward and backward; the kernels' arguments, workspace and LDS plans; the decoder's
-// body (forward, losses, backward) over a policy that says where ee, dL/dee and the saved block inputs live and how the
-// cross-attention block runs; and the fixed-order reduction.
+// Shared by tg_train.hip (training, whole games) and tg_train_sliced.hip (training at S = TG_NET_WIDE2_S and at
+// S = TG_NET_WIDE3_S): one attention block's geometry, LDS scratch, forward and backward; the kernels' arguments,
+// workspace and LDS plans; the decoder's body (forward, losses, backward) over a policy that says where ee, dL/dee and
+// the saved block inputs live and how the attention blocks run; the host path of the entries (the argument rules, the
+// workspace's size, the kernels' arguments); and the fixed-order reduction.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -560,15 +560,17 @@ struct Args {
   uint32_t* status;
 };
 
-struct Ws {  // byte offsets into the workspace
-  int64_t ee, dee, act, gl, flags, slabs, total;
+struct Ws {  // byte offsets into the workspace; a part a family does not have takes no room
+  int64_t ee, dee, act, gl, flags, xs, slabs, dyn, total;
 };
 
 inline int64_t round256(int64_t x) { return (x + 255) / 256 * 256; }
 
 inline int partials(int64_t B) { return static_cast<int>(B < TG_NET_TRAIN_PARTIALS ? B : TG_NET_TRAIN_PARTIALS); }
 
-inline Ws ws_plan(const tg_net_config& c, int64_t B) {
+// slabs: the partial slabs of the gradient.  xs: each of the decoder's partials(B) workgroups keeps its saved block inputs
+// here; dyn: each has a J x c accumulator here (tg_train_sliced.hip).
+inline Ws ws_plan(const tg_net_config& c, int64_t B, int slabs, bool xs, bool dyn) {
   const int64_t J = 3LL * c.S * c.S, T2 = 2LL * c.S * c.S;
   Ws w;
   int64_t p = 0;
@@ -577,7 +579,9 @@ inline Ws ws_plan(const tg_net_config& c, int64_t B) {
   w.act = p; p += round256(4 * B * c.torso_layers * 3 * T2 * c.c);
   w.gl = p; p += round256(4 * 2 * B);
   w.flags = p; p += round256(4 * B);
-  w.slabs = p; p += round256(4 * partials(B) * net::offsets(c).total);
+  w.xs = p; p += round256(xs ? 4LL * partials(B) * c.blocks * 2 * c.n_steps * c.W : 0);
+  w.slabs = p; p += round256(4LL * slabs * net::offsets(c).total);
+  w.dyn = p; p += round256(dyn ? 4LL * partials(B) * J * c.c : 0);
   w.total = p;
   return w;
 }
@@ -655,13 +659,20 @@ __host__ __device__ inline DPlan dplan_kv(const tg_net_config& c) {
 // time, and the decoder's cross-attention without keys and values.  Every other S keeps the whole-pair kernels.
 __host__ __device__ inline bool wide(const tg_net_config& c) { return c.S == TG_NET_WIDE_S; }
 
-// Sequences per chunk of the wide torso: the fewest chunks whose plan fits, evened out; 0 if not even one sequence fits.
-inline int torso_chunk(const tg_net_config& c) {
-  int n = c.S;
-  while (n > 0 && tplan(c, n).total * sizeof(float) > static_cast<size_t>(kMaxDynamicLds)) --n;
+// The rule of every chunked loop: `total` rows in the fewest chunks whose plan fits, evened out.  floats(n): the plan's
+// size at n rows per chunk.  The rows per chunk; 0 if not even one row fits.
+template <class Floats>
+inline int even_chunk(int total, Floats floats) {
+  int n = total;
+  while (n > 0 && floats(n) * sizeof(float) > static_cast<size_t>(kMaxDynamicLds)) --n;
   if (n == 0) return 0;
-  const int chunks = (c.S + n - 1) / n;
-  return (c.S + chunks - 1) / chunks;
+  const int chunks = (total + n - 1) / n;
+  return (total + chunks - 1) / chunks;
+}
+
+// Sequences per chunk of the wide torso.
+inline int torso_chunk(const tg_net_config& c) {
+  return even_chunk(c.S, [&](int n) { return tplan(c, n).total; });
 }
 
 // Whether a game strategy of decode runs the self-attention block itself (self_fwd / self_bwd).
@@ -886,13 +897,30 @@ __device__ inline void decode(const Args& a, const V& v) {
   }
 }
 
-// ---- one call's arguments (host) --------------------------------------------------------------------------------------
-// The argument rules of tg_net_loss_grad and tg_net_loss_grad_sliced after the configuration's check, in this order; the
-// workspace's size is the caller's to compare.
-inline int check_call(const char* fn, const float* theta, const float* pos_fix, const void* frames, int frames_is_i8,
-                      const float* scalars, const int8_t* g_action, const float* g_value, int64_t B, float weight_pol,
-                      float weight_val, float dropout_p, const void* workspace, const float* grad, const float* losses,
-                      const uint32_t* status) {
+// ---- the host path of the entries (every family's, after its own check of the configuration) -----------------------
+using WsPlan = Ws (*)(const tg_net_config&, int64_t);  // a family's workspace at B games
+
+// A *_workspace_size entry; rc: the family's check of cfg.
+inline int workspace_size(const char* fn, int rc, const tg_net_config* cfg, int64_t B, int64_t* bytes, WsPlan plan) {
+  if (rc) return rc;
+  if (B < 1 || B > (1LL << 24)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld outside [1, 2^24]", fn, (long long)B);
+  if (!bytes) return tg_internal_fail(TG_ERR_INVALID, "%s: null output", fn);
+  *bytes = plan(*cfg, B).total;
+  return TG_OK;
+}
+
+struct Call {
+  Args a;           // the kernels' arguments, all but P
+  float *xs, *dyn;  // the workspace parts that are no member of Args (the family's plan says whether it has them)
+};
+
+// A loss entry up to its launches: the argument rules in this order, the workspace's size against the family's plan,
+// then the kernels' arguments.
+inline int prepare_call(const char* fn, const tg_net_config& cfg, WsPlan plan, const float* theta, const float* pos_fix,
+                        const void* frames, int frames_is_i8, const float* scalars, const int8_t* g_action,
+                        const float* g_value, int64_t B, float weight_pol, float weight_val, float dropout_p, uint64_t seed,
+                        uint64_t call, const uint8_t* keep_in, uint8_t* keep_out, void* workspace, int64_t workspace_bytes,
+                        float* grad, float* losses, uint32_t* status, Call& k) {
   if (B < 1 || B > (1LL << 24)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld outside [1, 2^24]", fn, (long long)B);
   if (!(dropout_p >= 0.f && dropout_p < 1.f))
     return tg_internal_fail(TG_ERR_INVALID, "%s: dropout_p=%g outside [0, 1)", fn, static_cast<double>(dropout_p));
@@ -906,15 +934,12 @@ inline int check_call(const char* fn, const float* theta, const float* pos_fix, 
   if (!aligned(theta, 4) || !aligned(pos_fix, 4) || !aligned(frames, frames_is_i8 ? 1 : 4) || !aligned(scalars, 4) ||
       !aligned(g_value, 4) || !aligned(grad, 4) || !aligned(losses, 4) || !aligned(status, 4) || !aligned(workspace, 256))
     return tg_internal_fail(TG_ERR_INVALID, "%s: an argument is not aligned to its elements (workspace: 256 bytes)", fn);
-  return TG_OK;
-}
-
-// The kernels' arguments but the workspace parts and P.
-inline Args call_args(const tg_net_config& cfg, const float* theta, const float* pos_fix, const void* frames,
-                      int frames_is_i8, const float* scalars, const int8_t* g_action, const float* g_value, int64_t B,
-                      float weight_pol, float weight_val, float dropout_p, uint64_t seed, uint64_t call,
-                      const uint8_t* keep_in, uint8_t* keep_out, float* grad, float* losses, uint32_t* status) {
-  Args a{};
+  const Ws ws = plan(cfg, B);
+  if (workspace_bytes < ws.total)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed", fn, (long long)workspace_bytes,
+                            (long long)ws.total);
+  Args& a = k.a;
+  a = Args{};
   a.c = cfg;
   a.off = net::offsets(cfg);
   a.w = theta;
@@ -938,11 +963,20 @@ inline Args call_args(const tg_net_config& cfg, const float* theta, const float*
   a.grad = grad;
   a.losses = losses;
   a.status = status;
-  return a;
+  char* base = static_cast<char*>(workspace);
+  a.ee = reinterpret_cast<float*>(base + ws.ee);
+  a.dee = reinterpret_cast<float*>(base + ws.dee);
+  a.act = reinterpret_cast<float*>(base + ws.act);
+  a.gl = reinterpret_cast<float*>(base + ws.gl);
+  a.flags = reinterpret_cast<int*>(base + ws.flags);
+  a.slabs = reinterpret_cast<float*>(base + ws.slabs);
+  k.xs = reinterpret_cast<float*>(base + ws.xs);
+  k.dyn = reinterpret_cast<float*>(base + ws.dyn);
+  return TG_OK;
 }
 
 // ---- the last launch: the partial slabs, the losses, the status -----------------------------------------------------
-// static: each source that launches it holds its own copy.
+// static: a kernel is launched from the object that defines it, so tg_train.hip and tg_train_sliced.hip each hold one.
 static __global__ void __launch_bounds__(NT) train_reduce_kernel(Args a, int grad_blocks) {
   __shared__ float sp[NT], sv[NT];
   __shared__ int sf[NT];

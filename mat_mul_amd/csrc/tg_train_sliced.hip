@@ -1,5 +1,5 @@
-// The training loss and gradient at S = TG_NET_WIDE2_S (include/tensor_game_train_sliced.h).  gfx950 only; part of
-// libtensorgame.so.
+// The training loss and gradient at S = TG_NET_WIDE2_S (include/tensor_game_train_sliced.h) and at S = TG_NET_WIDE3_S
+// (include/tensor_game_train_s25.h).  gfx950 only; part of libtensorgame.so.
 //
 // The four launches of tg_train.hip cut to fit a workgroup's LDS at 3 x 256 torso rows and J = 768 keys, on the building
 // blocks of tg_train_common.h:
@@ -11,39 +11,99 @@
 //   - train_torso_bwd_slice_kernel: Pt workgroups, each a contiguous run of (game, slice) units in order, the pairs in
 //     reverse, each recomputed from its saved input, into slab p.
 //   - train_reduce_kernel over the Pt slabs.
-// No float atomics: a slab element, a dL/dee row and a saved block input are only ever written by one workgroup, between
-// barriers.
+// S = TG_NET_WIDE3_S takes the same torso kernels (they take S at run time) and a decoder cut once more, because at
+// n_steps = 75 and J = 1875 keys neither attention block of the decoder fits a workgroup's LDS beside the per-game rows:
+//   - train_decode_s25_kernel: Pd workgroups, the decoder body over Game25.  The self-attention block runs over chunks of
+//     nqs query positions against the keys up to the chunk's last row (causal: later keys have no weight); the
+//     cross-attention block over chunks of nqx query positions against one layer-normed copy of ee in LDS, with
+//     dL/d ln2(ee) in a J x c accumulator of the workgroup's own in the workspace and ln2's backward into dL/dee over
+//     tiles of keys after the last chunk.
+// No float atomics: a slab element, a dL/dee row, a saved block input and an accumulator element are only ever written
+// by one workgroup, between barriers.
+#include "../../include/tensor_game_net_s25.h"
+#include "../../include/tensor_game_train_s25.h"
 #include "../../include/tensor_game_train_sliced.h"
-#include "tg_train_slices.h"
+#include "tg_train_common.h"
 
 namespace tg {
 namespace train {
 
+constexpr int kLnTile = 256;  // keys per tile of ln2's backward into dL/dee (2 * kLnTile floats of scratch)
+
 // ---- LDS plans --------------------------------------------------------------------------------------------------------
-// the cross-attention block on nq decoder positions
+// the torso kernels: tplan's buffers for one slice (3S grid rows, 3S input rows, a pair's 2S tokens), one sequence of scratch
+__host__ __device__ inline TPlan tplan_slice(const tg_net_config& c) {
+  const int S = c.S, cin = S * c.T + 1;
+  TPlan p;
+  p.G = 0;
+  p.IN = p.G + 3 * S * c.c;
+  p.X = p.IN + 3 * S * cin;
+  p.DO = p.X + 2 * S * c.c;
+  p.DX = p.DO + 2 * S * c.c;
+  p.SS = p.DX + 2 * S * c.c;
+  p.DP = p.SS + TG_NET_MAX_DIM_S;
+  p.SCR = p.DP + 3 * S;
+  p.total = p.SCR + scr_plan(torso_geo(c, 1)).total;
+  return p;
+}
+
+// the self-attention block on nq query positions, keys and values of all n_steps
+__host__ __device__ inline Geo self_geo25(const tg_net_config& c, int nq) {
+  Geo g = self_geo(c);
+  g.Lx = nq;
+  return g;
+}
+
+// the cross-attention block on nq query positions
 __host__ __device__ inline Geo cross_geo(const tg_net_config& c, int nq) {
   Geo g = cross_geo(c);
   g.Lx = nq;
   return g;
 }
 
-// the decoder kernel: dplan's per-game rows without ee, dL/dee and the saved block inputs, and the larger of the
-// self-attention's scratch and the cross-attention's for nq positions without keys and values
+// S = TG_NET_WIDE2_S's decoder kernel: dplan's per-game rows without ee, dL/dee and the saved block inputs, and the larger
+// of the self-attention's scratch and the cross-attention's for nq positions without keys and values
 __host__ __device__ inline DPlan dplan_sliced(const tg_net_config& c, int nq) {
   return dplan_with(c, false, scr_plan_kv(cross_geo(c, nq)).total);
 }
 
-// Decoder positions per chunk of the cross-attention: the fewest chunks whose plan fits, evened out; 0 if not even one
-// position fits.
+// Decoder positions per chunk of its cross-attention (even_chunk).
 inline int decoder_chunk(const tg_net_config& c) {
-  int n = c.n_steps;
-  while (n > 0 && dplan_sliced(c, n).total * sizeof(float) > static_cast<size_t>(kMaxDynamicLds)) --n;
-  if (n == 0) return 0;
-  const int chunks = (c.n_steps + n - 1) / n;
-  return (c.n_steps + chunks - 1) / chunks;
+  return even_chunk(c.n_steps, [&](int n) { return dplan_sliced(c, n).total; });
 }
 
-// ---- launch 1: the torso forward of one slice -------------------------------------------------------------------------
+// S = TG_NET_WIDE3_S, floats behind the per-game rows: the self-attention block's scratch; ln2(ee) (J x c), which the
+// caller holds with its gradient, and the cross-attention block's
+__host__ __device__ inline int self_scr25(const tg_net_config& c, int nq) { return scr_plan(self_geo25(c, nq)).total; }
+__host__ __device__ inline int cross_scr25(const tg_net_config& c, int nq) {
+  return 3 * c.S * c.S * c.c + scr_plan_kv<true>(cross_geo(c, nq)).total;
+}
+
+// its decoder kernel: the same per-game rows, and the larger of the two blocks' needs (they run one after the other)
+__host__ __device__ inline DPlan dplan25(const tg_net_config& c, int nqs, int nqx) {
+  DPlan p = dplan_with(c, false, 0);
+  const int s1 = self_scr25(c, nqs), s2 = cross_scr25(c, nqx);
+  p.total = p.SCR + (s1 > s2 ? s1 : s2);
+  return p;
+}
+
+struct Chunks25 {
+  int nqs, nqx;  // query positions per chunk of the self- and of the cross-attention; 0: not even one fits
+};
+
+// The one plan function of S = TG_NET_WIDE3_S's decoder: even_chunk per block.
+inline Chunks25 decoder_chunks25(const tg_net_config& c) {
+  const int rows = dplan_with(c, false, 0).SCR;
+  return Chunks25{even_chunk(c.n_steps, [&](int n) { return rows + self_scr25(c, n); }),
+                  even_chunk(c.n_steps, [&](int n) { return rows + cross_scr25(c, n); })};
+}
+
+inline int torso_partials(const tg_net_config& c, int64_t B) {
+  const int64_t units = B * c.S;
+  return static_cast<int>(units < TG_NET_TRAIN_PARTIALS ? units : TG_NET_TRAIN_PARTIALS);
+}
+
+// ---- launch 1: the torso forward of one slice, B * S workgroups -------------------------------------------------------
 __global__ void __launch_bounds__(NT) train_torso_fwd_slice_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const tg_net_config& c = a.c;
@@ -81,13 +141,10 @@ __global__ void __launch_bounds__(NT) train_torso_fwd_slice_kernel(Args a) {
 }
 
 // ---- launch 2: the decoder, the losses, the decoder's backward --------------------------------------------------------
-// ee and dL/dee of the game in the workspace, the saved block inputs in this workgroup's part of xs, the cross-attention
-// block over chunks of nq decoder positions: every step of it is row-wise in the positions given ee, the chunks add their
-// weight gradients to the slab and their dL/dee to the game's rows one after another, in position order.
-struct SlicedGame {
+// What both sizes' game strategies keep in the workspace: ee and dL/dee of the game, the saved block inputs in this
+// workgroup's part of xs.
+struct WorkspaceGame {
   float* xs_all;
-  int nq;
-  __device__ DPlan plan(const tg_net_config& c) const { return dplan_sliced(c, nq); }
   __device__ float* xs(const Args& a, float*, const DPlan&) const {
     return xs_all + static_cast<int64_t>(blockIdx.x) * a.c.blocks * 2 * a.c.n_steps * a.c.W;
   }
@@ -97,6 +154,18 @@ struct SlicedGame {
     DEE = a.dee + g * JC;
     for (int it = threadIdx.x; it < JC; it += NT) DEE[it] = 0.f;
   }
+  __device__ void game_done(const Args&, int64_t, const float*) const {}
+};
+
+// The chunk loops below are written out, each with its own row count: behind a helper that hands a callback the chunk's
+// first row and row count, or one that returns the chunk's Geo, the decoder kernels come out with other instructions.
+//
+// S = TG_NET_WIDE2_S: the cross-attention block over chunks of nq decoder positions.  Every step of it is row-wise in the
+// positions given ee, the chunks add their weight gradients to the slab and their dL/dee to the game's rows one after
+// another, in position order.
+struct SlicedGame : WorkspaceGame {
+  int nq;
+  __device__ DPlan plan(const tg_net_config& c) const { return dplan_sliced(c, nq); }
   __device__ void cross_fwd(const Geo& g2, const Mha& w, const float* X, const float* EE, float* OUT, float* sc) const {
     for (int r0 = 0; r0 < g2.Lx; r0 += nq) {
       Geo q = g2;
@@ -112,11 +181,69 @@ struct SlicedGame {
       mha_bwd<true, true>(q, w, gw, X + r0 * g2.c1, EE, dOut + r0 * g2.c1, dX + r0 * g2.c1, DEE, sc);
     }
   }
-  __device__ void game_done(const Args&, int64_t, const float*) const {}
 };
 
 __global__ void __launch_bounds__(NT) train_decode_sliced_kernel(Args a, float* xs, int nq) {
-  decode(a, SlicedGame{xs, nq});
+  decode(a, SlicedGame{{xs}, nq});
+}
+
+// S = TG_NET_WIDE3_S: both attention blocks by chunks of query positions, which add their weight gradients to the slab
+// one after another, in position order.
+struct Game25 : WorkspaceGame {
+  float* dyn_all;
+  int nqs, nqx;
+  __device__ DPlan plan(const tg_net_config& c) const { return dplan25(c, nqs, nqx); }
+  // rows r0 .. r0 + n - 1 attend to the keys 0 .. r0 + n - 1; X is both the queries' rows and the keys'
+  __device__ void self_fwd(const Geo& g1, const Mha& w, const float* X, float* OUT, float* sc) const {
+    for (int r0 = 0; r0 < g1.Lx; r0 += nqs) {
+      Geo q = g1;
+      q.Lx = g1.Lx - r0 < nqs ? g1.Lx - r0 : nqs;
+      q.Ly = r0 + q.Lx;
+      mha_fwd(q, w, X + r0 * g1.c1, X, OUT + r0 * g1.c1, sc);
+    }
+  }
+  __device__ void self_bwd(const Geo& g1, const Mha& w, const GMha& gw, const float* X, const float* dOut, float* dX,
+                           float* sc) const {
+    for (int r0 = 0; r0 < g1.Lx; r0 += nqs) {
+      Geo q = g1;
+      q.Lx = g1.Lx - r0 < nqs ? g1.Lx - r0 : nqs;
+      q.Ly = r0 + q.Lx;
+      mha_bwd(q, w, gw, X + r0 * g1.c1, X, dOut + r0 * g1.c1, dX + r0 * g1.c1, dX, sc);
+    }
+  }
+  // sc: ln2(ee) (J x c2), then the chunks' scratch
+  __device__ void cross_fwd(const Geo& g2, const Mha& w, const float* X, const float* EE, float* OUT, float* sc) const {
+    float* YN = sc;
+    sc += g2.Ly * g2.c2;
+    net::layernorm(EE, g2.c2, g2.Ly, g2.c2, w.ln2w, w.ln2b, YN, g2.c2);
+    __syncthreads();
+    for (int r0 = 0; r0 < g2.Lx; r0 += nqx) {
+      Geo q = g2;
+      q.Lx = g2.Lx - r0 < nqx ? g2.Lx - r0 : nqx;
+      mha_fwd<true, true, true>(q, w, X + r0 * g2.c1, YN, OUT + r0 * g2.c1, sc);
+    }
+  }
+  __device__ void cross_bwd(const Geo& g2, const Mha& w, const GMha& gw, const float* X, const float* EE,
+                            const float* dOut, float* dX, float* DEE, float* sc) const {
+    const int JC = g2.Ly * g2.c2;
+    float *YN = sc, *DYN = dyn_all + static_cast<int64_t>(blockIdx.x) * JC;
+    sc += JC;
+    net::layernorm(EE, g2.c2, g2.Ly, g2.c2, w.ln2w, w.ln2b, YN, g2.c2);
+    for (int it = threadIdx.x; it < JC; it += NT) DYN[it] = 0.f;
+    __syncthreads();
+    for (int r0 = 0; r0 < g2.Lx; r0 += nqx) {
+      Geo q = g2;
+      q.Lx = g2.Lx - r0 < nqx ? g2.Lx - r0 : nqx;
+      mha_bwd<true, true, true>(q, w, gw, X + r0 * g2.c1, YN, dOut + r0 * g2.c1, dX + r0 * g2.c1, DYN, sc);
+    }
+    ln_bwd_tiles(EE, g2.Ly, g2.c2, w.ln2w, DYN, DEE, gw.ln2w, gw.ln2b, sc, kLnTile);
+  }
+};
+
+static_assert(has_self_hooks<Game25>::value, "decode must run Game25's self-attention chunks: the plan has no other room");
+
+__global__ void __launch_bounds__(NT) train_decode_s25_kernel(Args a, float* xs, float* dyn, int nqs, int nqx) {
+  decode(a, Game25{{xs}, dyn, nqs, nqx});
 }
 
 // ---- launch 3: the torso backward -------------------------------------------------------------------------------------
@@ -187,6 +314,8 @@ __global__ void __launch_bounds__(NT) train_torso_bwd_slice_kernel(Args a, int P
 
 namespace {
 
+using namespace tg::train;
+
 int check_sliced_cfg(const char* fn, const tg_net_config* c) {
   if (int rc = tg_net_check(c)) return rc;
   if (c->S != TG_NET_WIDE2_S)
@@ -195,13 +324,57 @@ int check_sliced_cfg(const char* fn, const tg_net_config* c) {
                             "(tensor_game_train.h)",
                             fn, c->S, TG_NET_WIDE2_S);
   // the decoder fits when one position at a time does
-  const size_t lt = tg::train::tplan_slice(*c).total * sizeof(float),
-               ld = tg::train::dplan_sliced(*c, 1).total * sizeof(float);
+  const size_t lt = tplan_slice(*c).total * sizeof(float), ld = dplan_sliced(*c, 1).total * sizeof(float);
   if (lt > tg::kMaxDynamicLds || ld > tg::kMaxDynamicLds)
     return tg_internal_fail(
         TG_ERR_UNSUPPORTED,
         "%s: the sliced training LDS plan needs %zu (torso) / %zu (decoder) bytes > 160 KiB per workgroup", fn, lt, ld);
   return TG_OK;
+}
+
+int check_s25_cfg(const char* fn, const tg_net_config* c) {
+  if (c && c->S != TG_NET_WIDE3_S) {
+    if (int rc = tg_net_check(c)) return rc;
+    return tg_internal_fail(TG_ERR_UNSUPPORTED,
+                            "%s: dim_3d=%d is not TG_NET_WIDE3_S=%d; the other sizes train through tg_net_loss_grad "
+                            "(tensor_game_train.h) and tg_net_loss_grad_sliced (tensor_game_train_sliced.h)",
+                            fn, c->S, TG_NET_WIDE3_S);
+  }
+  if (int rc = tg_net_s25_check(c)) return rc;
+  // the decoder fits when one position at a time does in either block
+  const int rows = dplan_with(*c, false, 0).SCR;
+  const size_t lt = tplan_slice(*c).total * sizeof(float), ls = (rows + self_scr25(*c, 1)) * sizeof(float),
+               lx = (rows + cross_scr25(*c, 1)) * sizeof(float);
+  if (lt > tg::kMaxDynamicLds || ls > tg::kMaxDynamicLds || lx > tg::kMaxDynamicLds)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED,
+                            "%s: the S = 25 training LDS plan needs %zu (torso) / %zu (decoder, self-attention) / %zu "
+                            "(decoder, cross-attention) bytes > 160 KiB per workgroup",
+                            fn, lt, ls, lx);
+  return TG_OK;
+}
+
+// the workspace: tg_train.hip's parts, the saved block inputs of each decoder workgroup and one slab per torso workgroup;
+// at S = TG_NET_WIDE3_S also the accumulator of each decoder workgroup
+Ws ws_sliced(const tg_net_config& c, int64_t B) { return ws_plan(c, B, torso_partials(c, B), true, false); }
+Ws ws_s25(const tg_net_config& c, int64_t B) { return ws_plan(c, B, torso_partials(c, B), true, true); }
+
+// The four launches of one call.  DEC: the size's decoder kernel, ld: its LDS bytes, more: its arguments after a.
+template <auto DEC, class... More>
+int launch_sliced(const char* fn, Args a, size_t ld, hipStream_t st, More... more) {
+  const unsigned NT = tg::net::NT;
+  const int Pd = partials(a.B), Pt = torso_partials(a.c, a.B);
+  const size_t lt = tplan_slice(a.c).total * sizeof(float);
+  const int gb = a.grad ? static_cast<int>((a.off.total + NT - 1) / NT) : 0;
+  if (int rc = lds_opt_in<train_torso_fwd_slice_kernel>(fn, lt)) return rc;
+  if (int rc = lds_opt_in<DEC>(fn, ld)) return rc;
+  if (int rc = lds_opt_in<train_torso_bwd_slice_kernel>(fn, lt)) return rc;
+  a.P = Pd;  // launch 2's game runs
+  if (int rc = launch(fn, train_torso_fwd_slice_kernel, static_cast<unsigned>(a.B * a.c.S), NT, lt, st, a)) return rc;
+  if (int rc = launch(fn, DEC, static_cast<unsigned>(Pd), NT, ld, st, a, more...)) return rc;
+  a.P = Pt;  // launch 3's unit runs and the slabs launch 4 sums
+  if (a.grad)
+    if (int rc = launch(fn, train_torso_bwd_slice_kernel, static_cast<unsigned>(Pt), NT, lt, st, a, Pd)) return rc;
+  return launch(fn, train_reduce_kernel, static_cast<unsigned>(gb + 1), NT, 0, st, a, gb);
 }
 
 }  // namespace
@@ -212,11 +385,7 @@ int tg_net_train_sliced_check(const tg_net_config* cfg) { return check_sliced_cf
 
 int tg_net_train_sliced_workspace_size(const tg_net_config* cfg, int64_t B, int64_t* bytes) {
   const char* fn = "tg_net_train_sliced_workspace_size";
-  if (int rc = check_sliced_cfg(fn, cfg)) return rc;
-  if (B < 1 || B > (1LL << 24)) return tg_internal_fail(TG_ERR_INVALID, "%s: B=%lld outside [1, 2^24]", fn, (long long)B);
-  if (!bytes) return tg_internal_fail(TG_ERR_INVALID, "%s: null output", fn);
-  *bytes = tg::train::ws_plan_sliced(*cfg, B).total;
-  return TG_OK;
+  return workspace_size(fn, check_sliced_cfg(fn, cfg), cfg, B, bytes, ws_sliced);
 }
 
 int tg_net_loss_grad_sliced(const tg_net_config* cfg, const float* theta, const float* pos_fix, const void* frames,
@@ -224,41 +393,40 @@ int tg_net_loss_grad_sliced(const tg_net_config* cfg, const float* theta, const 
                             int64_t B, float weight_pol, float weight_val, float dropout_p, uint64_t seed, uint64_t call,
                             const uint8_t* keep_in, uint8_t* keep_out, void* workspace, int64_t workspace_bytes,
                             float* grad, float* losses, uint32_t* status, tg_stream_t stream) {
-  using namespace tg::train;
   const char* fn = "tg_net_loss_grad_sliced";
   if (int rc = check_sliced_cfg(fn, cfg)) return rc;
-  if (int rc = check_call(fn, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B, weight_pol, weight_val,
-                          dropout_p, workspace, grad, losses, status))
+  Call k;
+  if (int rc = prepare_call(fn, *cfg, ws_sliced, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B,
+                            weight_pol, weight_val, dropout_p, seed, call, keep_in, keep_out, workspace, workspace_bytes,
+                            grad, losses, status, k))
     return rc;
-  const WsSliced ws = ws_plan_sliced(*cfg, B);
-  if (workspace_bytes < ws.total)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed", fn, (long long)workspace_bytes,
-                            (long long)ws.total);
-  Args a = call_args(*cfg, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B, weight_pol, weight_val,
-                     dropout_p, seed, call, keep_in, keep_out, grad, losses, status);
-  char* base = static_cast<char*>(workspace);
-  a.ee = reinterpret_cast<float*>(base + ws.ee);
-  a.dee = reinterpret_cast<float*>(base + ws.dee);
-  a.act = reinterpret_cast<float*>(base + ws.act);
-  a.gl = reinterpret_cast<float*>(base + ws.gl);
-  a.flags = reinterpret_cast<int*>(base + ws.flags);
-  a.slabs = reinterpret_cast<float*>(base + ws.slabs);
-  float* xs = reinterpret_cast<float*>(base + ws.xs);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned NT = tg::net::NT;
-  const int Pd = partials(B), Pt = torso_partials(*cfg, B), nq = decoder_chunk(*cfg);
-  const size_t lt = tplan_slice(*cfg).total * sizeof(float), ld = dplan_sliced(*cfg, nq).total * sizeof(float);
-  const int gb = grad ? static_cast<int>((a.off.total + NT - 1) / NT) : 0;
-  if (int rc = lds_opt_in<train_torso_fwd_slice_kernel>(fn, lt)) return rc;
-  if (int rc = lds_opt_in<train_decode_sliced_kernel>(fn, ld)) return rc;
-  if (int rc = lds_opt_in<train_torso_bwd_slice_kernel>(fn, lt)) return rc;
-  a.P = Pd;  // launch 2's game runs
-  if (int rc = launch(fn, train_torso_fwd_slice_kernel, static_cast<unsigned>(B * cfg->S), NT, lt, st, a)) return rc;
-  if (int rc = launch(fn, train_decode_sliced_kernel, static_cast<unsigned>(Pd), NT, ld, st, a, xs, nq)) return rc;
-  a.P = Pt;  // launch 3's unit runs and the slabs launch 4 sums
-  if (grad)
-    if (int rc = launch(fn, train_torso_bwd_slice_kernel, static_cast<unsigned>(Pt), NT, lt, st, a, Pd)) return rc;
-  return launch(fn, train_reduce_kernel, static_cast<unsigned>(gb + 1), NT, 0, st, a, gb);
+  const int nq = decoder_chunk(*cfg);
+  return launch_sliced<train_decode_sliced_kernel>(fn, k.a, dplan_sliced(*cfg, nq).total * sizeof(float),
+                                                   static_cast<hipStream_t>(stream), k.xs, nq);
+}
+
+int tg_net_train_s25_check(const tg_net_config* cfg) { return check_s25_cfg("tg_net_train_s25_check", cfg); }
+
+int tg_net_train_s25_workspace_size(const tg_net_config* cfg, int64_t B, int64_t* bytes) {
+  const char* fn = "tg_net_train_s25_workspace_size";
+  return workspace_size(fn, check_s25_cfg(fn, cfg), cfg, B, bytes, ws_s25);
+}
+
+int tg_net_loss_grad_s25(const tg_net_config* cfg, const float* theta, const float* pos_fix, const void* frames,
+                         int frames_is_i8, const float* scalars, const int8_t* g_action, const float* g_value, int64_t B,
+                         float weight_pol, float weight_val, float dropout_p, uint64_t seed, uint64_t call,
+                         const uint8_t* keep_in, uint8_t* keep_out, void* workspace, int64_t workspace_bytes, float* grad,
+                         float* losses, uint32_t* status, tg_stream_t stream) {
+  const char* fn = "tg_net_loss_grad_s25";
+  if (int rc = check_s25_cfg(fn, cfg)) return rc;
+  Call k;
+  if (int rc = prepare_call(fn, *cfg, ws_s25, theta, pos_fix, frames, frames_is_i8, scalars, g_action, g_value, B,
+                            weight_pol, weight_val, dropout_p, seed, call, keep_in, keep_out, workspace, workspace_bytes,
+                            grad, losses, status, k))
+    return rc;
+  const Chunks25 ch = decoder_chunks25(*cfg);
+  return launch_sliced<train_decode_s25_kernel>(fn, k.a, dplan25(*cfg, ch.nqs, ch.nqx).total * sizeof(float),
+                                                static_cast<hipStream_t>(stream), k.xs, k.dyn, ch.nqs, ch.nqx);
 }
 
 }  // extern "C"

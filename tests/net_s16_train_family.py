@@ -1,5 +1,5 @@
 """Training at the 4x4 matmul tensor (S = 16, include/tensor_game_train_sliced.h): the LDS plans of tg_train_sliced.hip
-restated in floats, what the host code derives from them, the workspace formula, and the rows of the S = 16 training
+at that size restated in floats, what the host code derives from them, the workspace formula, and the rows of the S = 16 training
 tests.
 
 * ``slice_tplan``: the torso kernels' plan for one slice (3S grid rows, 3S input rows, three buffers of a pair's 2S

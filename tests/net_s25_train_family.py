@@ -1,5 +1,5 @@
-"""Training at the 5x5 matmul tensor (S = 25, include/tensor_game_train_s25.h): the LDS plans of tg_train_s25.hip
-restated in floats, what the host code derives from them, the workspace formula, and the rows of the S = 25 training
+"""Training at the 5x5 matmul tensor (S = 25, include/tensor_game_train_s25.h): the LDS plans of tg_train_sliced.hip
+at that size restated in floats, what the host code derives from them, the workspace formula, and the rows of the S = 25 training
 tests.
 
 * ``slice_tplan``: the torso kernels' plan for one slice (net_s16_train_family's: the kernels are the same);
