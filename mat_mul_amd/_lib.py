@@ -173,6 +173,13 @@ ROLLOUT_SLOTS_SIGNATURES = {
     "tg_rollout_advance_slots": [_p] * 13 + [_i64, _i, _i, _i, _i, _i, _i, _p],
     "tg_rollout_refill": [_p, _p, _i64, _p, _i64, _u64, _i] + [_p] * 21 + [_i64, _i, _i, _i, _i, _i, _p],
 }
+# name -> argtypes; every symbol include/tensor_game_symmetry.h declares
+SYMMETRY_SIGNATURES = {
+    "tg_symmetry_apply": [_p, _p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "tg_symmetry_sample": [_p, _i64, _i, _u64, _u64, _i, _p],
+}
+# flags of tg_symmetry_sample (include/tensor_game_symmetry.h)
+TG_SYM_MODES, TG_SYM_PERMS, TG_SYM_SIGNS = 1, 2, 4
 TG_ROLLOUT_MAX_SLOTS = 65536
 TG_NET_TRAIN_PARTIALS = 256
 TG_TRAIN_STATUS_BAD_TOKEN = 1
@@ -229,7 +236,8 @@ def _load() -> C.CDLL:
                            **REPLAY_IO_SIGNATURES,
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
                            **TRAIN_S25_SIGNATURES,
-                           **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES}.items():
+                           **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
+                           **SYMMETRY_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -98,11 +98,14 @@ class SyntheticDemos:
         return state, scalar, self.action_seq[:, idx_action], reward
 
     def items(self, idx: Optional[torch.Tensor] = None, *, demo_idx: Optional[torch.Tensor] = None,
-              action_idx: Optional[torch.Tensor] = None, dtype=torch.float32, dim_t: Optional[int] = None):
+              action_idx: Optional[torch.Tensor] = None, dtype=torch.float32, dim_t: Optional[int] = None,
+              augment=None):
         """The ``__getitem__`` tuples (datasets.py:78-122) of a batch of items, each with its own demo and action index,
         in one launch (``ops.demo_items``): ``idx`` holds flat reference indices (demo * max_actions + action index),
         or ``demo_idx`` and ``action_idx`` the two halves.  Returns (state (N,dim_t,S,S,S) of ``dtype``, scalar fp32
-        (N,1), action int8 (N,3S), reward fp32 (N,1)).  An index outside the set gives an all-zero item."""
+        (N,1), action int8 (N,3S), reward fp32 (N,1)).  An index outside the set gives an all-zero item.
+        ``augment`` (an ``Augment``): the items are gathered as int8 and the augmenter emits state and action in a
+        random symmetric copy (two more launches); scalar and reward pass through."""
         if idx is None:
             if demo_idx is None or action_idx is None:
                 raise TensorGameError("items", -1, "pass idx, or both demo_idx and action_idx")
@@ -111,6 +114,14 @@ class SyntheticDemos:
         elif demo_idx is not None or action_idx is not None:
             raise TensorGameError("items", -1, "pass idx or demo_idx / action_idx, not both")
         idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1)
+        if augment is not None:
+            if augment.shift != self.shift:
+                raise TensorGameError("items", -1, f"augment.shift={augment.shift} != the demos' shift={self.shift}")
+            state, scalar, action, reward = ops.demo_items(self.action_seq, self.target_tensor, idx,
+                                                           self.dim_t if dim_t is None else dim_t, dtype=torch.int8,
+                                                           shift=self.shift)
+            state, action = augment(state, action, dtype)
+            return state, scalar, action, reward
         return ops.demo_items(self.action_seq, self.target_tensor, idx, self.dim_t if dim_t is None else dim_t,
                               dtype=dtype, shift=self.shift)
 
@@ -125,11 +136,11 @@ class SyntheticDemos:
 
     def batches(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None,
                 indices: Optional[torch.Tensor] = None, drop_last: bool = False,
-                dtype=torch.float32) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:
+                dtype=torch.float32, augment=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:
         """One epoch of ``items`` batches: what ``DataLoader(random_split(dataset)[i], batch_size, shuffle=True)``
         yields (training.py:234-246), gathered on the GPU.  ``indices`` (flat item indices) selects the subset, as
         ``random_split`` does; the permutation is drawn on the device (``generator``: a generator of that device), and
-        each batch is one ``ops.demo_items`` call.  No host sync."""
+        each batch is one ``ops.demo_items`` call (``augment``: as in ``items``).  No host sync."""
         if batch_size < 1:
             raise TensorGameError("batches", -1, "batch_size must be >= 1")
         if indices is None:
@@ -140,4 +151,4 @@ class SyntheticDemos:
             indices = indices[torch.randperm(n, generator=generator, device=self.device)]
         stop = n - n % batch_size if drop_last else n
         for lo in range(0, stop, batch_size):
-            yield self.items(indices[lo:lo + batch_size], dtype=dtype)
+            yield self.items(indices[lo:lo + batch_size], dtype=dtype, augment=augment)

@@ -30,6 +30,7 @@ __all__ = [
     "net_train_s25_check", "net_train_s25_workspace_size", "net_loss_grad_s25",
     "rollout_check", "rollout_records", "rollout_advance",
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
+    "symmetry_sample", "symmetry_apply",
 ]
 
 
@@ -562,6 +563,62 @@ def demo_items(tokens, targets, idx, T: int, dtype=torch.float32, out=None, scal
     _launch(dev, "tg_demo_items", _ptr(tokens), _ptr(targets), B, R, S, stride, _ptr(idx), N, int(T), code,
             _ptr(out), _ptr(scalars), _ptr(actions), _ptr(rewards), _ptr(overflow), _ptr(status), int(shift))
     return out, scalars, actions, rewards
+
+
+def symmetry_sample(N: int, S: int, device, seed: int = 0, item_offset: int = 0, modes: bool = True, perms: bool = True,
+                    signs: bool = True, out=None) -> torch.Tensor:
+    """One element of the symmetry group per item (include/tensor_game_symmetry.h): uint8 (N,3S+1) rows, byte 0 the
+    mode permutation's code, byte 1 + m*S + a = pi_m[a] | 0x80 for a negative sign.  Keyed by the global item id
+    ``item_offset + n``, so any split of an id range gives the same rows.  A part switched off (``modes``, ``perms``,
+    ``signs``) is the identity; the other parts do not change with it."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise TensorGameError("symmetry_sample", -1, f"device must be a ROCm device (got {dev}); there is no CPU path")
+    N, S = int(N), int(S)
+    if N < 0 or not 1 <= S <= TG_MAX_S:
+        raise TensorGameError("symmetry_sample", -1, f"N={N} must be >= 0 and S={S} in [1,{TG_MAX_S}]")
+    if out is None:
+        out = torch.empty((N, 3 * S + 1), dtype=torch.uint8, device=dev)
+    else:
+        _need_gpu(out, "out")
+        _flag(out, (N, 3 * S + 1), torch.uint8, out.device, "out")
+    flags = (_lib.TG_SYM_MODES if modes else 0) | (_lib.TG_SYM_PERMS if perms else 0) | (_lib.TG_SYM_SIGNS if signs else 0)
+    _launch(out.device, "tg_symmetry_sample", _ptr(out), N, S, C.c_uint64(_u64(seed)), C.c_uint64(_u64(item_offset)), flags)
+    return out
+
+
+def symmetry_apply(state_i8, action_i8, sym, dtype=torch.float32, shift: int = 1, overflow=None, status=None, out=None,
+                   actions=None):
+    """``sym[n]`` applied to item n (include/tensor_game_symmetry.h): state_i8 int8 (N,T,S,S,S) and action_i8 int8
+    (N,3S) (or None) -> (state (N,T,S,S,S) of ``dtype`` (float32, float16, bfloat16 or int8), action int8 (N,3S) or
+    None; ``out`` / ``actions`` receive them when given).  Out of place, one launch, no host sync.  ``overflow`` uint8
+    (N,) is set where a negation left int8; ``status`` uint32 (1,) gets bit 0 for a bad row of ``sym`` (that item is
+    all zero)."""
+    fn = "symmetry_apply"
+    _need_gpu(state_i8, "state_i8")
+    if state_i8.dtype != torch.int8 or state_i8.dim() != 5 or not (state_i8.shape[2] == state_i8.shape[3] == state_i8.shape[4]):
+        raise TensorGameError(fn, -1, f"state_i8 must be int8 (N,T,S,S,S), got {state_i8.dtype} {tuple(state_i8.shape)}")
+    if not state_i8.is_contiguous():
+        raise TensorGameError(fn, -1, "state_i8 must be C-contiguous")
+    N, T, S = state_i8.shape[0], state_i8.shape[1], state_i8.shape[2]
+    dev = state_i8.device
+    if dtype not in _ITEM_DTYPES:
+        raise TensorGameError(fn, -1, "dtype must be float32, float16, bfloat16 or int8")
+    _need_gpu(sym, "sym")
+    sym = _flag(sym, (N, 3 * S + 1), torch.uint8, dev, "sym")
+    actions_out = None
+    if action_i8 is not None:
+        action_i8 = _tokens(action_i8, (N,), S, dev, "action_i8")
+        actions_out = _out(actions, (N, 3 * S), torch.int8, dev, "actions")
+    if out is None:
+        out = torch.empty((N, T, S, S, S), dtype=dtype, device=dev)
+    elif out.dtype != dtype or tuple(out.shape) != (N, T, S, S, S) or not out.is_contiguous() or out.device != dev:
+        raise TensorGameError(fn, -1, "out must be contiguous (N,T,S,S,S) of the requested dtype")
+    overflow = _flag(overflow, (N,), torch.uint8, dev, "overflow")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_symmetry_apply", _ptr(state_i8), _ptr(action_i8), _ptr(sym), N, T, S, int(shift), _ITEM_DTYPES[dtype],
+            _ptr(out), _ptr(actions_out), _ptr(overflow), _ptr(status))
+    return out, actions_out
 
 
 def state_hash(state) -> torch.Tensor:

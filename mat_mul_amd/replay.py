@@ -67,11 +67,19 @@ class GameBuffer:
         """Games ever added (a host sync)."""
         return int(self.ring[1])
 
-    def items(self, idx, dtype=torch.float32):
+    def items(self, idx, dtype=torch.float32, augment=None):
         """The ``__getitem__`` tuples of a batch of flat move indices in one launch (``ops.replay_items``): (state
         (N,T,S,S,S) of ``dtype``, scalar fp32 (N,1) = the move index, action int8 (N,3S), reward fp32 (N,1)).  An index
-        outside the stored moves gives an all-zero item and sets bit 0 of ``status``."""
+        outside the stored moves gives an all-zero item and sets bit 0 of ``status``.  ``augment`` (an ``Augment``):
+        the items are gathered as int8 and the augmenter emits state and action in a random symmetric copy (two more
+        launches); scalar and reward pass through."""
         idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1)
+        if augment is not None:
+            state, scalar, action, reward = ops.replay_items(idx, self.T, self.S, self.device, played=self,
+                                                             direct_kind=TG_REPLAY_PLAYED, dtype=torch.int8,
+                                                             status=self.status)
+            state, action = augment(state, action, dtype, status=self.status)
+            return state, scalar, action, reward
         return ops.replay_items(idx, self.T, self.S, self.device, played=self, direct_kind=TG_REPLAY_PLAYED,
                                 dtype=dtype, status=self.status)
 
@@ -352,11 +360,20 @@ class TensorGameData:
     def __len__(self) -> int:
         return self.len_data
 
-    def items(self, idx, dtype=torch.float32):
+    def items(self, idx, dtype=torch.float32, augment=None):
         """The ``__getitem__`` tuples of a batch of dataset indices in one launch (``ops.replay_items``): (state
         (N,dim_t,S,S,S) of ``dtype``, scalar fp32 (N,1), action int8 (N,3S), reward fp32 (N,1)).  A synthetic item's
-        scalar is R - k, a played or best item's its move index (as the reference's two datasets do)."""
+        scalar is R - k, a played or best item's its move index (as the reference's two datasets do).  ``augment`` (an
+        ``Augment``): as in ``GameBuffer.items``."""
         idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1)
+        if augment is not None:
+            if augment.shift != self.shift:
+                raise TensorGameError("items", -1, f"augment.shift={augment.shift} != the dataset's shift={self.shift}")
+            state, scalar, action, reward = ops.replay_items(
+                idx, self.dim_t, self.S, self.device, tokens=self.tokens, targets=self.targets, played=self.played,
+                best=self.best, kind=self.kind, src=self.src, dtype=torch.int8, status=self.status, shift=self.shift)
+            state, action = augment(state, action, dtype, status=self.status)
+            return state, scalar, action, reward
         return ops.replay_items(idx, self.dim_t, self.S, self.device, tokens=self.tokens, targets=self.targets,
                                 played=self.played, best=self.best, kind=self.kind, src=self.src, dtype=dtype,
                                 status=self.status, shift=self.shift)
@@ -371,10 +388,10 @@ class TensorGameData:
         return state[0], scalar[0], action[0], reward[0]
 
     def batches(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None,
-                drop_last: bool = False, dtype=torch.float32) -> Iterator[Tuple[torch.Tensor, ...]]:
+                drop_last: bool = False, dtype=torch.float32, augment=None) -> Iterator[Tuple[torch.Tensor, ...]]:
         """One epoch of ``DataLoader(dataset, batch_size, shuffle=True)`` (training.py:424): a permutation of
         [0, len_data) drawn on the device (``generator``: a generator of that device), each batch one
-        ``tg_replay_items`` launch.  No host sync."""
+        ``tg_replay_items`` launch (``augment``: as in ``items``).  No host sync."""
         if batch_size < 1:
             raise TensorGameError("batches", -1, "batch_size must be >= 1")
         if shuffle:
@@ -383,4 +400,4 @@ class TensorGameData:
             order = torch.arange(self.len_data, device=self.device)
         stop = self.len_data - self.len_data % batch_size if drop_last else self.len_data
         for lo in range(0, stop, batch_size):
-            yield self.items(order[lo:lo + batch_size], dtype=dtype)
+            yield self.items(order[lo:lo + batch_size], dtype=dtype, augment=augment)
