@@ -16,9 +16,10 @@ __version__ = "0.1.0"
 __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameError", "functional", "ops", "demo_io",
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
            "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
-           "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment"]
+           "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
+           "SolutionArchive", "solutions"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -41,6 +42,7 @@ _ATTRS = {
     "save_run": "replay_io",
     "load_run": "replay_io",
     "Augment": "augment",
+    "SolutionArchive": "solutions",
 }
 
 

@@ -178,6 +178,13 @@ SYMMETRY_SIGNATURES = {
     "tg_symmetry_apply": [_p, _p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "tg_symmetry_sample": [_p, _i64, _i, _u64, _u64, _i, _p],
 }
+# name -> argtypes; every symbol include/tensor_game_solutions.h declares
+SOLUTION_SIGNATURES = {
+    "tg_solution_check": [_i64, _i, _i, _i],
+    "tg_solution_canon": [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+}
+# limits and status bits of include/tensor_game_solutions.h
+TG_SOL_MAX_K, TG_SOL_MAX_SHIFT, TG_SOL_BAD_LENGTH, TG_SOL_BAD_NEGATION = 256, 64, 1, 2
 # flags of tg_symmetry_sample (include/tensor_game_symmetry.h)
 TG_SYM_MODES, TG_SYM_PERMS, TG_SYM_SIGNS = 1, 2, 4
 TG_ROLLOUT_MAX_SLOTS = 65536
@@ -237,7 +244,7 @@ def _load() -> C.CDLL:
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
-                           **SYMMETRY_SIGNATURES}.items():
+                           **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -31,6 +31,7 @@ __all__ = [
     "rollout_check", "rollout_records", "rollout_advance",
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
     "symmetry_sample", "symmetry_apply",
+    "solution_check", "solution_canon",
 ]
 
 
@@ -619,6 +620,50 @@ def symmetry_apply(state_i8, action_i8, sym, dtype=torch.float32, shift: int = 1
     _launch(dev, "tg_symmetry_apply", _ptr(state_i8), _ptr(action_i8), _ptr(sym), N, T, S, int(shift), _ITEM_DTYPES[dtype],
             _ptr(out), _ptr(actions_out), _ptr(overflow), _ptr(status))
     return out, actions_out
+
+
+def solution_check(M: int, K: int, S: int, shift: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_solution_canon takes these sizes.  Host only."""
+    call("tg_solution_check", int(M), int(K), int(S), int(shift))
+
+
+def solution_canon(targets, tokens, lengths, shift: int = 1, canon=None, rank=None, key=None, residual_nnz=None,
+                   status=None):
+    """Verify and canonicalise M action lists in one launch (include/tensor_game_solutions.h).  tokens int8 (M,K,3S)
+    and lengths int64 (M,) as ``RolloutResult.solutions()`` returns them; targets int8 (M,S,S,S) (the start heads) or
+    None.  Returns (canon int8 (M,K,3S): the kept terms in canonical order, zero rows behind them; rank int32 (M,);
+    key int64 (M,) holding the 64 bits; residual_nnz int32 (M,): the non-zero entries of target - sum of the ORIGINAL
+    terms in exact arithmetic, 0 = proven; None when ``targets`` is None).  A row with a length outside [0,K] or a
+    negation that leaves int8 is all zero, with rank 0, key 0 and residual_nnz -1, and sets bit 0 / bit 1 of ``status``
+    uint32 (1,).  No host sync."""
+    fn = "solution_canon"
+    _need_gpu(tokens, "tokens")
+    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+    dev = tokens.device
+    solution_check(M, K, S, shift)
+    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+    if targets is not None:
+        _need_gpu(targets, "targets")
+        if targets.dtype != torch.int8 or tuple(targets.shape) != (M, S, S, S) or targets.device != dev:
+            raise TensorGameError(fn, -1, f"targets must be int8 {(M, S, S, S)} on {dev}, got {targets.dtype} "
+                                          f"{tuple(targets.shape)} on {targets.device}")
+        targets = targets if targets.is_contiguous() else targets.contiguous()
+    elif residual_nnz is not None:
+        raise TensorGameError(fn, -1, "residual_nnz needs targets")
+    _need_gpu(lengths, "lengths")
+    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
+        raise TensorGameError(fn, -1, "lengths must be given")
+    canon = _out(canon, (M, K, 3 * S), torch.int8, dev, "canon")
+    rank = _out(rank, (M,), torch.int32, dev, "rank")
+    key = _out(key, (M,), torch.int64, dev, "key")
+    if targets is not None:
+        residual_nnz = _out(residual_nnz, (M,), torch.int32, dev, "residual_nnz")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_solution_canon", _ptr(targets), _ptr(tokens), _ptr(lengths), M, K, S, int(shift), _ptr(canon),
+            _ptr(rank), _ptr(key), _ptr(residual_nnz), _ptr(status))
+    return canon, rank, key, residual_nnz
 
 
 def state_hash(state) -> torch.Tensor:
