@@ -185,6 +185,16 @@ SOLUTION_SIGNATURES = {
 }
 # limits and status bits of include/tensor_game_solutions.h
 TG_SOL_MAX_K, TG_SOL_MAX_SHIFT, TG_SOL_BAD_LENGTH, TG_SOL_BAD_NEGATION = 256, 64, 1, 2
+# name -> argtypes; every symbol include/tensor_game_bases.h declares
+BASES_SIGNATURES = {
+    "tg_basis_inverse_check": [_i64, _i],
+    "tg_solution_rebase_check": [_i64, _i, _i, _i64, _i],
+    "tg_basis_inverse_i32": [_p, _p, _i64, _i, _p, _p, _p, _p],
+    "tg_solution_rebase": [_p, _p, _p, _p, _i64, _i, _i, _i64, _i, _p, _p, _p, _p, _p],
+}
+# status bits of include/tensor_game_bases.h (the limits are TG_MAX_S, TG_SOL_MAX_K and TG_SOL_MAX_SHIFT)
+TG_BASIS_BAD_DIAGONAL, TG_BASIS_BAD_RANGE = 1, 2
+TG_REBASE_BAD_LENGTH, TG_REBASE_BAD_INDEX, TG_REBASE_BAD_RANGE = 1, 2, 4
 # flags of tg_symmetry_sample (include/tensor_game_symmetry.h)
 TG_SYM_MODES, TG_SYM_PERMS, TG_SYM_SIGNS = 1, 2, 4
 TG_ROLLOUT_MAX_SLOTS = 65536
@@ -244,7 +254,7 @@ def _load() -> C.CDLL:
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
-                           **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES}.items():
+                           **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

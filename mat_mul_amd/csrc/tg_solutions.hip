@@ -21,6 +21,7 @@
 
 #include "../../include/tensor_game_solutions.h"
 #include "tg_host.h"
+#include "tg_sol_copy.h"
 
 namespace tg {
 
@@ -39,29 +40,6 @@ struct SolArgs {
 };
 
 constexpr int kSolWRow = TG_MAX_S;  // bytes per term of the verifier's padded copy of the w tokens
-
-// n bytes from global memory (any alignment) into LDS (16-byte aligned)
-template <int NT>
-__device__ __forceinline__ void sol_copy_in(const int8_t* src, int8_t* dst, int n, int t) {
-  int nb = 0;
-  if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-    nb = n / 16;
-    for (int c = t; c < nb; c += NT) reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(src)[c];
-  }
-  for (int e = 16 * nb + t; e < n; e += NT) dst[e] = src[e];
-}
-
-// n bytes to global memory (any alignment) from LDS (16-byte aligned), or zeros when src is null
-template <int NT>
-__device__ __forceinline__ void sol_copy_out(int8_t* dst, const int8_t* src, int n, int t) {
-  int nb = 0;
-  if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-    nb = n / 16;
-    for (int c = t; c < nb; c += NT)
-      reinterpret_cast<uint4*>(dst)[c] = src ? reinterpret_cast<const uint4*>(src)[c] : uint4{0, 0, 0, 0};
-  }
-  for (int e = 16 * nb + t; e < n; e += NT) dst[e] = src ? src[e] : static_cast<int8_t>(0);
-}
 
 // the workgroup's sum of x (uniform result); `red` holds NT words
 template <int NT>

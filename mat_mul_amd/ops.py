@@ -32,6 +32,7 @@ __all__ = [
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
     "symmetry_sample", "symmetry_apply",
     "solution_check", "solution_canon",
+    "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
 ]
 
 
@@ -664,6 +665,94 @@ def solution_canon(targets, tokens, lengths, shift: int = 1, canon=None, rank=No
     _launch(dev, "tg_solution_canon", _ptr(targets), _ptr(tokens), _ptr(lengths), M, K, S, int(shift), _ptr(canon),
             _ptr(rank), _ptr(key), _ptr(residual_nnz), _ptr(status))
     return canon, rank, key, residual_nnz
+
+
+def basis_inverse_check(N: int, S: int) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_basis_inverse_i32 takes these sizes.  Host only."""
+    call("tg_basis_inverse_check", int(N), int(S))
+
+
+def solution_rebase_check(M: int, K: int, S: int, G: int, shift: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_solution_rebase takes these sizes.  Host only."""
+    call("tg_solution_rebase_check", int(M), int(K), int(S), int(G), int(shift))
+
+
+def _optional_bad(bad, shape, dev):
+    """The ``bad`` output of the two entries below: allocated when None, not written at all (NULL) when False."""
+    return None if bad is False else _out(bad, shape, torch.uint8, dev, "bad")
+
+
+def basis_inverse(lower, upper, inv=None, bad=None, status=None):
+    """The exact integer inverses of N sampled bases in one launch (include/tensor_game_bases.h).  lower, upper int8
+    (N,3,S,S): the L and U of ``sample_basis(want_factors=True)``, P = L @ U.  Returns (inv int32 (N,3,S,S) =
+    U^-1 @ L^-1, bad uint8 (N,)).  A triple with a diagonal entry other than +-1 (bit 0 of ``status`` uint32 (1,)) or
+    whose inverse leaves the accepted range (bit 1) is all zero and has bad = 1.  ``bad=False`` passes no flag buffer
+    (None is returned in its place).  No host sync."""
+    fn = "basis_inverse"
+    for t, name in ((lower, "lower"), (upper, "upper")):
+        if t.dtype != torch.int8 or t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != t.shape[3]:
+            raise TensorGameError(fn, -1, f"{name} must be int8 (N,3,S,S), got {t.dtype} {tuple(t.shape)}")
+    if upper.shape != lower.shape:
+        raise TensorGameError(fn, -1, f"upper must have the shape of lower {tuple(lower.shape)}, got {tuple(upper.shape)}")
+    _need_gpu(lower, "lower")
+    _need_gpu(upper, "upper")
+    N, S, dev = lower.shape[0], lower.shape[2], lower.device
+    if upper.device != dev:
+        raise TensorGameError(fn, -1, f"upper is on {upper.device}, lower on {dev}")
+    basis_inverse_check(N, S)
+    lower = lower if lower.is_contiguous() else lower.contiguous()
+    upper = upper if upper.is_contiguous() else upper.contiguous()
+    inv = _out(inv, (N, 3, S, S), torch.int32, dev, "inv")
+    bad = _optional_bad(bad, (N,), dev)
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_basis_inverse_i32", _ptr(lower), _ptr(upper), N, S, _ptr(inv), _ptr(bad), _ptr(status))
+    return inv, bad
+
+
+def solution_rebase(tokens, lengths, mats, index=None, shift: int = 1, tokens_out=None, lengths_out=None, bad=None,
+                    status=None):
+    """Apply a matrix triple to the factors of every term of M action lists in one launch
+    (include/tensor_game_bases.h): (u,v,w) -> (A u, B v, C w) with (A,B,C) = mats[index[m]].  tokens int8 (M,K,3S) and
+    lengths int64 (M,) as ``solutions()`` returns them; mats int32 (G,3,S,S); index int64 (M,), or None: row m uses
+    triple m (G == M).  Returns (tokens_out int8 (M,K,3S), zero rows behind each list; lengths_out int64 (M,); bad uint8
+    (M,)).  A row with a length outside [0,K] (bit 0 of ``status`` uint32 (1,)), an index outside [0,G) (bit 1) or a
+    mapped token outside int8 (bit 2) is all zero, with length 0 and bad = 1.  With ``BasisSet.inverse`` as ``mats``
+    this carries lists found in a changed basis back; with ``BasisSet.forward`` it moves known lists into it.
+    ``bad=False`` passes no flag buffer.  Out of place; no host sync."""
+    fn = "solution_rebase"
+    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+    if mats.dtype != torch.int32 or mats.dim() != 4 or tuple(mats.shape[1:]) != (3, S, S):
+        raise TensorGameError(fn, -1, f"mats must be int32 (G,3,{S},{S}), got {mats.dtype} {tuple(mats.shape)}")
+    G = mats.shape[0]
+    if lengths.dtype != torch.int64 or tuple(lengths.shape) != (M,):
+        raise TensorGameError(fn, -1, f"lengths must be int64 {(M,)}, got {lengths.dtype} {tuple(lengths.shape)}")
+    if index is None:
+        if G != M:
+            raise TensorGameError(fn, -1, f"index must be given unless mats has one triple per row: G={G}, M={M}")
+    elif index.dtype != torch.int64 or tuple(index.shape) != (M,):
+        raise TensorGameError(fn, -1, f"index must be int64 {(M,)}, got {index.dtype} {tuple(index.shape)}")
+    _need_gpu(tokens, "tokens")
+    dev = tokens.device
+    for t, name in ((lengths, "lengths"), (mats, "mats"), (index, "index")):
+        if t is not None and t.device != dev:
+            raise TensorGameError(fn, -1, f"{name} is on {t.device}, tokens on {dev}")
+    solution_rebase_check(M, K, S, G, shift)
+    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+    mats = mats if mats.is_contiguous() else mats.contiguous()
+    lengths = lengths if lengths.is_contiguous() else lengths.contiguous()
+    if index is not None and not index.is_contiguous():
+        index = index.contiguous()
+    tokens_out = _out(tokens_out, (M, K, 3 * S), torch.int8, dev, "tokens_out")
+    if M and tokens_out.data_ptr() == tokens.data_ptr():
+        raise TensorGameError(fn, -1, "tokens_out must not be tokens: in-place operation is not supported")
+    lengths_out = _out(lengths_out, (M,), torch.int64, dev, "lengths_out")
+    bad = _optional_bad(bad, (M,), dev)
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_solution_rebase", _ptr(tokens), _ptr(lengths), _ptr(mats), _ptr(index), M, K, S, G, int(shift),
+            _ptr(tokens_out), _ptr(lengths_out), _ptr(bad), _ptr(status))
+    return tokens_out, lengths_out, bad
 
 
 def state_hash(state) -> torch.Tensor:
