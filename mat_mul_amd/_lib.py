@@ -109,6 +109,14 @@ REPLAY_IO_SIGNATURES = {
 # status bits of include/tensor_game_replay_io.h
 TG_REPLAY_IO_BAD_LENGTH, TG_REPLAY_IO_TRUNCATED = 1, 2
 
+# name -> argtypes; every symbol include/tensor_game_replay_lists.h declares
+REPLAY_LISTS_SIGNATURES = {
+    "tg_replay_add_lists": [_p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _p, _p],
+}
+# status bits and the shift limit of include/tensor_game_replay_lists.h
+TG_REPLAY_LISTS_BAD_LENGTH, TG_REPLAY_LISTS_BAD_GROUP, TG_REPLAY_LISTS_BAD_RANGE, TG_REPLAY_LISTS_NOT_ZERO = 1, 4, 8, 16
+TG_REPLAY_LISTS_MAX_SHIFT = 64
+
 
 class ReplayBufferDesc(C.Structure):
     """``tg_replay_buffer`` of include/tensor_game_replay.h (sizes, then device pointers)."""
@@ -250,7 +258,7 @@ def _load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, argtypes in {**SIGNATURES, **DEMO_SIGNATURES, **SEARCH_SIGNATURES, **REPLAY_SIGNATURES,
-                           **REPLAY_IO_SIGNATURES,
+                           **REPLAY_IO_SIGNATURES, **REPLAY_LISTS_SIGNATURES,
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,

@@ -37,6 +37,7 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "tensor_game.h", 
                                             PKG.parent / "include" / "tensor_game_search.h",
                                             PKG.parent / "include" / "tensor_game_replay.h",
                                             PKG.parent / "include" / "tensor_game_replay_io.h",
+                                            PKG.parent / "include" / "tensor_game_replay_lists.h",
                                             PKG.parent / "include" / "tensor_game_net.h",
                                             PKG.parent / "include" / "tensor_game_net_s25.h",
                                             PKG.parent / "include" / "tensor_game_train.h",

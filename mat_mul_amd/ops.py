@@ -22,7 +22,7 @@ __all__ = [
     "gen_demos", "sample_basis", "change_basis", "as_tokens", "categorical_thresholds",
     "alloc_states", "alloc_ring", "emit_frames", "step_emit", "demo_items", "state_hash", "slice_rank", "alloc_seen_table", "seen",
     "search_reset", "search_select", "search_commit", "search_advance", "search_policy", "replay_add", "replay_items",
-    "replay_pack", "replay_add_packed",
+    "replay_pack", "replay_add_packed", "replay_add_lists",
     "net_check", "net_weights_size", "net_torso", "net_sample", "net_logits",
     "net_s25_check", "net_s25_weights_size", "net_s25_torso", "net_s25_sample", "net_s25_logits",
     "net_train_check", "net_train_workspace_size", "net_loss_grad",
@@ -1014,6 +1014,46 @@ def replay_add_packed(buf, frames, tokens, rewards, lengths, first_slot: int = -
     status = _flag(status, (1,), torch.uint32, dev, "status")
     _launch(dev, "tg_replay_add_packed", C.byref(buf.desc), _ptr(frames), _ptr(tokens), _ptr(rewards), _ptr(lengths),
             G, M, int(first_slot), int(games_added), _ptr(status))
+
+
+# ---- move lists stored as games (include/tensor_game_replay_lists.h) ------------------------------------------------
+
+
+def replay_add_lists(buf, starts, tokens, lengths, groups=None, shift: int = 1, select: bool = False, stored=None,
+                     status=None) -> torch.Tensor:
+    """Replay move lists from their start states and store the games in a ``replay.GameBuffer`` (tg_replay_add_lists):
+    starts int8 (G,T,S,S,S), tokens int8 (M,K,3S) = cat(u,v,w) + shift and lengths int64 (M,) as ``solutions()`` returns
+    them, groups int64 (M,) (None: list m starts from starts[m], M <= G).  A list is stored when 1 <= length <=
+    min(K, L), its group is in [0, G), no entry of its heads leaves int8 and its last head is zero; ``status`` uint32
+    (1,) gets bit 0, 2, 3 or 4 otherwise.  Move t is stored with the frames ``get_child_states`` leaves after t moves,
+    the list's tokens and the reward -(t+1).  ``select``: only the first shortest valid list.  Returns ``stored`` uint8
+    (M,) (allocated when it is not given): 1 where the list was stored.  No host sync."""
+    dev = buf.device
+    for t, name in ((starts, "starts"), (tokens, "tokens"), (lengths, "lengths")):
+        _need_gpu(t, name)
+    G = starts.shape[0] if starts.dim() == 5 else -1
+    want = (G, buf.T, buf.S, buf.S, buf.S)
+    if starts.dtype != torch.int8 or tuple(starts.shape) != want or starts.device != dev:
+        raise TensorGameError("replay_add_lists", -1, f"starts must be int8 (G,T,S,S,S) = {want[1:]} per state on {dev}, "
+                              f"got {starts.dtype} {tuple(starts.shape)} on {starts.device}")
+    if tokens.dim() != 3:
+        raise TensorGameError("replay_add_lists", -1, f"tokens must be int8 (M,K,3S), got {tuple(tokens.shape)}")
+    M, K = tokens.shape[0], tokens.shape[1]
+    tokens = _tokens(tokens, (M, K), buf.S, dev, "tokens")
+    lengths = _flag(lengths, (M,), torch.int64, dev, "lengths")
+    if groups is None:
+        if M > G:
+            raise TensorGameError("replay_add_lists", -1, f"groups: without it list m starts from starts[m], but M={M} "
+                                                          f"> G={G}")
+    else:
+        _need_gpu(groups, "groups")
+        groups = _flag(groups, (M,), torch.int64, dev, "groups")
+    stored = _out(stored, (M,), torch.uint8, dev, "stored", new=torch.zeros)
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    starts = starts.contiguous()
+    _launch(dev, "tg_replay_add_lists", C.byref(buf.desc), _ptr(starts), G, _ptr(groups), _ptr(tokens),
+            _ptr(lengths), M, int(K), int(shift), 1 if select else 0, _ptr(stored), _ptr(status))
+    return stored
 
 
 # ---- fused network inference (include/tensor_game_net.h) ------------------------------------------------------------

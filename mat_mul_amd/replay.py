@@ -24,7 +24,8 @@ class GameBuffer:
     """A ring of ``capacity`` finished games of up to ``max_actions`` moves, each move stored as its ``T`` frames, its
     argmax tokens and its reward (``PlayedGamesDataset``: ``buffer_size`` = capacity).  Flat move indices walk the slots
     in slot order, as the reference walks ``game_lengths``.  ``status`` (uint32 (1,)) collects bit 0 for a game that was
-    not stored (length 0 or > max_actions) and for a bad item index."""
+    not stored (length 0 or > max_actions) and for a bad item index, and bits 2, 3 and 4 for a move list ``add_lists``
+    refused (a bad group, a head outside int8, a last head that is not zero)."""
 
     def __init__(self, capacity: int, max_actions: int, T: int, S: int, device="cuda"):
         self.device = torch.device(device)
@@ -58,6 +59,19 @@ class GameBuffer:
         """Store only the first game with the greatest final reward (act_step's best game, training.py:468-483; nothing
         when no final reward exceeds -1e6).  Asynchronous."""
         self._add(states, policy, rewards, lengths, True)
+
+    def add_lists(self, starts, tokens, lengths, groups=None, shift: int = 1, best: bool = False) -> torch.Tensor:
+        """Store move lists that take their start states to zero -- what ``solutions()`` of the solution search returns
+        -- as games (``ops.replay_add_lists``): starts int8 (G,T,S,S,S), tokens int8 (M,K,3S), lengths (M,), groups
+        (M,) (None: list m starts from starts[m]).  Every valid list is stored, or with ``best`` only the first
+        shortest one; an invalid list (a bad length or group, a head that leaves int8, a last head that is not zero)
+        stores nothing and sets bit 0, 2, 3 or 4 of ``status``.  Returns stored uint8 (M,).  Asynchronous."""
+        dev = self.device
+        lengths = torch.as_tensor(lengths, device=dev).to(torch.int64).contiguous()
+        if groups is not None:
+            groups = torch.as_tensor(groups, device=dev).to(torch.int64).contiguous()
+        return ops.replay_add_lists(self, starts, tokens, lengths, groups=groups, shift=shift, select=best,
+                                    status=self.status)
 
     def __len__(self) -> int:
         """Moves stored (``sum(game_lengths.values())``).  A host sync."""
@@ -297,6 +311,31 @@ class TensorGameData:
         played buffer, the first game with the greatest final reward to the best buffer.  Asynchronous."""
         self.played.add_games(states, policy, rewards, lengths)
         self.best.add_best(states, policy, rewards, lengths)
+
+    def add_solutions(self, res, states: torch.Tensor) -> torch.Tensor:
+        """The factorisations a solution search found, as games to train on: ``res`` is a ``RolloutResult`` (its
+        ``solutions()``) or a ``SolveResult`` (its groups, tokens and lengths), resolved as
+        ``SolutionArchive.add_result`` resolves it, and ``states`` int8 (G,dim_t,S,S,S) the start states the search ran
+        on.  Every valid list goes to the played buffer and the first shortest one to the best buffer, as
+        ``add_act_step`` does for played games.  For ``bases.solve_in_bases`` pass ``reb.found`` with
+        ``bases.expand(states)[0]``: the lists of ``found`` start from the expanded states.  Returns stored uint8 (M,):
+        1 where the list was stored in the played buffer.  No host sync of its own."""
+        if hasattr(res, "solutions"):
+            groups, tokens, lengths = res.solutions()
+        else:
+            groups, tokens, lengths = res.groups, res.tokens, res.lengths
+        if getattr(res, "shift", self.shift) != self.shift:
+            raise TensorGameError("add_solutions", -1, f"res.shift={res.shift}, the dataset's shift={self.shift}")
+        want = (self.dim_t, self.S, self.S, self.S)
+        if states.dim() != 5 or tuple(states.shape[1:]) != want or states.dtype != torch.int8:
+            raise TensorGameError("add_solutions", -1, f"states must be int8 (G,T,S,S,S) with (T,S,S,S) = {want}, got "
+                                                       f"{states.dtype} {tuple(states.shape)}")
+        if tokens.dim() != 3 or tokens.shape[1] > self.played.L:
+            raise TensorGameError("add_solutions", -1, f"max_actions: the lists have {tuple(tokens.shape)[1:2]} moves, "
+                                                       f"the buffers hold {self.played.L}")
+        stored = self.played.add_lists(states, tokens, lengths, groups=groups, shift=self.shift)
+        self.best.add_lists(states, tokens, lengths, groups=groups, shift=self.shift, best=True)
+        return stored
 
     # ---- disk -----------------------------------------------------------------------------------------------------
     def _targets_hash(self, targets) -> int:
