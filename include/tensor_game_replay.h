@@ -35,8 +35,9 @@ extern "C" {
  * its move m (m < length[s]) is frames[s][m] (the T frames of the state the move was played from), tokens[s][m]
  * (the argmax tokens of the move's policy) and rewards[s][m].  offset[s] = length[0] + ... + length[s-1] (offset[C]
  * = every stored move): flat move index i lies in the slot s with offset[s] <= i < offset[s+1], in SLOT order, as the
- * reference walks game_lengths.  ring[0] = the next slot to write, ring[1] = games ever added.  Create it zeroed
- * (lengths, offsets, ring); contents past a slot's length are unspecified. */
+ * reference walks game_lengths.  ring[0] = the next slot to write, ring[1] = games ever added.  Every entry that
+ * stores games leaves ring[0] in [0, C) and takes any other value it finds there modulo C, so no slot index leaves the
+ * buffer.  Create it zeroed (lengths, offsets, ring); contents past a slot's length are unspecified. */
 typedef struct tg_replay_buffer {
   int32_t C, L, T, S;     /* capacity (1..TG_REPLAY_MAX_CAPACITY), moves per slot, frames per state, state size */
   int8_t* frames;         /* [C][L][T][S^3] */

@@ -17,6 +17,10 @@
 int tg_internal_fail(int code, const char* fmt, ...);  // records tg_last_error(), returns code (tg_kernels.hip)
 // the key pass of tg_expand_keyed_i8 (tg_aux.hip)
 extern "C" int tg_internal_hash(const int8_t* state, uint64_t* hash_out, int64_t B, int S, int64_t stride, hipStream_t st);
+// the last launch of every entry that stores games in a replay ring (tg_ring.h): offset = the exclusive prefix sums of
+// length (tg_replay.hip)
+struct tg_replay_buffer;
+int tg_internal_ring_rebuild(const tg_replay_buffer* buf, hipStream_t st);
 namespace tg { struct Dist; }
 // the generator in one kernel (tg_genfused.h, launched from the host side of tg_kernels.hip), called by tg_gen_demos_i8 (tg_gen.hip):
 // 1 = launched, 0 = not applicable (the caller takes the token kernel + tg_gen_from_factors_i8), < 0 = error

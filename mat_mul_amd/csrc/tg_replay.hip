@@ -1,14 +1,13 @@
 // Replay buffers of played games and mixed training batches (include/tensor_game_replay.h).  gfx950 only; part of
 // libtensorgame.so.
 //
-// tg_replay_add: three launches, no host sync.
-//   - replay_plan_kernel (one workgroup of 1024): counts the storable games (select 0) or finds the best one (select 1),
-//     gives every surviving game its slot -- the survivor of rank r goes to (next + r) mod C, so no two games share a
-//     slot -- writes its length, parks the game index in offset[slot] and the survivor count in offset[C] (offset is
-//     rebuilt by the scan anyway), and advances the ring words;
-//   - replay_copy_kernel (one workgroup per possible survivor): copies the game's frames (16-byte loads and stores when
-//     both sides allow), takes the argmax token of every (move, step) of its policy and copies its rewards;
-//   - replay_scan_kernel (one workgroup of 1024): offset = exclusive prefix sums of length over the C slots.
+// tg_replay_add: the three launches of the ring protocol (tg_ring.h), no host sync.
+//   - replay_plan_kernel (one workgroup of 1024): the plan over the storable games (select 0) or the one with the best
+//     final reward (select 1); the parked index is the game's;
+//   - replay_copy_kernel (one workgroup per possible survivor): copies the game's frames, takes the argmax token of
+//     every (move, step) of its policy and copies its rewards;
+//   - ring_rebuild_kernel (one workgroup of 1024): offset = exclusive prefix sums of length over the C slots.  It is
+//     the library's only one: tg_internal_ring_rebuild launches it for the other two entries as well.
 // tg_replay_items: the three item kernels of tg_items.h with the MixedRows policy -- a row resolves through the epoch
 // table (or directly) to a synthetic item, which takes the tg_demo_items path unchanged, or to a stored move, found by a
 // binary search over offset and written as a plain frame copy.
@@ -18,6 +17,7 @@
 
 #include "../../include/tensor_game_replay.h"
 #include "tg_items.h"
+#include "tg_ring.h"
 
 namespace tg {
 
@@ -106,8 +106,6 @@ struct MixedRows {
 };
 
 // ---- tg_replay_add --------------------------------------------------------------------------------------------------
-constexpr int kScanBlock = 1024;
-
 struct AddArgs {
   tg_replay_buffer b;
   const int8_t* states;  // (B,L,T,S^3)
@@ -119,35 +117,19 @@ struct AddArgs {
   uint32_t* status;
 };
 
-// exclusive prefix sum of v over the workgroup (kScanBlock threads); *total = the sum of all.  sh: kScanBlock int64.
-__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t* sh, int64_t* total) {
-  const int t = threadIdx.x;
-  __syncthreads();  // sh's previous readers are done
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const int64_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  *total = sh[kScanBlock - 1];
-  return sh[t] - v;
-}
-
 __device__ __forceinline__ bool storable(int64_t len, int L) { return len >= 1 && len <= L; }
 
-__global__ __launch_bounds__(kScanBlock) void replay_plan_kernel(AddArgs p) {
-  __shared__ int64_t sh[kScanBlock];
-  __shared__ float best_r[kScanBlock];
-  __shared__ int64_t best_g[kScanBlock];
+__global__ __launch_bounds__(kRingScanBlock) void replay_plan_kernel(AddArgs p) {
+  __shared__ int64_t sh[kRingScanBlock];
+  __shared__ float best_r[kRingScanBlock];
+  __shared__ int64_t best_g[kRingScanBlock];
   const int t = threadIdx.x, L = p.b.L;
-  const int64_t C = p.b.C, next = p.b.ring[0];
+  const int64_t next = ring_next(p.b);
   int64_t cnt = 0;
   int bad = 0;
   float br = -1e6f;  // act_step: best_reward = -1e6, strict >
   int64_t bg = -1;
-  for (int64_t g = t; g < p.B; g += kScanBlock) {
+  for (int64_t g = t; g < p.B; g += kRingScanBlock) {
     const int64_t len = p.lengths[g];
     const bool ok = storable(len, L);
     cnt += ok;
@@ -160,52 +142,18 @@ __global__ __launch_bounds__(kScanBlock) void replay_plan_kernel(AddArgs p) {
   if (__syncthreads_or(bad) && t == 0 && p.status) atomicOr(p.status, 1u);
   int64_t V, n_surv;
   if (p.select == 0) {
-    block_exclusive_scan(cnt, sh, &V);
-    n_surv = V < C ? V : C;
-    const int64_t r0 = V - n_surv;  // ranks below r0 would be overwritten within this call: never written
-    int64_t base = 0;
-    for (int64_t g0 = 0; g0 < p.B; g0 += kScanBlock) {
-      const int64_t g = g0 + t;
-      const int64_t len = g < p.B ? p.lengths[g] : 0;
-      const bool ok = storable(len, L);
-      int64_t chunk;
-      const int64_t r = base + block_exclusive_scan(ok, sh, &chunk);
-      if (ok && r >= r0) {
-        const int64_t slot = (next + r) % C;
-        p.b.offset[slot] = g;
-        p.b.length[slot] = static_cast<int32_t>(len);
-      }
-      base += chunk;
-    }
+    ring_plan_all(p.b, next, p.B, cnt, sh, [&](int64_t g0, int32_t* len, int64_t* park) {
+      const int64_t g = g0 + t, n = g < p.B ? p.lengths[g] : 0;
+      *len = static_cast<int32_t>(n);
+      *park = g;
+      return storable(n, L);
+    }, &V, &n_surv);
   } else {
     // (reward greater, or equal at a smaller game index) wins: the sequential first-strict-maximum
-    best_r[t] = br;
-    best_g[t] = bg;
-    __syncthreads();
-    for (int d = kScanBlock / 2; d > 0; d >>= 1) {
-      if (t < d) {
-        const float r2 = best_r[t + d];
-        const int64_t g2 = best_g[t + d];
-        if (g2 >= 0 && (best_g[t] < 0 || r2 > best_r[t] || (r2 == best_r[t] && g2 < best_g[t]))) {
-          best_r[t] = r2;
-          best_g[t] = g2;
-        }
-      }
-      __syncthreads();
-    }
-    const int64_t g = best_g[0];
-    V = n_surv = g >= 0 ? 1 : 0;
-    if (t == 0 && g >= 0) {
-      p.b.offset[next] = g;
-      p.b.length[next] = static_cast<int32_t>(p.lengths[g]);
-    }
+    const int64_t g = ring_best(br, bg, best_r, best_g, [](float a, float b) { return a > b; });
+    V = n_surv = ring_plan_one(p.b, next, g, g >= 0 ? p.lengths[g] : 0);
   }
-  __syncthreads();  // every thread has read ring[0]
-  if (t == 0) {
-    p.b.ring[0] = (next + V) % C;
-    p.b.ring[1] += V;
-    p.b.offset[C] = n_surv;
-  }
+  ring_commit(p.b, next, V, n_surv);
 }
 
 // torch.argmax over n floats: the first maximal index, a NaN counts as the maximum (the first NaN wins)
@@ -222,23 +170,12 @@ __device__ __forceinline__ int argmax_first(const float* v, int n) {
 }
 
 __global__ __launch_bounds__(kBlock) void replay_copy_kernel(AddArgs p) {
-  const int64_t C = p.b.C, n_surv = p.b.offset[C], j = blockIdx.x;
-  if (j >= n_surv) return;
+  int64_t slot, g;
+  int len;
+  if (!ring_survivor(p.b, blockIdx.x, &slot, &g, &len)) return;
   const int t = threadIdx.x, L = p.b.L, A3 = 3 * p.b.S;
-  const int64_t slot = ((p.b.ring[0] - n_surv + j) % C + C) % C;
-  const int64_t g = p.b.offset[slot];
-  const int len = p.b.length[slot];
   const int64_t fb = static_cast<int64_t>(p.b.T) * p.b.S * p.b.S * p.b.S;  // bytes per state
-  const int8_t* sf = p.states + g * L * fb;
-  int8_t* df = p.b.frames + slot * L * fb;
-  const int64_t nbytes = len * fb;
-  int64_t done = 0;
-  if (((reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(df)) & 15) == 0) {
-    done = nbytes & ~static_cast<int64_t>(15);
-    for (int64_t c = t; c < done / 16; c += kBlock)
-      reinterpret_cast<uint4*>(df)[c] = reinterpret_cast<const uint4*>(sf)[c];
-  }
-  for (int64_t e = done + t; e < nbytes; e += kBlock) df[e] = sf[e];
+  copy_bytes(p.b.frames + slot * L * fb, p.states + g * L * fb, len * fb, t, kBlock);
   const float* pol = p.policy + g * L * A3 * static_cast<int64_t>(p.n_logits);
   int8_t* tk = p.b.tokens + slot * L * A3;
   for (int q = t; q < len * A3; q += kBlock)
@@ -246,9 +183,9 @@ __global__ __launch_bounds__(kBlock) void replay_copy_kernel(AddArgs p) {
   for (int m = t; m < len; m += kBlock) p.b.rewards[slot * L + m] = p.rewards[g * L + m];
 }
 
-__global__ __launch_bounds__(kScanBlock) void replay_scan_kernel(tg_replay_buffer b) {
-  __shared__ int64_t sh[kScanBlock];
-  const int t = threadIdx.x, per = (b.C + kScanBlock - 1) / kScanBlock;
+__global__ __launch_bounds__(kRingScanBlock) void ring_rebuild_kernel(tg_replay_buffer b) {
+  __shared__ int64_t sh[kRingScanBlock];
+  const int t = threadIdx.x, per = (b.C + kRingScanBlock - 1) / kRingScanBlock;
   const int lo = min(t * per, b.C), hi = min(lo + per, b.C);
   int64_t sum = 0;
   for (int s = lo; s < hi; ++s) sum += b.length[s];
@@ -275,22 +212,6 @@ struct MixKernels {
   static constexpr auto exact() { return tg::items_exact_kernel<tg::MixedRows, OutT, tg::MixArgs>; }
 };
 
-int check_buffer(const char* fn, const char* what, const tg_replay_buffer* b) {
-  if (b->C < 1 || b->C > TG_REPLAY_MAX_CAPACITY)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: %s C=%d outside [1,%d]", fn, what, b->C, TG_REPLAY_MAX_CAPACITY);
-  if (b->L < 1 || b->L > TG_REPLAY_MAX_ACTIONS)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: %s L=%d outside [1,%d]", fn, what, b->L, TG_REPLAY_MAX_ACTIONS);
-  if (b->T < 1 || b->T > TG_REPLAY_MAX_T)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: %s T=%d outside [1,%d]", fn, what, b->T, TG_REPLAY_MAX_T);
-  if (b->S < 1 || b->S > TG_MAX_S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: %s S=%d outside [1,%d]", fn, what, b->S, TG_MAX_S);
-  if (!b->frames || !b->tokens || !b->rewards || !b->length || !b->offset || !b->ring)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: null %s buffer array", fn, what);
-  if (!aligned(b->rewards, 4) || !aligned(b->length, 4) || !aligned(b->offset, 8) || !aligned(b->ring, 8))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: %s buffer arrays not aligned to their elements", fn, what);
-  return TG_OK;
-}
-
 }  // namespace
 
 extern "C" int tg_replay_add(const tg_replay_buffer* buf, const int8_t* states, const float* policy, int n_logits,
@@ -298,7 +219,8 @@ extern "C" int tg_replay_add(const tg_replay_buffer* buf, const int8_t* states, 
                              tg_stream_t stream) {
   const char* fn = "tg_replay_add";
   if (!buf) return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer", fn);
-  if (int rc = check_buffer(fn, "the", buf)) return rc;
+  if (int rc = check_ring_sizes(fn, "", buf)) return rc;
+  if (int rc = check_ring_arrays(fn, "", buf)) return rc;
   if (n_logits < 1 || n_logits > TG_REPLAY_MAX_LOGITS)
     return tg_internal_fail(TG_ERR_INVALID, "%s: n_logits=%d outside [1,%d]", fn, n_logits, TG_REPLAY_MAX_LOGITS);
   if (select != 0 && select != 1) return tg_internal_fail(TG_ERR_INVALID, "%s: select=%d (0 all, 1 best)", fn, select);
@@ -311,9 +233,13 @@ extern "C" int tg_replay_add(const tg_replay_buffer* buf, const int8_t* states, 
   const tg::AddArgs p{*buf, states, policy, rewards, lengths, B, n_logits, select, status};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t copies = select ? 1 : (B < buf->C ? B : buf->C);
-  if (int rc = launch(fn, tg::replay_plan_kernel, 1, tg::kScanBlock, 0, st, p)) return rc;
+  if (int rc = launch(fn, tg::replay_plan_kernel, 1, tg::kRingScanBlock, 0, st, p)) return rc;
   if (int rc = launch(fn, tg::replay_copy_kernel, static_cast<unsigned>(copies), tg::kBlock, 0, st, p)) return rc;
-  return launch(fn, tg::replay_scan_kernel, 1, tg::kScanBlock, 0, st, *buf);
+  return tg_internal_ring_rebuild(buf, st);
+}
+
+int tg_internal_ring_rebuild(const tg_replay_buffer* buf, hipStream_t st) {
+  return launch("tg_internal_ring_rebuild", tg::ring_rebuild_kernel, 1, tg::kRingScanBlock, 0, st, *buf);
 }
 
 extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int64_t n_demos, int R, int S,
@@ -325,12 +251,13 @@ extern "C" int tg_replay_items(const int8_t* tokens, const int8_t* targets, int6
   const char* fn = "tg_replay_items";
   if (int rc = check_items(fn, n_demos, R, S, target_stride_bytes, T, out_dtype)) return rc;
   const tg_replay_buffer* bufs[2] = {played, best};
-  const char* names[2] = {"played", "best"};
+  const char* names[2] = {"played ", "best "};
   for (int q = 0; q < 2; ++q) {
     if (!bufs[q]) continue;
-    if (int rc = check_buffer(fn, names[q], bufs[q])) return rc;
+    if (int rc = check_ring_sizes(fn, names[q], bufs[q])) return rc;
+    if (int rc = check_ring_arrays(fn, names[q], bufs[q])) return rc;
     if (bufs[q]->S != S || bufs[q]->T != T)
-      return tg_internal_fail(TG_ERR_INVALID, "%s: %s buffer has S=%d T=%d, the items S=%d T=%d", fn, names[q],
+      return tg_internal_fail(TG_ERR_INVALID, "%s: %sbuffer has S=%d T=%d, the items S=%d T=%d", fn, names[q],
                               bufs[q]->S, bufs[q]->T, S, T);
   }
   if (kind) {

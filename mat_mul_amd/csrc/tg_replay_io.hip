@@ -8,68 +8,29 @@
 //     writes (G, M);
 //   - pack_copy_kernel (one workgroup per possible rank): reads its slot, replaces it by the length, and copies the
 //     game's frames, tokens and rewards to its rows unless they would pass max_moves.
-// tg_replay_add_packed: three launches, the shape of tg_replay_add.
+// tg_replay_add_packed: the three launches of the ring protocol (tg_ring.h).
 //   - unpack_plan_kernel (one workgroup of 1024): walks the G lengths in chunks of 1024, twice: the first walk counts
-//     the games that will be stored (a good length and rows inside M), the second gives each its rank and slot
-//     (next + rank) mod C, writes its length and parks its first row in offset[slot]; then the ring words;
+//     the games that will be stored (a good length and rows inside M), the second is the plan; the parked index is the
+//     game's first row;
 //   - unpack_copy_kernel (one workgroup per stored game): frames, tokens and rewards from the rows into the slot;
-//   - unpack_scan_kernel: offset = exclusive prefix sums of length, as tg_replay_add's scan.
-// Every copy picks its access width per game from the two addresses: 16 bytes, dwords, or bytes, with a byte tail.
+//   - the rebuild of offset (tg_internal_ring_rebuild).
+// Every copy picks its access width per game from the two addresses (copy_bytes, tg_ring.h).
 #include <hip/hip_runtime.h>
 
 #include "../../include/tensor_game_replay_io.h"
 #include "tg_host.h"
+#include "tg_ring.h"
 
 namespace tg {
 namespace rio {
-
-constexpr int kScanBlock = 1024;
-
-// exclusive prefix sum of v over the workgroup (kScanBlock threads); *total = the sum of all.  sh: kScanBlock int64.
-__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t* sh, int64_t* total) {
-  const int t = threadIdx.x;
-  __syncthreads();  // sh's previous readers are done
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const int64_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  *total = sh[kScanBlock - 1];
-  return sh[t] - v;
-}
-
-// n bytes from s to d by the whole workgroup (kBlock threads): the widest access both addresses allow, then a byte tail
-__device__ __forceinline__ void copy_bytes(int8_t* d, const int8_t* s, int64_t n, int t) {
-  const uintptr_t both = reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(s);
-  int64_t done = 0;
-  if ((both & 15) == 0) {
-    done = n & ~static_cast<int64_t>(15);
-    for (int64_t c = t; c < done / 16; c += kBlock)
-      reinterpret_cast<uint4*>(d)[c] = reinterpret_cast<const uint4*>(s)[c];
-  } else if ((both & 3) == 0) {
-    done = n & ~static_cast<int64_t>(3);
-    for (int64_t c = t; c < done / 4; c += kBlock)
-      reinterpret_cast<uint32_t*>(d)[c] = reinterpret_cast<const uint32_t*>(s)[c];
-  }
-  for (int64_t e = done + t; e < n; e += kBlock) d[e] = s[e];
-}
 
 // the three arrays of one game: `len` moves from (frames, tokens, rewards) at sf/st/sr to df/dt/dr
 __device__ __forceinline__ void copy_game(const tg_replay_buffer& b, int len, int8_t* df, const int8_t* sf, int8_t* dt,
                                           const int8_t* st, float* dr, const float* sr, int t) {
   const int64_t fb = static_cast<int64_t>(b.T) * b.S * b.S * b.S;  // bytes per state
-  copy_bytes(df, sf, len * fb, t);
-  copy_bytes(dt, st, static_cast<int64_t>(len) * 3 * b.S, t);
+  copy_bytes(df, sf, len * fb, t, kBlock);
+  copy_bytes(dt, st, static_cast<int64_t>(len) * 3 * b.S, t, kBlock);
   for (int m = t; m < len; m += kBlock) dr[m] = sr[m];
-}
-
-// ring[0] as a slot (a consistent ring holds 0 .. C-1; anything else is folded into it, so no index leaves the buffer)
-__device__ __forceinline__ int64_t next_slot(const tg_replay_buffer& b) {
-  const int64_t C = b.C;
-  return (b.ring[0] % C + C) % C;
 }
 
 // ---- tg_replay_pack -------------------------------------------------------------------------------------------------
@@ -91,11 +52,11 @@ __device__ __forceinline__ int stored_len(const tg_replay_buffer& b, int64_t s) 
   return len < 0 ? 0 : (len > b.L ? b.L : len);
 }
 
-__global__ __launch_bounds__(kScanBlock) void pack_plan_kernel(PackArgs p) {
-  __shared__ int64_t sh[kScanBlock];
+__global__ __launch_bounds__(kRingScanBlock) void pack_plan_kernel(PackArgs p) {
+  __shared__ int64_t sh[kRingScanBlock];
   const int t = threadIdx.x;
-  const int64_t C = p.b.C, next = next_slot(p.b);
-  const int64_t per = (C + kScanBlock - 1) / kScanBlock;
+  const int64_t C = p.b.C, next = ring_next(p.b);
+  const int64_t per = (C + kRingScanBlock - 1) / kRingScanBlock;
   const int64_t lo = t * per < C ? t * per : C, hi = lo + per < C ? lo + per : C;
   int64_t cnt = 0, sum = 0;
   for (int64_t j = lo; j < hi; ++j) {
@@ -166,103 +127,48 @@ __device__ __forceinline__ bool chunk_game(const UnpackArgs& p, int64_t g0, int6
   return good && fits;
 }
 
-__global__ __launch_bounds__(kScanBlock) void unpack_plan_kernel(UnpackArgs p) {
-  __shared__ int64_t sh[kScanBlock];
+__global__ __launch_bounds__(kRingScanBlock) void unpack_plan_kernel(UnpackArgs p) {
+  __shared__ int64_t sh[kRingScanBlock];
   const int t = threadIdx.x;
-  const int64_t C = p.b.C, next = p.first_slot >= 0 ? p.first_slot : next_slot(p.b);
-  int64_t cnt = 0, base = 0, row;
-  int flags = 0, len;
-  for (int64_t g0 = 0; g0 < p.G; g0 += kScanBlock) cnt += chunk_game(p, g0, sh, &base, &len, &row, &flags);
+  const int64_t next = p.first_slot >= 0 ? p.first_slot : ring_next(p.b);
+  int64_t cnt = 0, base = 0;  // base: the first row of the chunk a walk is at
+  int flags = 0;
+  const auto game = [&](int64_t g0, int32_t* len, int64_t* row) {
+    return chunk_game(p, g0, sh, &base, len, row, &flags);
+  };
+  int32_t len;
+  int64_t row;
+  for (int64_t g0 = 0; g0 < p.G; g0 += kRingScanBlock) cnt += game(g0, &len, &row);
   const int bad = __syncthreads_or(flags & TG_REPLAY_IO_BAD_LENGTH), cut = __syncthreads_or(flags & TG_REPLAY_IO_TRUNCATED);
   if (t == 0 && p.status && (bad || cut))
     atomicOr(p.status, (bad ? TG_REPLAY_IO_BAD_LENGTH : 0u) | (cut ? TG_REPLAY_IO_TRUNCATED : 0u));
-  int64_t V;
-  block_exclusive_scan(cnt, sh, &V);
-  const int64_t n_surv = V < C ? V : C;
-  const int64_t r0 = V - n_surv;  // ranks below r0 would be overwritten within this call: never written
-  int64_t rank0 = 0;
-  base = 0;
-  for (int64_t g0 = 0; g0 < p.G; g0 += kScanBlock) {
-    const bool ok = chunk_game(p, g0, sh, &base, &len, &row, &flags);
-    int64_t chunk;
-    const int64_t r = rank0 + block_exclusive_scan(ok, sh, &chunk);
-    if (ok && r >= r0) {
-      const int64_t slot = (next + r) % C;
-      p.b.offset[slot] = row;  // parked for the copy; the scan rebuilds offset
-      p.b.length[slot] = len;
-    }
-    rank0 += chunk;
-  }
-  __syncthreads();  // every thread has read ring[0]
-  if (t == 0) {
-    p.b.ring[0] = (next + V) % C;
-    p.b.ring[1] = p.games_added >= 0 ? p.games_added : p.b.ring[1] + V;
-    p.b.offset[C] = n_surv;
-  }
+  int64_t V, n_surv;
+  base = 0;  // the second walk starts at row 0 again
+  ring_plan_all(p.b, next, p.G, cnt, sh, game, &V, &n_surv);
+  ring_commit(p.b, next, V, n_surv, p.games_added);
 }
 
 __global__ __launch_bounds__(kBlock) void unpack_copy_kernel(UnpackArgs p) {
-  const int64_t C = p.b.C, n_surv = p.b.offset[C], j = blockIdx.x;
-  if (j >= n_surv) return;
+  int64_t slot, row;
+  int len;
+  if (!ring_survivor(p.b, blockIdx.x, &slot, &row, &len)) return;
   const int t = threadIdx.x, L = p.b.L, A3 = 3 * p.b.S;
-  const int64_t slot = ((p.b.ring[0] - n_surv + j) % C + C) % C;
-  const int64_t row = p.b.offset[slot];
-  const int len = p.b.length[slot];
   const int64_t fb = static_cast<int64_t>(p.b.T) * p.b.S * p.b.S * p.b.S;
   copy_game(p.b, len, p.b.frames + slot * L * fb, p.frames + row * fb, p.b.tokens + slot * L * A3,
             p.tokens + row * A3, p.b.rewards + slot * L, p.rewards + row, t);
 }
 
-__global__ __launch_bounds__(kScanBlock) void unpack_scan_kernel(tg_replay_buffer b) {
-  __shared__ int64_t sh[kScanBlock];
-  const int t = threadIdx.x, per = (b.C + kScanBlock - 1) / kScanBlock;
-  const int lo = min(t * per, b.C), hi = min(lo + per, b.C);
-  int64_t sum = 0;
-  for (int s = lo; s < hi; ++s) sum += b.length[s];
-  int64_t total;
-  int64_t run = block_exclusive_scan(sum, sh, &total);
-  for (int s = lo; s < hi; ++s) {
-    b.offset[s] = run;
-    run += b.length[s];
-  }
-  if (t == 0) b.offset[b.C] = total;
-}
-
 }  // namespace rio
 }  // namespace tg
-
-namespace {
-
-int check_sizes(const char* fn, const tg_replay_buffer* b) {
-  if (b->C < 1 || b->C > TG_REPLAY_MAX_CAPACITY)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: C=%d outside [1,%d]", fn, b->C, TG_REPLAY_MAX_CAPACITY);
-  if (b->L < 1 || b->L > TG_REPLAY_MAX_ACTIONS)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: L=%d outside [1,%d]", fn, b->L, TG_REPLAY_MAX_ACTIONS);
-  if (b->T < 1 || b->T > TG_REPLAY_MAX_T)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: T=%d outside [1,%d]", fn, b->T, TG_REPLAY_MAX_T);
-  if (b->S < 1 || b->S > TG_MAX_S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, b->S, TG_MAX_S);
-  return TG_OK;
-}
-
-int check_arrays(const char* fn, const tg_replay_buffer* b) {
-  if (!b->frames || !b->tokens || !b->rewards || !b->length || !b->offset || !b->ring)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer array", fn);
-  if (!aligned(b->rewards, 4) || !aligned(b->length, 4) || !aligned(b->offset, 8) || !aligned(b->ring, 8))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: buffer arrays not aligned to their elements", fn);
-  return TG_OK;
-}
-
-}  // namespace
 
 extern "C" int tg_replay_pack(const tg_replay_buffer* buf, int64_t max_moves, int32_t* lengths_out,
                               int64_t* move_offset_out, int64_t* counts_out, float* rewards_out, int8_t* tokens_out,
                               int8_t* frames_out, uint32_t* status, tg_stream_t stream) {
   const char* fn = "tg_replay_pack";
   if (!buf) return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer", fn);
-  if (int rc = check_sizes(fn, buf)) return rc;
+  if (int rc = check_ring_sizes(fn, "", buf)) return rc;
   if (max_moves < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: max_moves=%lld < 0", fn, (long long)max_moves);
-  if (int rc = check_arrays(fn, buf)) return rc;
+  if (int rc = check_ring_arrays(fn, "", buf)) return rc;
   if (!lengths_out || !move_offset_out || !counts_out)
     return tg_internal_fail(TG_ERR_INVALID, "%s: null lengths_out, move_offset_out or counts_out", fn);
   if (max_moves > 0 && (!rewards_out || !tokens_out || !frames_out))
@@ -274,7 +180,7 @@ extern "C" int tg_replay_pack(const tg_replay_buffer* buf, int64_t max_moves, in
   const tg::rio::PackArgs p{*buf, max_moves, lengths_out, move_offset_out, counts_out, rewards_out, tokens_out,
                             frames_out, status};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = launch(fn, tg::rio::pack_plan_kernel, 1, tg::rio::kScanBlock, 0, st, p)) return rc;
+  if (int rc = launch(fn, tg::rio::pack_plan_kernel, 1, tg::kRingScanBlock, 0, st, p)) return rc;
   return launch(fn, tg::rio::pack_copy_kernel, static_cast<unsigned>(buf->C), tg::kBlock, 0, st, p);
 }
 
@@ -283,7 +189,7 @@ extern "C" int tg_replay_add_packed(const tg_replay_buffer* buf, const int8_t* f
                                     int64_t first_slot, int64_t games_added, uint32_t* status, tg_stream_t stream) {
   const char* fn = "tg_replay_add_packed";
   if (!buf) return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer", fn);
-  if (int rc = check_sizes(fn, buf)) return rc;
+  if (int rc = check_ring_sizes(fn, "", buf)) return rc;
   if (M < 0) return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld < 0", fn, (long long)M);
   if (G < 0 || G > (int64_t{1} << 31))
     return tg_internal_fail(TG_ERR_INVALID, "%s: G=%lld outside [0,2^31]", fn, (long long)G);
@@ -291,7 +197,7 @@ extern "C" int tg_replay_add_packed(const tg_replay_buffer* buf, const int8_t* f
     return tg_internal_fail(TG_ERR_INVALID, "%s: first_slot=%lld outside [-1,%d)", fn, (long long)first_slot, buf->C);
   if (games_added < -1)
     return tg_internal_fail(TG_ERR_INVALID, "%s: games_added=%lld < -1", fn, (long long)games_added);
-  if (int rc = check_arrays(fn, buf)) return rc;
+  if (int rc = check_ring_arrays(fn, "", buf)) return rc;
   if (G == 0) return TG_OK;
   if (!lengths) return tg_internal_fail(TG_ERR_INVALID, "%s: null lengths", fn);
   if (M > 0 && (!frames || !tokens || !rewards))
@@ -301,7 +207,7 @@ extern "C" int tg_replay_add_packed(const tg_replay_buffer* buf, const int8_t* f
   const tg::rio::UnpackArgs p{*buf, frames, tokens, rewards, lengths, G, M, first_slot, games_added, status};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t copies = G < buf->C ? G : buf->C;
-  if (int rc = launch(fn, tg::rio::unpack_plan_kernel, 1, tg::rio::kScanBlock, 0, st, p)) return rc;
+  if (int rc = launch(fn, tg::rio::unpack_plan_kernel, 1, tg::kRingScanBlock, 0, st, p)) return rc;
   if (int rc = launch(fn, tg::rio::unpack_copy_kernel, static_cast<unsigned>(copies), tg::kBlock, 0, st, p)) return rc;
-  return launch(fn, tg::rio::unpack_scan_kernel, 1, tg::rio::kScanBlock, 0, st, *buf);
+  return tg_internal_ring_rebuild(buf, st);
 }

@@ -5,14 +5,13 @@
 //   - lists_valid_kernel (one workgroup per list): checks the length and the group, then replays the list ROW BY ROW: a
 //     thread takes rows (i, j, 0 .. S-1) of the tensor and runs the L moves on that one row in registers, so nothing is
 //     stored and no barrier is needed until the flags are combined; writes stored[m] and ORs the status bits;
-//   - lists_plan_kernel (one workgroup of 1024): the plan of tg_replay_add over the valid lists -- the valid list of
-//     rank r goes to slot (next + r) mod C (select 0) or the first shortest one to `next` (select 1), its length is
-//     written, its index parked in offset[slot], the survivor count in offset[C]; the ring words advance; with select 1
-//     stored[] is cut down to the winner.  Without `stored` the plan calls the validity replay itself, one thread per list;
+//   - lists_plan_kernel (one workgroup of 1024): the plan of the ring protocol (tg_ring.h) over the valid lists (select
+//     0) or the first shortest one (select 1); the parked index is the list's; with select 1 stored[] is cut down to
+//     the winner.  Without `stored` the plan calls the validity replay itself, one thread per list;
 //   - lists_emit_kernel (one workgroup per stored game and per kEmitChunk entries of the tensor -- the entries are
 //     independent of each other, and a game alone is too little work for a CU): its entries of the game's frames as below;
 //     the first workgroup of a game also writes its tokens and rewards;
-//   - lists_scan_kernel (one workgroup of 1024): offset = exclusive prefix sums of length over the C slots.
+//   - the rebuild of offset (tg_internal_ring_rebuild).
 //
 // The emit kernel loads its entries of the T frames of the start state into LDS, as bytes, and walks s = -(T-1) .. L-1:
 // for s <= 0 the tensor is frame -s of the start state, for s > 0 it is head_s = head_{s-1} - u (x) v (x) w, frame 0
@@ -25,11 +24,11 @@
 
 #include "../../include/tensor_game_replay_lists.h"
 #include "tg_host.h"
+#include "tg_ring.h"
 
 namespace tg {
 namespace rl {
 
-constexpr int kScanBlock = 1024;
 constexpr int kSmallBlock = 64;  // one wavefront per list or game while S^3 <= kSmallEntries
 constexpr int kSmallEntries = 1024;
 constexpr int kValidBlock = 1024;  // per list above kSmallEntries: the replay is latency bound, one workgroup per list
@@ -47,28 +46,6 @@ struct ListArgs {
   uint8_t* stored;   // (M) or NULL
   uint32_t* status;  // (1) or NULL
 };
-
-// exclusive prefix sum of v over the workgroup (kScanBlock threads); *total = the sum of all.  sh: kScanBlock int64.
-__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t* sh, int64_t* total) {
-  const int t = threadIdx.x;
-  __syncthreads();  // sh's previous readers are done
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const int64_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  *total = sh[kScanBlock - 1];
-  return sh[t] - v;
-}
-
-// ring[0] as a slot (a consistent ring holds 0 .. C-1; anything else is folded into it, so no index leaves the buffer)
-__device__ __forceinline__ int64_t next_slot(const tg_replay_buffer& b) {
-  const int64_t C = b.C;
-  return (b.ring[0] % C + C) % C;
-}
 
 // The status bits list m earns on the rows tid, tid + nthr, ... of its tensor (the length and group bits on every
 // thread).  The length and the group are checked before they address anything; a list that fails either is not
@@ -140,15 +117,15 @@ __device__ __forceinline__ bool list_valid(const ListArgs& p, int64_t m, uint32_
   return f == 0;
 }
 
-__global__ __launch_bounds__(kScanBlock) void lists_plan_kernel(ListArgs p) {
-  __shared__ int64_t sh[kScanBlock];
-  __shared__ int64_t best_l[kScanBlock];
-  __shared__ int64_t best_m[kScanBlock];
+__global__ __launch_bounds__(kRingScanBlock) void lists_plan_kernel(ListArgs p) {
+  __shared__ int64_t sh[kRingScanBlock];
+  __shared__ int64_t best_l[kRingScanBlock];
+  __shared__ int64_t best_m[kRingScanBlock];
   const int t = threadIdx.x;
-  const int64_t C = p.b.C, next = next_slot(p.b);
+  const int64_t next = ring_next(p.b);
   int64_t cnt = 0, bl = 0, bm = -1;
   uint32_t flags = 0;
-  for (int64_t m = t; m < p.M; m += kScanBlock) {
+  for (int64_t m = t; m < p.M; m += kRingScanBlock) {
     if (!list_valid(p, m, &flags)) continue;
     ++cnt;
     const int64_t len = p.lengths[m];
@@ -162,68 +139,21 @@ __global__ __launch_bounds__(kScanBlock) void lists_plan_kernel(ListArgs p) {
   }
   int64_t V, n_surv;
   if (p.select == 0) {
-    block_exclusive_scan(cnt, sh, &V);
-    n_surv = V < C ? V : C;
-    const int64_t r0 = V - n_surv;  // ranks below r0 would be overwritten within this call: never written
-    int64_t base = 0;
-    for (int64_t m0 = 0; m0 < p.M; m0 += kScanBlock) {
+    ring_plan_all(p.b, next, p.M, cnt, sh, [&](int64_t m0, int32_t* len, int64_t* park) {
       const int64_t m = m0 + t;
       const bool ok = m < p.M && list_valid(p, m, &flags);
-      int64_t chunk;
-      const int64_t r = base + block_exclusive_scan(ok, sh, &chunk);
-      if (ok && r >= r0) {
-        const int64_t slot = (next + r) % C;
-        p.b.offset[slot] = m;  // parked for the emit; the scan rebuilds offset
-        p.b.length[slot] = static_cast<int32_t>(p.lengths[m]);
-      }
-      base += chunk;
-    }
+      *len = ok ? static_cast<int32_t>(p.lengths[m]) : 0;
+      *park = m;
+      return ok;
+    }, &V, &n_surv);
   } else {
     // (shorter, or equal at a smaller list index) wins: the sequential first-strict-maximum of the final reward -L
-    best_l[t] = bl;
-    best_m[t] = bm;
-    __syncthreads();
-    for (int d = kScanBlock / 2; d > 0; d >>= 1) {
-      if (t < d) {
-        const int64_t l2 = best_l[t + d], m2 = best_m[t + d];
-        if (m2 >= 0 && (best_m[t] < 0 || l2 < best_l[t] || (l2 == best_l[t] && m2 < best_m[t]))) {
-          best_l[t] = l2;
-          best_m[t] = m2;
-        }
-      }
-      __syncthreads();
-    }
-    const int64_t win = best_m[0];
-    V = n_surv = win >= 0 ? 1 : 0;
-    if (t == 0 && win >= 0) {
-      p.b.offset[next] = win;
-      p.b.length[next] = static_cast<int32_t>(best_l[0]);
-    }
+    const int64_t win = ring_best(bl, bm, best_l, best_m, [](int64_t a, int64_t b) { return a < b; });
+    V = n_surv = ring_plan_one(p.b, next, win, best_l[0]);
     if (p.stored)  // every thread has read the flags of the lists it rewrites
-      for (int64_t m = t; m < p.M; m += kScanBlock) p.stored[m] = m == win;
+      for (int64_t m = t; m < p.M; m += kRingScanBlock) p.stored[m] = m == win;
   }
-  __syncthreads();  // every thread has read ring[0]
-  if (t == 0) {
-    p.b.ring[0] = (next + V) % C;
-    p.b.ring[1] += V;
-    p.b.offset[C] = n_surv;
-  }
-}
-
-// n bytes from s to d by the whole workgroup: the widest access both addresses allow, then a byte tail (the rule of
-// tg_replay_pack's copies)
-__device__ __forceinline__ void copy_bytes(int8_t* d, const int8_t* s, int64_t n, int t, int nthr) {
-  const uintptr_t both = reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(s);
-  int64_t done = 0;
-  if ((both & 15) == 0) {
-    done = n & ~static_cast<int64_t>(15);
-    for (int64_t c = t; c < done / 16; c += nthr) reinterpret_cast<uint4*>(d)[c] = reinterpret_cast<const uint4*>(s)[c];
-  } else if ((both & 3) == 0) {
-    done = n & ~static_cast<int64_t>(3);
-    for (int64_t c = t; c < done / 4; c += nthr)
-      reinterpret_cast<uint32_t*>(d)[c] = reinterpret_cast<const uint32_t*>(s)[c];
-  }
-  for (int64_t e = done + t; e < n; e += nthr) d[e] = s[e];
+  ring_commit(p.b, next, V, n_surv);
 }
 
 __device__ __forceinline__ int8_t lds_byte(const uint32_t* w, int e) {
@@ -261,14 +191,12 @@ __host__ __device__ inline int emit_lds_words(int S, int T) {
 
 __global__ __launch_bounds__(kBlock) void lists_emit_kernel(ListArgs p) {
   extern __shared__ uint32_t lds[];
-  const int64_t C = p.b.C, n_surv = p.b.offset[C], j = blockIdx.x;
-  if (j >= n_surv) return;
+  int64_t slot, m;
+  int len;
+  if (!ring_survivor(p.b, blockIdx.x, &slot, &m, &len)) return;
   const int t = threadIdx.x, nthr = blockDim.x;
   const int S = p.b.S, S2 = S * S, N3 = S2 * S, A3 = 3 * S, T = p.b.T;
   const int64_t L = p.b.L;
-  const int64_t slot = ((p.b.ring[0] - n_surv + j) % C + C) % C;
-  const int64_t m = p.b.offset[slot];
-  const int len = p.b.length[slot];
   const int64_t g = p.groups ? p.groups[m] : m;
   const int8_t* tk = p.tokens + m * p.K * A3;
   const int8_t* st = p.starts + g * T * N3;
@@ -342,21 +270,6 @@ __global__ __launch_bounds__(kBlock) void lists_emit_kernel(ListArgs p) {
   }
 }
 
-__global__ __launch_bounds__(kScanBlock) void lists_scan_kernel(tg_replay_buffer b) {
-  __shared__ int64_t sh[kScanBlock];
-  const int t = threadIdx.x, per = (b.C + kScanBlock - 1) / kScanBlock;
-  const int lo = min(t * per, b.C), hi = min(lo + per, b.C);
-  int64_t sum = 0;
-  for (int s = lo; s < hi; ++s) sum += b.length[s];
-  int64_t total;
-  int64_t run = block_exclusive_scan(sum, sh, &total);
-  for (int s = lo; s < hi; ++s) {
-    b.offset[s] = run;
-    run += b.length[s];
-  }
-  if (t == 0) b.offset[b.C] = total;
-}
-
 }  // namespace rl
 }  // namespace tg
 
@@ -365,14 +278,7 @@ extern "C" int tg_replay_add_lists(const tg_replay_buffer* buf, const int8_t* st
                                    uint8_t* stored, uint32_t* status, tg_stream_t stream) {
   const char* fn = "tg_replay_add_lists";
   if (!buf) return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer", fn);
-  if (buf->C < 1 || buf->C > TG_REPLAY_MAX_CAPACITY)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: C=%d outside [1,%d]", fn, buf->C, TG_REPLAY_MAX_CAPACITY);
-  if (buf->L < 1 || buf->L > TG_REPLAY_MAX_ACTIONS)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: L=%d outside [1,%d]", fn, buf->L, TG_REPLAY_MAX_ACTIONS);
-  if (buf->T < 1 || buf->T > TG_REPLAY_MAX_T)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: T=%d outside [1,%d]", fn, buf->T, TG_REPLAY_MAX_T);
-  if (buf->S < 1 || buf->S > TG_MAX_S)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, buf->S, TG_MAX_S);
+  if (int rc = check_ring_sizes(fn, "", buf)) return rc;
   if (M < 0 || M > INT32_MAX) return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld out of range", fn, (long long)M);
   if (G < 0 || G > INT32_MAX) return tg_internal_fail(TG_ERR_INVALID, "%s: G=%lld out of range", fn, (long long)G);
   if (K < 1 || K > TG_REPLAY_MAX_ACTIONS)
@@ -383,10 +289,7 @@ extern "C" int tg_replay_add_lists(const tg_replay_buffer* buf, const int8_t* st
   if (M == 0) return TG_OK;
   if (!groups && M > G)
     return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld > G=%lld with null groups", fn, (long long)M, (long long)G);
-  if (!buf->frames || !buf->tokens || !buf->rewards || !buf->length || !buf->offset || !buf->ring)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: null buffer array", fn);
-  if (!aligned(buf->rewards, 4) || !aligned(buf->length, 4) || !aligned(buf->offset, 8) || !aligned(buf->ring, 8))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: buffer arrays not aligned to their elements", fn);
+  if (int rc = check_ring_arrays(fn, "", buf)) return rc;
   if ((G > 0 && !starts) || !tokens || !lengths)
     return tg_internal_fail(TG_ERR_INVALID, "%s: null starts, tokens or lengths", fn);
   if (!aligned(lengths, 8) || !aligned(groups, 8) || !aligned(status, 4))
@@ -402,8 +305,8 @@ extern "C" int tg_replay_add_lists(const tg_replay_buffer* buf, const int8_t* st
   if (stored)
     if (int rc = launch(fn, tg::rl::lists_valid_kernel, grid_for(M), small ? block : tg::rl::kValidBlock, 0, st, p))
       return rc;
-  if (int rc = launch(fn, tg::rl::lists_plan_kernel, 1, tg::rl::kScanBlock, 0, st, p)) return rc;
+  if (int rc = launch(fn, tg::rl::lists_plan_kernel, 1, tg::kRingScanBlock, 0, st, p)) return rc;
   if (int rc = launch(fn, tg::rl::lists_emit_kernel, dim3(static_cast<unsigned>(games), chunks), block, lds, st, p))
     return rc;
-  return launch(fn, tg::rl::lists_scan_kernel, 1, tg::rl::kScanBlock, 0, st, *buf);
+  return tg_internal_ring_rebuild(buf, st);
 }

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import replay_ref as RR
+import ring_cases as RC
 from guarded_buffers import check_flat, guarded
 from mat_mul_amd import GameBuffer, SyntheticDemos, TensorGameData, ops, search
 
@@ -164,6 +165,12 @@ def test_ring_wraps_and_skips_like_the_restatement(C, B, calls):
     assert int(buf.status[0]) == bits == 1
     off = buf.offset.cpu().numpy()
     assert np.array_equal(off, np.concatenate([[0], np.cumsum(buf.length.cpu().numpy())]))
+
+
+@pytest.mark.parametrize("C", RC.EDGE_C)
+@pytest.mark.parametrize("N", RC.EDGE_N)
+def test_add_at_the_plan_chunk_and_slot_range_edges(N, C):
+    RC.check_edges("add", N, C, DEV)
 
 
 def test_best_rule_follows_act_step(golden):

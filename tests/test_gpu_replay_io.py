@@ -13,17 +13,17 @@ import torch
 
 import replay_io_ref as IO
 import replay_ref as RR
+import ring_cases as RC
 from guarded_buffers import CANARY, check_flat, guarded
-from mat_mul_amd import FusedTrainer, GameBuffer, SyntheticDemos, TensorGameData, _lib, ops, replay_io, search
+from mat_mul_amd import FusedTrainer, GameBuffer, SyntheticDemos, TensorGameData, ops, replay_io, search
 from net_ref import CONFIGS, make_weights
+from ring_cases import ARRAYS, guarded_buffer
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ARRAYS = ("frames", "tokens", "rewards", "length", "offset", "ring")
 # (C, L, T, S): the aligned path; 27-byte frames (every packed row misaligned); misaligned with T = 3; 729-byte frames;
 # the smallest buffer; two age positions per scan thread with a ragged last thread; the capacity bound
 SHAPES = [(3, 4, 2, 4), (5, 3, 1, 3), (7, 2, 3, 5), (4, 3, 1, 9), (1, 1, 1, 1), (1025, 2, 1, 2), (65536, 1, 1, 1)]
-POISON_F32 = np.frombuffer(bytes([CANARY] * 4), np.float32)[0]
 
 
 def dev(x, dtype=None):
@@ -44,24 +44,6 @@ def dense_games(rng, lengths, T, S):
     M = int(np.maximum(lengths, 0).sum())
     return (rng.integers(-3, 4, size=(M, T, S, S, S)).astype(np.int8), rng.integers(0, 3, size=(M, 3 * S)).astype(np.int8),
             -rng.integers(1, 9, size=M).astype(np.float32))
-
-
-def guarded_buffer(C, L, T, S):
-    """A GameBuffer whose six arrays lie between guard bytes; frames, tokens and rewards are poisoned, so whatever a
-    call leaves outside the stored moves is seen."""
-    buf = GameBuffer(C, L, T, S, DEV)
-    buf.guards = {}
-    for name in ARRAYS:
-        old = getattr(buf, name)
-        raw, t = guarded(tuple(old.shape), old.dtype)
-        if name in ("length", "offset", "ring"):
-            t.zero_()
-        buf.guards[name] = raw
-        setattr(buf, name, t)
-    buf.desc = _lib.ReplayBufferDesc(C, L, T, S, *(getattr(buf, n).data_ptr() for n in ARRAYS))
-    buf.shadow = (np.full((C, L, T, S, S, S), CANARY, np.int8), np.full((C, L, 3 * S), CANARY, np.int8),
-                  np.full((C, L), POISON_F32, np.float32))
-    return buf
 
 
 def mirror(buf, ring):
@@ -279,6 +261,12 @@ def test_add_packed_equals_replay_add_with_one_hot_policies(C, L, T, S):
         IO.add_packed(ring, fr, tk, rw, ln)
         check_buffer(a, ring, ("replay_add", G))  # every valid byte, length, offset and ring: equal to the restatement,
         check_buffer(b, ring, ("add_packed", G))  # and so to each other
+
+
+@pytest.mark.parametrize("C", RC.EDGE_C)
+@pytest.mark.parametrize("N", RC.EDGE_N)
+def test_add_packed_at_the_plan_chunk_and_slot_range_edges(N, C):
+    RC.check_edges("add_packed", N, C, DEV)
 
 
 # ---- GameBuffer: pack, save, load ------------------------------------------------------------------------------------------

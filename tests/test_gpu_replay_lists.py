@@ -2,7 +2,8 @@
 GameBuffer.add_lists, TensorGameData.add_solutions) on the MI355X: bit for bit against the host restatement
 (tests/replay_lists_ref.py) over the sizes, history depths and list lengths at which the kernels take another path; every
 class of invalid list between valid ones; the ring's wrap; the best-list rule; equivalence with the composed path
-(env steps, stacked frames, a one-hot policy, ops.replay_add) on the device; addressing at odd byte offsets between
+(env steps, stacked frames, a one-hot policy, ops.replay_add) on the device; the ring protocol of the three entries that store games (the edges of
+the plan's chunk and of the rebuild's slot ranges, one ring from the three input forms, a folded ring[0]); addressing at odd byte offsets between
 guard bytes; graph capture; and the solution search end to end into the dataset, its batches and a saved run."""
 import ctypes as C
 
@@ -10,9 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+import replay_io_ref as IO
 import replay_lists_ref as LR
 import replay_ref as RR
-from guarded_buffers import CANARY, GUARD
+import ring_cases as RC
+from guarded_buffers import CANARY, GUARD, check_flat
+from ring_cases import assert_ring
 from mat_mul_amd import (FusedTrainer, GameBuffer, SolutionArchive, SyntheticDemos, TensorGameData, TensorGameError, _lib,
                          ops, replay_io, rollout)
 from net_ref import CONFIGS, make_weights
@@ -55,19 +59,6 @@ def make_lists(rng, S, T, K, M, shift, shared):
         n = int(glen[g])
         tokens[m, :n] = own[g, :n] if m % 2 == 0 else own[g, :n][::-1]
     return starts, tokens, lengths, groups
-
-
-def assert_ring(buf, want, what=""):
-    """Every valid byte of the device buffer equals the restatement's ring."""
-    length, offset, ring = host(buf.length), host(buf.offset), host(buf.ring)
-    assert ring.tolist() == [want.pointer, want.added], what
-    assert length.tolist() == [len(want.slots[s][2]) if s in want.slots else 0 for s in range(buf.C)], what
-    assert offset.tolist() == [0] + np.cumsum(length).tolist(), what
-    frames, tokens, rewards = host(buf.frames), host(buf.tokens), host(buf.rewards)
-    for s, (f, t, r) in want.slots.items():
-        n = len(r)
-        assert np.array_equal(frames[s, :n], f) and np.array_equal(tokens[s, :n], t), (what, s)
-        assert np.array_equal(rewards[s, :n].view(np.uint32), r.view(np.uint32)), (what, s)
 
 
 def run_both(buf, want, starts, tokens, lengths, groups, shift, select=False, what=""):
@@ -211,6 +202,67 @@ def test_equals_the_composed_path_on_the_device(S, T, shared):
         for x, y in zip(a.items(idx), b.items(idx)):
             assert torch.equal(x, y)
         assert int(a.status) == int(b.status) == 0
+
+
+# ---- the ring protocol the three entries share (csrc/tg_ring.h) --------------------------------------------------------
+@pytest.mark.parametrize("C", RC.EDGE_C)
+@pytest.mark.parametrize("N", RC.EDGE_N)
+def test_add_lists_at_the_plan_chunk_and_slot_range_edges(N, C):
+    RC.check_edges("add_lists", N, C, DEV)
+
+
+@pytest.mark.parametrize("C, held", [(3, 0), (5, 4)])
+def test_the_three_entries_leave_one_ring(C, held):
+    """The same games as padded states with a one-hot policy, as packed rows and as move lists, each into a zeroed ring
+    of 3 slots and into one of 5 that already holds four games: one ring, whichever entry stored them."""
+    S, T, K = 2, 2, 3
+    rng = np.random.default_rng(C)
+    before = RC.three_forms(*RC.solvable_lists(rng, held, S, T, K), K)["add_packed"] if held else None
+    forms = RC.three_forms(*RC.solvable_lists(rng, 4, S, T, K), K)     # 4 games: both rings wrap
+    want = RR.Ring(C, K)
+    if held:
+        IO.add_packed(want, *before)
+    IO.add_packed(want, *forms["add_packed"])
+    assert want.added == held + 4 and len(want.slots) == C and want.pointer == (held + 4) % C
+    left = {}
+    for entry in RC.ENTRIES:
+        for select in (False, True) if entry != "add_packed" else (False,):
+            buf = RC.guarded_buffer(C, K, T, S, DEV)
+            if held:
+                RC.call_entry("add_packed", buf, before)
+            RC.call_entry(entry, buf, forms[entry], select, buf.status)
+            left[entry, select] = RC.ring_of(buf)
+            for name in RC.ARRAYS:
+                check_flat(buf.guards[name], (entry, select, name))
+            assert int(buf.status) == 0
+    for (entry, select), ring in left.items():                         # (equal to one ring: equal pairwise)
+        other = left["add", select]
+        assert IO.rings_equal(ring, other), (entry, select)
+        if not select:
+            assert IO.rings_equal(ring, want), entry
+    assert left["add", True].added == held + 1                         # the first shortest list = the best final reward
+
+
+@pytest.mark.parametrize("entry", RC.ENTRIES)
+def test_a_ring_pointer_outside_the_ring_is_folded_into_it(entry):
+    """ring[0] outside [0, C) in a caller-owned descriptor: every entry takes it modulo C, so the call equals the one
+    made from the folded value and nothing outside the six arrays is written."""
+    C, N = 5, 7                                                        # 6 valid candidates: the ring wraps
+    args = RC.edge_case(entry, N)
+    for select in (False, True) if entry != "add_packed" else (False,):
+        for raw in (-1, -C - 2, C, 3 * C + 1):
+            want, status, _ = RC.restate(entry, args, C, raw % C, select)
+            assert want.added == (1 if select else 6) and status
+            bufs = [RC.guarded_buffer(C, RC.L, RC.T, RC.S, DEV) for _ in (0, 1)]
+            for buf, first in zip(bufs, (raw, raw % C)):
+                buf.ring[0] = first
+                RC.call_entry(entry, buf, args, select, buf.status)
+                assert_ring(buf, want, (select, raw, first))
+                for name in RC.ARRAYS:
+                    check_flat(buf.guards[name], (select, raw, first, name))
+            for name in RC.ARRAYS + ("status",):                       # the poison outside the stored moves included
+                x, y = getattr(bufs[0], name), getattr(bufs[1], name)
+                assert torch.equal(x.view(torch.uint8), y.view(torch.uint8)), (select, raw, name)
 
 
 # ---- addressing ------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import pytest
 import replay_io_ref as IO
 import replay_lists_ref as LR
 import replay_ref as RR
+import ring_cases as RC
 from mat_mul_amd import _lib, build
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -172,6 +173,22 @@ def test_restatement_equals_replay_add_on_the_padded_form(select):
         st, po, rw, ln = LR.padded_form(starts, tokens[valid], lengths[valid], groups[valid], K + 1, shift, 3 + shift)
         padded.add(st, po, rw, ln, select=select)
         assert IO.rings_equal(padded, ring) and ring.added == (1 if select else int(valid.sum()))
+
+
+@pytest.mark.parametrize("entry", RC.ENTRIES)
+def test_ring_edge_cases_store_and_reject_in_every_combination(entry):
+    """The cases tests/ring_cases.py gives the three GPU files, on the restatement alone: every combination stores at
+    least one game and rejects at least one, so none of them passes vacuously on the device."""
+    for N in RC.EDGE_N:
+        args = RC.edge_case(entry, N)
+        valid = N - len(range(3, N, 7))
+        for C in RC.EDGE_C:
+            for first in RC.edge_starts(C):
+                for select in (False, True) if entry != "add_packed" else (False,):
+                    ring, status, stored = RC.restate(entry, args, C, first, select)
+                    assert status and ring.added == (1 if select else valid), (N, C, first, select)
+                    assert len(ring.slots) == min(ring.added, C) and ring.pointer == (first + ring.added) % C
+                    assert stored is None or stored.sum() == ring.added
 
 
 def test_restated_edges():
