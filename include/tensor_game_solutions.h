@@ -35,7 +35,8 @@
  *      are zero bytes (the padding RolloutResult.solutions() uses).
  *   The sum of the canonical terms equals the sum of the original terms.  The form does not depend on the order of the
  *   input terms, on how signs were distributed inside a term, or on inserted null terms or cancelling pairs.  Two things
- *   are NOT factored out: rescalings between factors, such as (2u) (x) v = u (x) (2v), and symmetries of the target.
+ *   are NOT factored out here: rescalings between factors, such as (2u) (x) v = u (x) (2v), and symmetries of the target
+ *   (tg_orbit_canon, tensor_game_orbits.h, factors out a set of symmetries the caller supplies).
  *
  * Key.  The n = rank * 3S canonical token bytes are read as one byte stream, zero-padded to 8-byte little-endian words
  *   w_k:  key = fmix64( (sum_k fmix64(w_k + (k+1)*0x9E3779B97F4A7C15)) ^ (n * 0xC2B2AE3D27D4EB4F) ), which is

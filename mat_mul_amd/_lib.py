@@ -203,6 +203,16 @@ BASES_SIGNATURES = {
 # status bits of include/tensor_game_bases.h (the limits are TG_MAX_S, TG_SOL_MAX_K and TG_SOL_MAX_SHIFT)
 TG_BASIS_BAD_DIAGONAL, TG_BASIS_BAD_RANGE = 1, 2
 TG_REBASE_BAD_LENGTH, TG_REBASE_BAD_INDEX, TG_REBASE_BAD_RANGE = 1, 2, 4
+# name -> argtypes; every symbol include/tensor_game_orbits.h declares
+ORBIT_SIGNATURES = {
+    "tg_orbit_check": [_i64, _i, _i, _i, _i],
+    "tg_orbit_workspace_size": [_i64, _i, _i, _i, _p],
+    "tg_orbit_fixes": [_p, _i64, _i, _p, _i, _p, _p, _p],
+    "tg_orbit_canon": [_p, _p, _p, _i64, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
+}
+# limits and status bits of include/tensor_game_orbits.h
+TG_ORBIT_MAX_G, TG_ORBIT_MAX_ROW = 2048, 24576
+TG_ORBIT_BAD_LENGTH, TG_ORBIT_BAD_NEGATION, TG_ORBIT_BAD_GROUP = 1, 2, 4
 # flags of tg_symmetry_sample (include/tensor_game_symmetry.h)
 TG_SYM_MODES, TG_SYM_PERMS, TG_SYM_SIGNS = 1, 2, 4
 TG_ROLLOUT_MAX_SLOTS = 65536
@@ -262,7 +272,8 @@ def _load() -> C.CDLL:
                            **NET_SIGNATURES, **NET_S25_SIGNATURES, **TRAIN_SIGNATURES, **TRAIN_SLICED_SIGNATURES,
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
-                           **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES}.items():
+                           **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
+                           **ORBIT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

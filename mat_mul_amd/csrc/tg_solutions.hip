@@ -22,6 +22,7 @@
 #include "../../include/tensor_game_solutions.h"
 #include "tg_host.h"
 #include "tg_sol_copy.h"
+#include "tg_sol_phases.h"
 
 namespace tg {
 
@@ -38,58 +39,6 @@ struct SolArgs {
   int K, S, shift;
   int img;                 // bytes of one LDS image: K * 3S rounded up to 16
 };
-
-constexpr int kSolWRow = TG_MAX_S;  // bytes per term of the verifier's padded copy of the w tokens
-
-// the workgroup's sum of x (uniform result); `red` holds NT words
-template <int NT>
-__device__ __forceinline__ uint64_t sol_block_sum(uint64_t x, uint64_t* red, int t) {
-  red[t] = x;
-  __syncthreads();
-#pragma unroll
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const uint64_t r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// The number of non-zero entries of target - sum_r u (x) v (x) w over this thread's rows (i, j), for S <= 8 * CH.
-// |p| <= 192^2 and a token is an int8, so both products are exact 24-bit multiplies; |sum p * w| <= 256 * 192^2 * 128
-// and |shift * sum p| <= 64 * 256 * 192^2 stay below 2^31, and their difference is the exact sum of the terms.
-template <int NT, int CH>
-__device__ __forceinline__ int sol_residual_nnz(const int8_t* tok, const int8_t* wq, const int8_t* target, int L, int S,
-                                                int shift, int t) {
-  const int A3 = 3 * S;
-  int nnz = 0;
-  for (int ij = t; ij < S * S; ij += NT) {
-    const int i = ij / S, j = ij - i * S;
-    int acc[8 * CH] = {};
-    int psum = 0;
-    for (int r = 0; r < L; ++r) {
-      const int8_t* row = tok + r * A3;
-      const int p = mul24_pinned(row[i] - shift, row[S + j] - shift);
-      psum += p;
-      const uint2* w = reinterpret_cast<const uint2*>(wq + r * kSolWRow);
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const uint2 q = w[c];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          acc[8 * c + k] = mad24_pinned(p, sbyte(q.x, k), acc[8 * c + k]);
-          acc[8 * c + 4 + k] = mad24_pinned(p, sbyte(q.y, k), acc[8 * c + 4 + k]);
-        }
-      }
-    }
-    const int off = shift * psum;
-#pragma unroll
-    for (int e = 0; e < 8 * CH; ++e)
-      if (e < S) nnz += (target[ij * S + e] - (acc[e] - off)) != 0;
-  }
-  return nnz;
-}
 
 // a bad row: zero canon row, rank 0, key 0, residual -1, the status bit
 template <int NT>

@@ -15,6 +15,7 @@
 
 #include "../../include/tensor_game_symmetry.h"
 #include "tg_items.h"
+#include "tg_sym_code.h"
 
 namespace tg {
 
@@ -30,13 +31,6 @@ struct SymArgs {
   int T, S, shift;
   int img;             // bytes of LDS per team: S^3 + 16, rounded up to 16
 };
-
-constexpr int kSymNeg = 1 << 16;
-// rho[m] of the mode permutation `code` (lexicographic rank): six codes x three modes x two bits
-constexpr uint64_t kRho = (0ull | 1ull << 2 | 2ull << 4) | (0ull | 2ull << 2 | 1ull << 4) << 6 |
-                          (1ull | 0ull << 2 | 2ull << 4) << 12 | (1ull | 2ull << 2 | 0ull << 4) << 18 |
-                          (2ull | 0ull << 2 | 1ull << 4) << 24 | (2ull | 1ull << 2 | 0ull << 4) << 30;
-__device__ __forceinline__ int rho_of(int code, int m) { return static_cast<int>(kRho >> (6 * code + 2 * m)) & 3; }
 
 // One input frame (N3 bytes at src, any alignment) into LDS: 16-byte loads between the first and the last 16-byte
 // boundary of src, bytes before and after.  img is 16-byte aligned with N3 + 16 bytes; entry e lands at img[pad + e],

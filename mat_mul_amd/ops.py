@@ -32,6 +32,7 @@ __all__ = [
     "RolloutSlots", "rollout_slots", "rollout_advance_slots", "rollout_refill",
     "symmetry_sample", "symmetry_apply",
     "solution_check", "solution_canon",
+    "orbit_check", "orbit_fixes", "orbit_workspace_size", "orbit_canon",
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
 ]
 
@@ -665,6 +666,102 @@ def solution_canon(targets, tokens, lengths, shift: int = 1, canon=None, rank=No
     _launch(dev, "tg_solution_canon", _ptr(targets), _ptr(tokens), _ptr(lengths), M, K, S, int(shift), _ptr(canon),
             _ptr(rank), _ptr(key), _ptr(residual_nnz), _ptr(status))
     return canon, rank, key, residual_nnz
+
+
+def orbit_check(M: int, K: int, S: int, shift: int = 1, G: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_orbit_canon takes these sizes.  Host only."""
+    call("tg_orbit_check", int(M), int(K), int(S), int(shift), int(G))
+
+
+def _group_rows(sym, S: int, dev, fn: str) -> torch.Tensor:
+    """The set of group elements of the orbit entries: contiguous uint8 (G,3S+1) on ``dev``."""
+    _need_gpu(sym, "sym")
+    if sym.dtype != torch.uint8 or sym.dim() != 2 or sym.shape[1] != 3 * S + 1 or sym.shape[0] < 1:
+        raise TensorGameError(fn, -1, f"sym must be uint8 (G,{3 * S + 1}) with G >= 1, got {sym.dtype} {tuple(sym.shape)}")
+    return _flag(sym, tuple(sym.shape), torch.uint8, dev, "sym")
+
+
+def orbit_fixes(targets, sym, fixes=None, status=None) -> torch.Tensor:
+    """Whether every element of a set fixes each target, in one launch (include/tensor_game_orbits.h).  targets int8
+    (M,S,S,S); sym uint8 (G,3S+1) in the encoding of ``symmetry_sample``.  Returns fixes uint8 (M,): 1 where
+    ``symmetry_apply(target, g) == target`` for every row g.  A bad row of ``sym`` (mode code above 5, an index >= S)
+    sets bit 0 of ``status`` uint32 (1,) and makes every flag 0.  No host sync."""
+    fn = "orbit_fixes"
+    _need_gpu(targets, "targets")
+    if targets.dtype != torch.int8 or targets.dim() != 4 or not (targets.shape[1] == targets.shape[2] == targets.shape[3]):
+        raise TensorGameError(fn, -1, f"targets must be int8 (M,S,S,S), got {targets.dtype} {tuple(targets.shape)}")
+    M, S, dev = targets.shape[0], targets.shape[1], targets.device
+    targets = targets if targets.is_contiguous() else targets.contiguous()
+    sym = _group_rows(sym, S, dev, fn)
+    fixes = _out(fixes, (M,), torch.uint8, dev, "fixes")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_orbit_fixes", _ptr(targets), M, S, _ptr(sym), sym.shape[0], _ptr(fixes), _ptr(status))
+    return fixes
+
+
+def orbit_workspace_size(M: int, K: int, S: int, G: int) -> int:
+    """Bytes of workspace with which ``orbit_canon`` spreads the set over several workgroups per list (0: it does not)."""
+    n = C.c_int64(0)
+    call("tg_orbit_workspace_size", int(M), int(K), int(S), int(G), C.byref(n))
+    return int(n.value)
+
+
+def orbit_canon(targets, tokens, lengths, sym, shift: int = 1, canon=None, rank=None, key=None, residual_nnz=None,
+                which=None, stab=None, status=None, workspace=None):
+    """``solution_canon`` modulo a set of symmetries (include/tensor_game_orbits.h): per list the smallest canonical
+    form over g.X, g a row of ``sym`` uint8 (G,3S+1).  Arguments and the first four results as ``solution_canon``
+    (the residual is that of the ORIGINAL list); then which int32 (M,): the smallest row index attaining the minimum,
+    and stab int32 (M,): how many rows attain it.  ``status`` uint32 (1,) gets bit 0 for a bad length, bit 1 for a token
+    that leaves int8 under some g, bit 2 for a bad row of ``sym`` (every list is bad then); a bad list is all zero with
+    rank 0, key 0, residual_nnz -1, which -1, stab 0.  ``workspace``: None allocates what ``orbit_workspace_size`` asks
+    for (uint8, a small batch is then spread over the device: two launches), False uses none (one launch), or a uint8
+    tensor of that size.  The outputs do not depend on it.  No host sync."""
+    fn = "orbit_canon"
+    _need_gpu(tokens, "tokens")
+    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+    dev = tokens.device
+    sym = _group_rows(sym, S, dev, fn)
+    G = sym.shape[0]
+    orbit_check(M, K, S, shift, G)
+    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+    if targets is not None:
+        _need_gpu(targets, "targets")
+        if targets.dtype != torch.int8 or tuple(targets.shape) != (M, S, S, S) or targets.device != dev:
+            raise TensorGameError(fn, -1, f"targets must be int8 {(M, S, S, S)} on {dev}, got {targets.dtype} "
+                                          f"{tuple(targets.shape)} on {targets.device}")
+        targets = targets if targets.is_contiguous() else targets.contiguous()
+    elif residual_nnz is not None:
+        raise TensorGameError(fn, -1, "residual_nnz needs targets")
+    _need_gpu(lengths, "lengths")
+    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
+        raise TensorGameError(fn, -1, "lengths must be given")
+    canon = _out(canon, (M, K, 3 * S), torch.int8, dev, "canon")
+    rank = _out(rank, (M,), torch.int32, dev, "rank")
+    key = _out(key, (M,), torch.int64, dev, "key")
+    if targets is not None:
+        residual_nnz = _out(residual_nnz, (M,), torch.int32, dev, "residual_nnz")
+    which = _out(which, (M,), torch.int32, dev, "which")
+    stab = _out(stab, (M,), torch.int32, dev, "stab")
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    if workspace is False:
+        workspace = None
+    else:
+        with torch.cuda.device(dev):  # the plan follows the device the launch goes to
+            need = orbit_workspace_size(M, K, S, G)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+        else:
+            _need_gpu(workspace, "workspace")
+            if workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < need or workspace.device != dev \
+                    or not workspace.is_contiguous():
+                raise TensorGameError(fn, -1, f"workspace must be contiguous uint8 of at least {need} bytes on {dev}")
+            workspace = workspace if need else None
+    _launch(dev, "tg_orbit_canon", _ptr(targets), _ptr(tokens), _ptr(lengths), M, K, S, int(shift), _ptr(sym), G,
+            _ptr(canon), _ptr(rank), _ptr(key), _ptr(residual_nnz), _ptr(which), _ptr(stab), _ptr(status), _ptr(workspace),
+            0 if workspace is None else workspace.numel())
+    return canon, rank, key, residual_nnz, which, stab
 
 
 def basis_inverse_check(N: int, S: int) -> None:
