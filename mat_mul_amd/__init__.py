@@ -17,9 +17,10 @@ __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameE
            "shard_range", "SearchForest", "search", "GameBuffer", "TensorGameData", "replay",
            "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
-           "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits"]
+           "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits",
+           "FlipWalks", "reduce_archive", "flips"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -46,6 +47,8 @@ _ATTRS = {
     "BasisSet": "bases",
     "solve_in_bases": "bases",
     "SymmetryGroup": "orbits",
+    "FlipWalks": "flips",
+    "reduce_archive": "flips",
 }
 
 

@@ -213,6 +213,15 @@ ORBIT_SIGNATURES = {
 # limits and status bits of include/tensor_game_orbits.h
 TG_ORBIT_MAX_G, TG_ORBIT_MAX_ROW = 2048, 24576
 TG_ORBIT_BAD_LENGTH, TG_ORBIT_BAD_NEGATION, TG_ORBIT_BAD_GROUP = 1, 2, 4
+# name -> argtypes; every symbol include/tensor_game_flips.h declares
+FLIP_SIGNATURES = {
+    "tg_flip_check": [_i64, _i64, _i, _i, _i, _i, _i64, _i64],
+    "tg_flip_begin": [_p, _p, _i64, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "tg_flip_advance": [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _i64, _p],
+}
+# limits and status bits of include/tensor_game_flips.h
+TG_FLIP_MAX_K, TG_FLIP_MAX_BOUND, TG_FLIP_MAX_STEPS = 128, 63, 65536
+TG_FLIP_BAD_LENGTH, TG_FLIP_BAD_RANGE, TG_FLIP_BAD_SRC = 1, 2, 4
 # flags of tg_symmetry_sample (include/tensor_game_symmetry.h)
 TG_SYM_MODES, TG_SYM_PERMS, TG_SYM_SIGNS = 1, 2, 4
 TG_ROLLOUT_MAX_SLOTS = 65536
@@ -273,7 +282,7 @@ def _load() -> C.CDLL:
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
-                           **ORBIT_SIGNATURES}.items():
+                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

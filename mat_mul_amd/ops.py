@@ -34,6 +34,7 @@ __all__ = [
     "solution_check", "solution_canon",
     "orbit_check", "orbit_fixes", "orbit_workspace_size", "orbit_canon",
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
+    "flip_check", "flip_begin", "flip_advance",
 ]
 
 
@@ -1621,3 +1622,74 @@ def rollout_refill(slots: RolloutSlots, states, scalars, out, seed: int = 0, fir
             *map(_ptr, slots.records), _ptr(slots.actions), _ptr(slots.active), _ptr(slots.slot_state),
             _ptr(slots.slot_step), *map(_ptr, out), _ptr(slots.rows), _ptr(slots.uniforms if uniforms else None),
             _ptr(slots.live), B, int(slots.n), S, T, dim_s, K)
+
+
+def flip_check(M: int, W: int, K: int, S: int, shift: int = 1, bound: int = 1, step0: int = 0, n_steps: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_flip_begin / tg_flip_advance take these sizes.  Host only."""
+    call("tg_flip_check", int(M), int(W), int(K), int(S), int(shift), int(bound), int(step0), int(n_steps))
+
+
+_FLIP_STATE = (("cur", torch.int8), ("cur_rank", torch.int32), ("best", torch.int8), ("best_rank", torch.int32),
+               ("best_step", torch.int64), ("flips", torch.int64), ("state", torch.int32))
+
+
+def _flip_state(given: dict, W: int, K: int, S: int, dev, fn: str) -> dict:
+    """The seven walk-state tensors of include/tensor_game_flips.h on ``dev``: ``given[name]`` held to the rule of
+    ``_flag``, or allocated where it is None."""
+    out = {}
+    for name, dtype in _FLIP_STATE:
+        shape = (W, K, 3 * S) if dtype == torch.int8 else (W,)
+        t = given.get(name)
+        if t is not None:
+            _need_gpu(t, name)
+        out[name] = _out(t, shape, dtype, dev, name)
+    return out
+
+
+def flip_begin(tokens, lengths, src=None, bound: int = 1, shift: int = 1, status=None, **state):
+    """Start W flip-graph walks in one launch (include/tensor_game_flips.h).  tokens int8 (M,K,3S) and lengths int64 (M,)
+    as ``solutions()`` or an archive's ``entries()`` give them; ``src`` int64 (W,): the list walk w starts from (None:
+    walk w starts from list w).  Each list loses its null terms, is brought to stored form and reduced.  Returns the walk
+    state, a dict of device tensors: cur, best int8 (W,K,3S); cur_rank, best_rank, state int32 (W,); best_step, flips
+    int64 (W,) (any of them may be passed in by name).  A bad row (length outside [0,K]: bit 0 of ``status`` uint32 (1,);
+    a factor value outside [-bound,bound]: bit 1; a ``src`` outside [0,M): bit 2) gets state -1.  No host sync."""
+    fn = "flip_begin"
+    _need_gpu(tokens, "tokens")
+    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+    dev = tokens.device
+    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+    _need_gpu(lengths, "lengths")
+    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
+        raise TensorGameError(fn, -1, "lengths must be given")
+    W = M
+    if src is not None:
+        _need_gpu(src, "src")
+        if src.dim() != 1:
+            raise TensorGameError(fn, -1, f"src must be int64 (W,), got {tuple(src.shape)}")
+        W = src.shape[0]
+        src = _flag(src, (W,), torch.int64, dev, "src")
+    flip_check(M, W, K, S, shift, bound)
+    st = _flip_state(state, W, K, S, dev, fn)
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_flip_begin", _ptr(tokens), _ptr(lengths), M, _ptr(src), W, K, S, int(shift), int(bound),
+            *[_ptr(st[name]) for name, _ in _FLIP_STATE], _ptr(status))
+    return st
+
+
+def flip_advance(st: dict, n_steps: int, bound: int = 1, shift: int = 1, seed: int = 0, walk0: int = 0, step0: int = 0):
+    """``n_steps`` steps (at most TG_FLIP_MAX_STEPS) of the walks ``st`` (the dict ``flip_begin`` returned) in place, in
+    one launch: steps step0 .. step0 + n_steps - 1 of the walks with global ids walk0 .. walk0 + W - 1, drawn from Philox
+    keyed by (seed, id, step).  Walks of state 1 (stuck) or -1 (bad) are left alone.  Returns ``st``.  No host sync."""
+    fn = "flip_advance"
+    cur = st["cur"]
+    _need_gpu(cur, "cur")
+    if cur.dtype != torch.int8 or cur.dim() != 3 or cur.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"cur must be int8 (W,K,3S), got {cur.dtype} {tuple(cur.shape)}")
+    W, K, S = cur.shape[0], cur.shape[1], cur.shape[2] // 3
+    flip_check(0, W, K, S, shift, bound, step0, n_steps)
+    st = _flip_state({name: st[name] for name, _ in _FLIP_STATE}, W, K, S, cur.device, fn)
+    _launch(cur.device, "tg_flip_advance", *[_ptr(st[name]) for name, _ in _FLIP_STATE], W, K, S, int(shift), int(bound),
+            C.c_uint64(_u64(seed)), C.c_uint64(_u64(walk0)), int(step0), int(n_steps))
+    return st

@@ -23,7 +23,8 @@ factorisation and its images under the target's symmetries are ONE entry, and ``
 
 Not factored out: rescalings between the factors of a term, and symmetries of the target outside the group the caller
 supplied (without a group: none of the target's symmetries), so two entries can still be the same factorisation up to
-those.  Archives of several GPUs are not merged.
+those.  Archives of several GPUs are not merged.  The archive itself does not improve an entry; ``reduce_archive``
+(mat_mul_amd/flips.py) walks the flip graph from every entry and adds what got shorter through ``add``.
 """
 from __future__ import annotations
 

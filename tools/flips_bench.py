@@ -1,0 +1,145 @@
+"""tg_flip_advance (include/tensor_game_flips.h): time per step, and how far walks get.
+
+    python tools/flips_bench.py OUT_DIR [--reps 5] [--warmup 1] [--hist-steps 100000]
+    python tools/flips_bench.py OUT_DIR --resources      (no GPU: where the library was built, its objects are at hand)
+
+One process, one GPU.  Starting lists: the standard algorithms of <2,2,2> (S=4, K=8), <3,3,3> (S=9, K=27) and <4,4,4>
+(S=16, K=64), bound 1, shift 1.  Timing: W in {256, 4 096, 65 536} walks from one list, n_steps = 4 096 per launch;
+every repetition starts again from the begin state (so all repetitions do the same work; the copy is outside the
+events) and is timed with HIP events around the one launch, after warm-up: median, p10, p90 in microseconds, ns per step
+per walk (over the steps walks really took: a stuck walk takes none), aggregate steps per second, and the accepted
+share.  Histogram: ``best_rank`` over 4 096 walks after ``--hist-steps`` steps from each start.  Also records the
+kernels' VGPRs, LDS and scratch from the code object.  Writes OUT_DIR/flips_bench.json.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import re
+import statistics
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+from mat_mul_amd import FlipWalks, build, ops  # noqa: E402
+
+DEV = "cuda:0"
+N_STEPS = 4096
+
+
+def standard_matmul(n, shift=1):
+    """The n^3 terms a_ij (x) b_jk (x) c_ik of <n,n,n> as tokens (K = n^3 rows)."""
+    S = n * n
+    rows = np.zeros((n ** 3, 3 * S), dtype=np.int64)
+    t = 0
+    for i in range(n):
+        for j in range(n):
+            for k in range(n):
+                rows[t, i * n + j] = rows[t, S + j * n + k] = rows[t, 2 * S + i * n + k] = 1
+                t += 1
+    return (rows + shift).astype(np.int8)
+
+
+def stats(ts):
+    ts = sorted(ts)
+    q = lambda f: ts[min(len(ts) - 1, int(f * len(ts)))]  # noqa: E731
+    return {"median_us": statistics.median(ts), "p10_us": q(0.1), "p90_us": q(0.9), "reps": len(ts)}
+
+
+def kernel_resources():
+    """VGPRs, LDS and scratch of the flip kernels, from the metadata of the built object."""
+    obj = build.OBJ_DIR / "tg_flips.o"
+    llvm = Path("/opt/rocm/llvm/bin")
+    out = {}
+    if not obj.exists():  # a tree that received the library without its objects
+        return {"error": f"{obj.name} is not here: run `python tools/flips_bench.py --resources` where the library was built"}
+    with tempfile.TemporaryDirectory() as tmp:
+        fat, co = Path(tmp) / "fat", Path(tmp) / "co"
+        try:
+            subprocess.run([llvm / "llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, Path(tmp) / "discard.o"], check=True)
+            subprocess.run([llvm / "clang-offload-bundler", "--unbundle", "--type=o",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
+            notes = subprocess.run([llvm / "llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
+        except (OSError, subprocess.CalledProcessError) as e:
+            return {"error": str(e)}
+    for block in notes.split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block)
+        if name:
+            out[name.group(1)] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
+                                  for k in ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size",
+                                            "vgpr_spill_count", "sgpr_spill_count")}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--resources", action="store_true", help="only (re)write the kernels' resources into OUT_DIR/flips_bench.json; no GPU")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--hist-steps", type=int, default=100000)
+    ap.add_argument("--walks", type=int, nargs="*", default=[256, 4096, 65536])
+    args = ap.parse_args()
+    out = Path(args.out) / "flips_bench.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    if args.resources:
+        res = json.loads(out.read_text()) if out.exists() else {}
+        res["resources"] = kernel_resources()
+        out.write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res["resources"], indent=1))
+        return
+    res = {"torch": torch.__version__, "device": torch.cuda.get_device_name(0), "n_steps": N_STEPS, "resources": kernel_resources(),
+           "rows": [], "histograms": []}
+    for n in (2, 3, 4):
+        S, K = n * n, n ** 3
+        tokens = torch.from_numpy(standard_matmul(n)[None]).to(DEV)
+        lengths = torch.tensor([K], dtype=torch.int64, device=DEV)
+        for W in args.walks:
+            walks = FlipWalks.start(tokens, lengths, walks_per_list=W, bound=1, shift=1, seed=1)
+            begin = {k: v.clone() for k, v in walks._st.items()}
+            ts = []
+            for rep in range(args.warmup + args.reps):
+                for k, v in begin.items():
+                    walks._st[k].copy_(v)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                ops.flip_advance(walks._st, N_STEPS, bound=1, shift=1, seed=1)
+                b.record()
+                b.synchronize()
+                if rep >= args.warmup:
+                    ts.append(a.elapsed_time(b) * 1e3)
+            st = stats(ts)
+            # steps really taken: a list can only lose its last match in a step that lowers the rank, so a stuck walk took
+            # best_step steps and one more that found no match
+            stuck = walks.state == 1
+            taken = int(torch.where(stuck, walks.best_step + 1, torch.full_like(walks.best_step, N_STEPS)).sum())
+            row = {"n": n, "S": S, "K": K, "W": W, **st, "steps_taken": taken,
+                   "ns_per_step_per_walk": st["median_us"] * 1e3 / max(taken, 1),
+                   "steps_per_s": taken / (st["median_us"] * 1e-6), "accepted_share": float(walks.flips.sum()) / max(taken, 1),
+                   "stuck_walks": int(stuck.sum()), "min_best_rank": int(walks.best_rank.min())}
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+        walks = FlipWalks.start(tokens, lengths, walks_per_list=4096, bound=1, shift=1, seed=2)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        walks.advance(args.hist_steps)
+        b.record()
+        b.synchronize()
+        ranks, counts = torch.unique(walks.best_rank, return_counts=True)
+        hist = {"n": n, "S": S, "K": K, "W": 4096, "steps": args.hist_steps, "seconds": a.elapsed_time(b) * 1e-3,
+                "best_rank": {int(r): int(c) for r, c in zip(ranks.cpu(), counts.cpu())}, "stuck_walks": int((walks.state == 1).sum())}
+        res["histograms"].append(hist)
+        print(json.dumps(hist), flush=True)
+        out.write_text(json.dumps(res, indent=1) + "\n")
+    out.write_text(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
