@@ -1,10 +1,12 @@
 """CPU checks of the flip-graph walks (include/tensor_game_flips.h): the header, the exported symbols, the size checks and
 the refusals of the host side of the library, and the host restatement's own invariants -- every step keeps the exact sum,
-the bound and the stored form, the rank never rises, and from the standard <2,2,2> list walks reach Strassen's rank."""
+the bound and the stored form, the rank never rises, and from the standard <2,2,2> list walks reach Strassen's rank;
+and that the gadget lists of flips_ref.py reach the rule events their slots name, which test_gpu_flips.py relies on."""
 import ctypes as C
 import re
 import shutil
 import subprocess
+from collections import Counter
 from pathlib import Path
 
 import numpy as np
@@ -206,3 +208,84 @@ def test_begin_restated_drops_normalises_and_reduces():
         assert status3 == bit and (st3["state"] == -1).sum() == (2 if src else 1) and not st3["cur"][st3["state"] == -1].any()
     tokens[0, 0, 0] = 2 + shift                                        # a value outside the bound, in a null term
     assert FR.begin(tokens, [7], None, 1, shift)[1] == FR.BAD_RANGE
+
+
+# ---- the gadget lists reach the rule events their slots name ---------------------------------------------------------
+def test_event_counters_change_nothing():
+    tokens, L = FR.pool_list(np.random.default_rng(1), 5, 20, 17, 3, 2)
+    plain, _ = FR.begin(tokens[None], [L], np.zeros(3, dtype=np.int64), 2, 2)
+    counted = FR.copy_state(plain)
+    events = Counter()
+    FR.advance(plain, 4, 0, 0, 60, 2, 2)
+    FR.advance(counted, 4, 0, 0, 60, 2, 2, events=events)
+    for k in FR.STATE_NAMES:
+        assert np.array_equal(plain[k], counted[k]), k
+    assert set(events) <= set(FR.EVENTS) and events["accepted"] == plain["flips"].sum() > 0
+
+
+def test_gadget_list_is_inert_but_for_its_gadgets():
+    S, K, L, bound = FR.GADGET_S, 128, 100, FR.GADGET_BOUND
+    slots = (64, 99, 98, 3, 63, 65, 97, 96)
+    tokens, L = FR.gadget_list(np.random.default_rng(0), S, K, L, bound, bound, slots[:2], slots[2:4], slots[4:])
+    terms = FR.from_rows(tokens, L, S, bound)
+    ms = FR.matches(terms)
+    assert ms and all(i in slots and j in slots for i, j, _ in ms)                    # every match is between gadgets
+    assert sorted(m for i, j, m in ms if (i, j) == (64, 99)) == [0, 1, 2]             # the duplicate shares all three
+    assert [m for i, j, m in ms if (i, j) == (3, 98)] == [0]                          # the hidden pair: mode 0 alone
+    before = [list(t) for t in terms]
+    FR.reduce(terms, bound)
+    assert terms == before                                                            # begin's reduce merges nothing
+    assert np.abs(tokens[:L].astype(int) - bound).max() == bound and not tokens[L:].any()
+
+
+@pytest.mark.parametrize("name", list(FR.GADGET_CASES))
+def test_gadget_walks_reach_the_events_of_their_slots(name):
+    K, L, dup, hidden, quad, W, n_steps, by_slots = FR.GADGET_CASES[name]
+    assert W <= 64 or L <= 64
+    tokens, L, W, n_steps, st, events = FR.gadget_ref(name)
+    print(name, {k: events[k] for k in FR.EVENTS})
+    for e in FR.ALWAYS + by_slots:
+        assert events[e] >= FR.MIN_EVENTS, (e, events[e])
+    # both derived from the rules (NOTES.md): after a reduce no flip can null both terms, and a pair that cancels
+    # inside a walk is the pair the flip just wrote
+    assert events["null_both"] == 0 and events["cancel_with_third"] == 0
+    total = FR.term_sum(tokens, L, FR.GADGET_S, FR.GADGET_BOUND)
+    for w in range(W):
+        assert np.array_equal(FR.term_sum(st["cur"][w], st["cur_rank"][w], FR.GADGET_S, FR.GADGET_BOUND), total)
+        assert np.array_equal(FR.term_sum(st["best"][w], st["best_rank"][w], FR.GADGET_S, FR.GADGET_BOUND), total)
+
+
+def test_gadget_cases_cover_the_placements():
+    """Every slot pattern the kernel's two-terms-per-lane layout distinguishes is in some case."""
+    cases = list(FR.GADGET_CASES.values())
+    assert {(K, L) for K, L, *_ in cases} == {(8, 8), (64, 64), (128, 128), (128, 100)}
+    dups = {(d, L) for _, L, d, *_ in cases}
+    assert any(d == (0, 1) for d, L in dups) and any(d == (0, L - 1) for d, L in dups)
+    assert any(d == (L - 2, L - 1) for d, L in dups) and {((63, 64), 128), ((62, 127), 128)} <= dups
+    assert any(d == (64, L - 1) for d, L in dups)
+    hidden = [(min(h), max(h), L) for _, L, _, h, *_ in cases]
+    assert any(lo < 64 <= hi for lo, hi, L in hidden) and any(lo >= 64 for lo, hi, L in hidden)
+    assert any(hi == L - 2 and L > 64 for lo, hi, L in hidden) and any(hi == L - 2 and L <= 64 for lo, hi, L in hidden)
+
+
+@pytest.mark.parametrize("K", list(FR.ANTIPAIR_CASES))
+def test_only_a_hand_written_unreduced_list_reaches_both_null(K):
+    st, want, events = FR.antipair_ref(K)
+    print(K, {k: events[k] for k in FR.EVENTS})
+    n = FR.ANTIPAIR_WALKS
+    for c, (L, p0, p1) in enumerate(FR.ANTIPAIR_CASES[K]):
+        rows = slice(c * n, (c + 1) * n)
+        # the walks whose one accepted flip removed the pair (two flips: the pair was doubled and cancelled later)
+        both = (want["cur_rank"][rows] == L - 2) & (want["flips"][rows] == 1)
+        assert both.sum() >= 4 and (want["state"][rows][both] == 1).all()
+        start = st["cur"][c * n]
+        # the higher slot first: the last term into p1, then the new last into p0.  (Removing p0 first would give other
+        # rows, unless p1 is slot L-2: the inert terms are pairwise different.)
+        moved = start.copy()
+        for p in (p1, p0):
+            L -= 1
+            moved[p] = moved[L]
+            moved[L] = 0
+        for w in np.flatnonzero(both):
+            assert np.array_equal(want["cur"][rows][w], moved)
+    assert events["null_both"] >= FR.MIN_EVENTS

@@ -1,7 +1,9 @@
 """GPU checks of the flip-graph walks (include/tensor_game_flips.h): ``ops.flip_begin`` and ``ops.flip_advance`` bit for
 bit against the host restatement (flips_ref.py) on unaligned, canary-guarded buffers; continuation, sharding, stuck and
 bad walks; the exact proof of every walk's best list, which does not go through the restatement; ``FlipWalks`` and
-``reduce_archive``."""
+``reduce_archive``; gadget lists that reach the rule events plausible lists do not (null terms, cancels, merges, moves
+between a lane's two slots); S = 16, 25, 32 and S < 4; more walks than workgroups; the Philox words and step tails; the
+cur_rank guard and graph capture."""
 import io
 
 import numpy as np
@@ -81,18 +83,19 @@ def gpu_advance(g, n_steps, bound, shift, seed, walk0=0, step0=0):
     return to_np(g.st)
 
 
-def assert_proven(tokens, lengths, src, shift, st):
+def assert_proven(tokens, lengths, src, shift, st, reduced=True):
     """Independent of the restatement: every walk's best list is a proven factorisation of what its start list sums to,
-    of rank best_rank."""
+    of rank best_rank.  (``reduced=False``: a hand-written list that holds a term and its negative -- the canonical
+    form drops such a pair, so its rank is not the list's; the sum is still proven.)"""
     targets = flips.term_sum(dev(tokens), dev(np.asarray(lengths, np.int64)), shift)
     idx = torch.arange(len(lengths), device=DEV) if src is None else dev(np.asarray(src, np.int64))
     good = st["state"] >= 0
     _, rank, _, res = ops.solution_canon(targets[idx].contiguous(), st["best"].contiguous(), st["best_rank"].to(torch.int64),
                                          shift=shift)
-    assert bool((res[good] == 0).all()) and torch.equal(rank[good], st["best_rank"][good])
+    assert bool((res[good] == 0).all()) and (not reduced or torch.equal(rank[good], st["best_rank"][good]))
     _, rank, _, res = ops.solution_canon(targets[idx].contiguous(), st["cur"].contiguous(), st["cur_rank"].to(torch.int64),
                                          shift=shift)
-    assert bool((res[good] == 0).all()) and torch.equal(rank[good], st["cur_rank"][good])
+    assert bool((res[good] == 0).all()) and (not reduced or torch.equal(rank[good], st["cur_rank"][good]))
 
 
 # ---- begin -----------------------------------------------------------------------------------------------------------
@@ -294,3 +297,200 @@ def test_reduce_archive_lowers_the_standard_algorithm_to_rank_7(with_group):
     assert not fresh[want["best_rank"] == 8].any()                                    # the entry itself is not new
     tokens, rank, _, _ = arch.entries()
     assert torch.equal(flips.term_sum(tokens.contiguous(), rank.to(torch.int64), 1), target.expand(len(rank), 4, 4, 4))
+
+
+# ---- the rule events: gadget lists whose slots decide the branch (flips_ref.GADGET_CASES) -----------------------------
+@pytest.mark.parametrize("name", list(FR.GADGET_CASES))
+def test_gadget_walks_equal_the_restatement(name):
+    """Null a' and b' with the hi/lo removal order, cancelling pairs and merges inside a walk, moves between a lane's
+    two slots: test_flips_cpu.py asserts that the restatement reaches each at least MIN_EVENTS times on this list."""
+    tokens, L, W, n_steps, want, events = FR.gadget_ref(name)
+    for e in FR.ALWAYS + FR.GADGET_CASES[name][7]:
+        assert events[e] >= FR.MIN_EVENTS, (e, events[e])
+    src = np.zeros(W, dtype=np.int64)
+    g, status = gpu_begin(tokens[None], [L], src, FR.GADGET_BOUND, FR.GADGET_BOUND)
+    assert status == 0
+    got = gpu_advance(g, n_steps, FR.GADGET_BOUND, FR.GADGET_BOUND, FR.GADGET_SEED)
+    assert_state(got, want, name)
+    assert_proven(tokens[None], [L], src, FR.GADGET_BOUND, g.st)
+
+
+# ---- the sizes of the workload and the limits ------------------------------------------------------------------------
+def _size_list(case):
+    rng = np.random.default_rng(21)
+    if case == "4x4":                                             # 4 full dwords per vector, K = 64 = L: one-word masks, full
+        return (*FR.standard_matmul(4), 16, 80)
+    if case == "5x5":                                             # 7 dwords, 125 terms
+        return (*FR.standard_matmul(5, K=128), 25, 64)
+    if case == "S32":                                             # TG_MAX_S; sparse vectors, or no flip stays inside bound 1
+        return (*FR.pool_list(rng, 32, 128, 128, 12, 1, nnz=2), 32, 64)
+    S = int(case[1:])                                             # S < 4: one partly filled dword
+    return (*FR.pool_list(rng, S, 24, 24, 3, 1), S, 96)
+
+
+@pytest.mark.parametrize("case", ["4x4", "5x5", "S32", "S1", "S2", "S3"])
+def test_sizes_equal_the_restatement(case):
+    tokens, L, S, n_steps = _size_list(case)
+    K, W, bound, shift, split = tokens.shape[0], 4, 1, 1, 37
+    src = np.zeros(W, dtype=np.int64)
+    want, wstatus = FR.begin(tokens[None], [L], src, bound, shift)
+    g, status = gpu_begin(tokens[None], [L], src, bound, shift)
+    assert status == wstatus == 0
+    assert_state(to_np(g.st), want, (case, "begin"))
+    trace = []
+    FR.advance(want, SEED + 5, 0, 0, split, bound, shift, trace=trace)
+    FR.advance(want, SEED + 5, 0, split, n_steps - split, bound, shift, trace=trace)
+    gpu_advance(g, split, bound, shift, SEED + 5)
+    got = gpu_advance(g, n_steps - split, bound, shift, SEED + 5, step0=split)
+    # At S = 1 and bound 1 every normalised vector is (1): a flip's n_q(a) + eps n_q(b) is 2, or it is 0 and then the
+    # other term's mode r holds s_b + s_a = +-2, because the reduce left no two terms of opposite sign.  No flip is
+    # ever accepted there; everywhere else both outcomes occur.
+    assert {a for _, _, _, a in trace} == ({False} if S == 1 else {False, True})
+    assert (want["state"] == 0).all() and len(trace) == W * n_steps
+    if case in ("5x5", "S32"):
+        assert want["cur_rank"].min() > 64
+    assert_state(got, want, case)
+    assert_proven(tokens[None], [L], src, shift, g.st)
+
+
+# ---- more walks than workgroups ---------------------------------------------------------------------------------------
+def test_a_workgroup_loops_over_walks_of_mixed_length_and_state(golden):
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    W = 2 * 32 * cus + 77
+    assert W > 32 * cus                                           # the launch starts at most 32 workgroups per CU
+    S, K, bound, shift, n_steps = 4, 8, 1, 1, 2
+    std, L = FR.standard_matmul(2)
+    tokens = np.zeros((7, K, 3 * S), dtype=np.int8)
+    tokens[0] = std                                               # the standard list
+    tokens[1, :7] = golden("strassen")["tokens"]                  # stuck at once
+    tokens[3] = std                                               # 2: empty; 3: K/2 terms and rows behind them
+    tokens[4] = std                                               # a bad length
+    tokens[5] = std
+    tokens[5, 6, 7] = 2 + shift                                   # a value out of range
+    tokens[6] = FR.pool_list(np.random.default_rng(5), S, K, K, 3, shift)[0]
+    lengths = np.array([L, 7, 0, K // 2, K + 1, L, K], dtype=np.int64)
+    src = np.arange(W, dtype=np.int64) % 7                        # 7 does not divide the grid: a workgroup meets them all
+    one, wstatus = FR.begin(tokens, lengths, None, bound, shift)  # once per list
+    want = {k: v[src] for k, v in one.items()}
+    assert wstatus == FR.BAD_LENGTH | FR.BAD_RANGE and list(one["state"]) == [0, 0, 0, 0, -1, -1, 0]
+    g, status = gpu_begin(tokens, lengths, src, bound, shift)
+    assert status == wstatus
+    assert_state(to_np(g.st), want, "begin")
+    FR.advance(want, SEED, 0, 0, n_steps, bound, shift)
+    assert {int(s) for s in want["state"]} == {-1, 0, 1} and (want["state"][src == 1] == 1).all()
+    assert (want["state"][src == 2] == 1).all() and (want["flips"][src == 6] > 0).any()
+    got = gpu_advance(g, n_steps, bound, shift, SEED)
+    assert_state(got, want, "advance")
+    assert_proven(tokens, np.clip(lengths, 0, K), src, shift, g.st)
+
+
+def test_advance_does_not_depend_on_what_the_lds_held():
+    """At S = 5 a vector fills a dword and a quarter: the list's padding bytes must be the kernel's own zeros, not
+    what an earlier launch with the same LDS footprint (S = 8: the same two dwords per vector, all bytes used) left."""
+    tokens, L, S, W, n_steps, bound, shift, want, _ = advanced_ref("pool70")
+    K = tokens.shape[0]
+    g, _ = gpu_begin(tokens[None], [L], np.zeros(W, dtype=np.int64), bound, shift)
+    rng = np.random.default_rng(9)
+    dense = (rng.integers(1, 3, size=(1, K, 24)) * rng.choice([-1, 1], size=(1, K, 24)) + shift).astype(np.int8)
+    slots = 32 * torch.cuda.get_device_properties(DEV).multi_processor_count
+    d = ops.flip_begin(dev(dense), dev(np.array([K])), src=torch.zeros(slots, dtype=torch.int64, device=DEV), bound=bound,
+                       shift=shift)
+    ops.flip_advance(d, 1, bound=bound, shift=shift)
+    assert int(d["cur_rank"].min()) == K
+    got = gpu_advance(g, n_steps, bound, shift, SEED)
+    assert_state(got, want)
+
+
+# ---- the Philox words and the step tails -----------------------------------------------------------------------------
+def _philox_run(seed, walk0, step0, n_steps):
+    std, L = FR.standard_matmul(2)
+    src = np.zeros(8, dtype=np.int64)
+    want, _ = FR.begin(std[None], [L], src, 1, 1)
+    FR.advance(want, seed, walk0, step0, n_steps, 1, 1)
+    g, _ = gpu_begin(std[None], [L], src, 1, 1)
+    got = gpu_advance(g, n_steps, 1, 1, seed, walk0=walk0, step0=step0)
+    assert_state(got, want, (seed, walk0, step0, n_steps))
+    return got
+
+
+@pytest.mark.parametrize("step0, n_steps", [(0, 1), (0, 63), (0, 65), (37, 100), (2 ** 32 - 70, 70)])
+def test_step_tails_and_the_last_step_index(step0, n_steps):
+    got = _philox_run(SEED, 0, step0, n_steps)
+    assert got["flips"].sum() > 0
+
+
+def test_high_words_of_seed_and_walk_id_reach_philox():
+    low_seed, high_seed = _philox_run(3, 0, 0, 100), _philox_run((9 << 32) | 3, 0, 0, 100)
+    low_walk, high_walk = _philox_run(SEED, 5, 0, 100), _philox_run(SEED, (1 << 40) + 5, 0, 100)
+    for a, b in ((low_seed, high_seed), (low_walk, high_walk)):
+        assert not np.array_equal(a["cur"], b["cur"]) and not np.array_equal(a["flips"], b["flips"])
+    _philox_run(SEED, 2 ** 32 - 3, 0, 100)                        # the id's low word wraps inside the call
+
+
+# ---- cur_rank outside [0, K]; capture --------------------------------------------------------------------------------
+def test_a_walk_whose_cur_rank_is_outside_0_K_is_left_as_it_is():
+    std, L = FR.standard_matmul(2)
+    K, W = std.shape[0], 6
+    src = np.zeros(W, dtype=np.int64)
+    g, _ = gpu_begin(std[None], [L], src, 1, 1)
+    for w, rank in ((1, K + 1), (4, -1)):
+        g.st["cur_rank"][w] = rank
+        g.st["cur"][w].fill_(0x55)
+        g.st["best"][w].fill_(0x55)
+    marked = to_np(g.st)
+    assert list(marked["state"]) == [0] * W
+    want = FR.copy_state(marked)
+    FR.advance(want, SEED, 0, 0, 64, 1, 1)
+    got = gpu_advance(g, 64, 1, 1, SEED)
+    for k in FR.STATE_NAMES:
+        assert np.array_equal(got[k][[1, 4]], marked[k][[1, 4]]), k
+    assert_state(got, want)
+    assert (got["flips"][[0, 2, 3, 5]] > 0).all()
+
+
+def test_captured_graph_of_begin_and_two_advances_equals_the_eager_calls():
+    tokens, L, S, W, n_steps, bound, shift, want, _ = advanced_ref("3x3")
+    K = tokens.shape[0]
+    _, tok = odd(dev(tokens[None]))
+    lens, src = dev(np.array([L], dtype=np.int64)), torch.zeros(W, dtype=torch.int64, device=DEV)
+    status = torch.zeros(1, dtype=torch.uint32, device=DEV)
+    g = Guarded(W, K, S)
+
+    def call():
+        ops.flip_begin(tok, lens, src=src, bound=bound, shift=shift, status=status, **g.st)
+        ops.flip_advance(g.st, 100, bound=bound, shift=shift, seed=SEED)
+        ops.flip_advance(g.st, n_steps - 100, bound=bound, shift=shift, seed=SEED, step0=100)
+
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        call()
+    torch.cuda.current_stream(DEV).wait_stream(side)
+    eager = to_np(g.st)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        call()
+    for name, _ in ops._FLIP_STATE:
+        g.st[name].fill_(0x33)                                    # the replay starts from rubbish, as begin may
+    graph.replay()
+    torch.cuda.synchronize()
+    g.check()
+    got = to_np(g.st)
+    assert_state(got, eager, "eager")
+    assert_state(got, want, "restatement")
+    assert int(status.cpu().view(torch.int32).item()) == 0
+
+
+@pytest.mark.parametrize("K", list(FR.ANTIPAIR_CASES))
+def test_both_terms_null_removes_the_higher_slot_first(K):
+    """No walk from a reduced list nulls both terms of a flip (test_flips_cpu.py), so the state is written by hand: a
+    term and its negative among inert terms.  The rule is the header's all the same."""
+    start, want, events = FR.antipair_ref(K)
+    assert events["null_both"] >= FR.MIN_EVENTS
+    W, S, bound = len(start["state"]), FR.GADGET_S, FR.GADGET_BOUND
+    g = Guarded(W, K, S)
+    for name in FR.STATE_NAMES:
+        g.st[name].copy_(dev(start[name]))
+    got = gpu_advance(g, FR.ANTIPAIR_STEPS, bound, bound, FR.GADGET_SEED)
+    assert_state(got, want, K)
+    assert_proven(start["cur"], start["cur_rank"], None, bound, g.st, reduced=False)
