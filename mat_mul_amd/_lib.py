@@ -219,6 +219,12 @@ FLIP_SIGNATURES = {
     "tg_flip_begin": [_p, _p, _i64, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "tg_flip_advance": [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _i64, _p],
 }
+# name -> argtypes; every symbol include/tensor_game_flips_plus.h declares
+FLIP_PLUS_SIGNATURES = {
+    "tg_flip_plus_check": [_i64, _i, _i, _i, _i, _i64, _i64, _i64, _i64],
+    "tg_flip_advance_plus": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _i64, _i64, _i64, _p],
+}
+TG_FLIP_MAX_PLUS_AFTER = 2 ** 31 - 1
 # limits and status bits of include/tensor_game_flips.h
 TG_FLIP_MAX_K, TG_FLIP_MAX_BOUND, TG_FLIP_MAX_STEPS = 128, 63, 65536
 TG_FLIP_BAD_LENGTH, TG_FLIP_BAD_RANGE, TG_FLIP_BAD_SRC = 1, 2, 4
@@ -282,7 +288,7 @@ def _load() -> C.CDLL:
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
-                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES}.items():
+                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

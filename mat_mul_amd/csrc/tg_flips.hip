@@ -1,4 +1,5 @@
-// Random walks on the flip graph (include/tensor_game_flips.h).  gfx950 only; part of libtensorgame.so.
+// Random walks on the flip graph (include/tensor_game_flips.h), and the same walks with plus transitions
+// (include/tensor_game_flips_plus.h).  gfx950 only; part of libtensorgame.so.
 //
 // A walk is sequential, so the parallelism is across walks and, inside a step, across terms: ONE wavefront (a 64-thread
 // workgroup of its own, so nothing ever waits for another wavefront) per walk, lane l owning terms l and l + 64.
@@ -16,11 +17,15 @@
 //           header's full scans give, because a pair that does not involve a changed term is either no candidate or
 //           passed over again.
 //   draws   Philox for 64 consecutive steps at a time, one step per lane.
+//   plus    (flip_advance_plus_kernel only) two terms become three: the pair number is located with the same prefix sum
+//           over L - 1 - t pairs per term, the three new vectors are tested before anything is written, the third term
+//           is appended in slot L, and the three slots are refreshed like any changed term; then the reduce above.
+//           flip_begin_kernel and flip_advance_kernel do not see any of it: FlipWalk::step is as it was.
 // Every loop is bounded by n_steps, K, S or the number of walks; none waits on memory another wavefront writes.  No
 // floating point, no atomics but the OR of the sticky bad-row bits.
 #include <hip/hip_runtime.h>
 
-#include "../../include/tensor_game_flips.h"
+#include "../../include/tensor_game_flips_plus.h"
 #include "tg_host.h"
 
 namespace tg {
@@ -283,6 +288,68 @@ struct FlipWalk {
     return 2;
   }
 
+  // The plus (tensor_game_flips_plus.h step 4) the draws oy, oz choose; needs 2 <= L < K.  1: refused, 2: accepted.
+  __device__ __forceinline__ int plus(uint32_t oy, uint32_t oz) {
+    const uint32_t P = static_cast<uint32_t>(L * (L - 1) / 2);
+    int k = static_cast<int>((static_cast<uint64_t>(oy) * P) >> 32);
+    const int v = static_cast<int>((static_cast<uint64_t>(oz) * 24u) >> 32);
+    // pair number k: term t owns the L - 1 - t pairs (t, j > t); the slots in turn, a prefix sum over each
+    int i = 0, j = 0;
+#pragma unroll
+    for (int s = 0; s < NW; ++s) {
+      const int t = lane + 64 * s;
+      const int own = t < L - 1 ? L - 1 - t : 0;
+      const int inc = scan(own);
+      const int tot = uniform(__shfl(inc, 63));
+      if (k >= 0 && k < tot) {
+        const int il = static_cast<int>(__builtin_ctzll(__ballot(inc > k)));
+        const int before = uniform(__shfl(inc - own, il));
+        i = il + 64 * s;
+        j = i + 1 + (k - before);
+        k = -1;
+      } else if (k >= 0) {
+        k -= tot;
+      }
+    }
+    const int a = (v & 1) ? j : i, b = (v & 1) ? i : j;
+    const int eps = (v & 2) ? -1 : 1;
+    const int perm = v >> 2;  // 012, 021, 102, 120, 201, 210
+    const int p = perm >> 1, q = perm == 0 || perm == 5 ? 1 : perm == 1 || perm == 3 ? 2 : 0, r = 3 - p - q;
+    const int sa = sgn[a], sb = sgn[b];
+    int d1 = 0, d2 = 0, d3 = 0;  // A_p - B_p, A_r + B_r, B_q - A_q
+    if (lane < S) {
+      d1 = bytes(a, p)[lane] - eps * bytes(b, p)[lane];
+      d2 = sa * bytes(a, r)[lane] + eps * sb * bytes(b, r)[lane];
+      d3 = bytes(b, q)[lane] - bytes(a, q)[lane];
+    }
+    if (__any(d1 > bound || d1 < -bound || d2 > bound || d2 < -bound || d3 > bound || d3 < -bound)) return 1;
+    const int n = L;  // the new slot: t2 = B_p, A_q, d2 (its copies first: slot a keeps mode q and slot b mode p)
+    const uint32_t cp = lane < SW ? vec[b * TS + p * SW + lane] : 0u, cq = lane < SW ? vec[a * TS + q * SW + lane] : 0u;
+    const int s1 = put_normalised(a, p, d1);  // t1 = d1, A_q, A_r
+    const int s3 = put_normalised(b, q, d3);  // t3 = B_p, d3, B_r: eps twice
+    const int s2 = put_normalised(n, r, d2);
+    if (s2 != 0 && lane < SW) {
+      vec[n * TS + p * SW + lane] = cp;
+      vec[n * TS + q * SW + lane] = cq;
+    }
+    if (lane == 0) {
+      if (s1 != 0) sgn[a] = static_cast<int8_t>(sa * s1);
+      if (s3 != 0) sgn[b] = static_cast<int8_t>(sb * s3);
+      if (s2 != 0) sgn[n] = static_cast<int8_t>(eps * s2);
+    }
+    __syncthreads();
+    if (s2 != 0) L = n + 1;  // (a null t2 would be removed first, from the last slot: it is not appended)
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    const bool null_hi = (a > b ? s1 : s3) == 0, null_lo = (a > b ? s3 : s1) == 0;
+    if (null_hi) remove(hi);  // the higher slot first; the last term moves in and is refreshed there
+    if (null_lo) remove(lo);
+    if (s2 != 0 && n < L) refresh(n);  // bit n of every mask and all of n's masks: nothing of an earlier tenant stays
+    if (!null_hi && hi < L) refresh(hi);
+    if (!null_lo && lo < L) refresh(lo);
+    reduce();
+    return 2;
+  }
+
   // ---- global <-> LDS
   __device__ __forceinline__ void clear() {
     for (int x = lane; x < K * TS; x += 64) vec[x] = 0;
@@ -458,6 +525,84 @@ __global__ __launch_bounds__(64) void flip_advance_kernel(FlipArgs a) {
   }
 }
 
+struct FlipPlusArgs {
+  FlipArgs f;
+  int32_t* since;   // (W)
+  int64_t* pluses;  // (W)
+  int plus_after, plus_slack;
+};
+
+// tg_flip_advance_plus: flip_advance_kernel's walk with the choice of tensor_game_flips_plus.h in front of every step.
+// since, pluses and the cap are wavefront-uniform scalars, read once per walk and written once, by lane 0.
+template <int NW>
+__global__ __launch_bounds__(64) void flip_advance_plus_kernel(FlipPlusArgs pa) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t flip_lds[];
+  const FlipArgs& a = pa.f;
+  FlipWalk<NW> wk = flip_walk<NW>(a, flip_lds);
+  const int64_t n_row = static_cast<int64_t>(a.K) * 3 * a.S;
+  const uint32_t k0 = static_cast<uint32_t>(a.seed), k1 = static_cast<uint32_t>(a.seed >> 32);
+  for (int64_t w = blockIdx.x; w < a.W; w += gridDim.x) {
+    const int L0 = a.cur_rank[w];
+    if (a.state[w] != 0 || L0 < 0 || L0 > a.K) continue;  // left exactly as it is (uniform)
+    const uint64_t g = a.walk0 + static_cast<uint64_t>(w);
+    wk.clear();
+    wk.stage(a.cur + w * n_row, L0);
+    wk.normalise(L0);
+    wk.L = L0;
+    wk.refresh_all();
+    int best = a.best_rank[w];
+    int since = uniform(pa.since[w]);
+    int64_t accepted = 0, plused = 0;
+    int stuck = 0;
+    U4 o64{0, 0, 0, 0};
+    for (int k = 0; k < a.n_steps; ++k) {
+      if ((k & 63) == 0) {  // the draws of steps k .. k + 63, one per lane
+        const uint32_t t = static_cast<uint32_t>(static_cast<uint64_t>(a.step0) + static_cast<uint64_t>(k + wk.lane));
+        o64 = philox4x32_10(U4{static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), t, TG_FLIP_DOMAIN}, k0, k1);
+      }
+      const int before = wk.L;
+      const int64_t cap64 = static_cast<int64_t>(best) + pa.plus_slack;
+      const bool can = before >= 2 && before < (cap64 < a.K ? cap64 : a.K);
+      // a flip step unless the walk is due for a plus and may take one; step() returns 0 for C == 0
+      int what = 0;
+      if (!(can && since >= pa.plus_after)) {
+        const uint32_t ox = static_cast<uint32_t>(uniform(static_cast<int>(__shfl(o64.x, k & 63))));
+        what = wk.step(ox);
+        accepted += what == 2;
+      }
+      bool progress = wk.L < before;
+      if (what == 0) {
+        if (!can) {
+          stuck = 1;
+          break;
+        }
+        const uint32_t oy = static_cast<uint32_t>(uniform(static_cast<int>(__shfl(o64.y, k & 63))));
+        const uint32_t oz = static_cast<uint32_t>(uniform(static_cast<int>(__shfl(o64.z, k & 63))));
+        progress = wk.plus(oy, oz) == 2;
+        plused += progress;
+      }
+      since = progress ? 0 : since == INT32_MAX ? since : since + 1;
+      if (wk.L < best) {
+        best = wk.L;
+        wk.store(a.best + w * n_row, best);
+        if (wk.lane == 0) {
+          a.best_rank[w] = best;
+          a.best_step[w] = a.step0 + k + 1;
+        }
+      }
+    }
+    wk.store(a.cur + w * n_row, wk.L);
+    if (wk.lane == 0) {
+      a.cur_rank[w] = wk.L;
+      a.flips[w] += accepted;
+      pa.since[w] = since;
+      pa.pluses[w] += plused;
+      if (stuck) a.state[w] = 1;
+    }
+    __syncthreads();  // the list is free for the next walk
+  }
+}
+
 }  // namespace tg
 
 namespace {
@@ -502,13 +647,27 @@ int flip_state_pointers(const char* fn, const int8_t* cur, const int32_t* cur_ra
   return TG_OK;
 }
 
-// a wavefront per walk: as many workgroups as walks, up to what the device holds a few times over
-template <typename Kern>
-int launch_flip(const char* fn, Kern kernel, const tg::FlipArgs& a, hipStream_t st) {
+int flip_plus_sizes(const char* fn, int64_t plus_after, int64_t plus_slack) {
+  if (plus_after < 1 || plus_after > TG_FLIP_MAX_PLUS_AFTER)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: plus_after=%lld outside [1,%d]", fn, (long long)plus_after, TG_FLIP_MAX_PLUS_AFTER);
+  if (plus_slack < 0 || plus_slack > TG_FLIP_MAX_K)
+    return tg_internal_fail(TG_ERR_INVALID, "%s: plus_slack=%lld outside [0,%d]", fn, (long long)plus_slack, TG_FLIP_MAX_K);
+  return TG_OK;
+}
+
+// a wavefront per walk: as many workgroups as walks, up to what the device holds a few times over; `args` is what the
+// kernel takes (FlipArgs `a` itself, or a struct that holds it)
+template <typename Kern, typename Args>
+int launch_flip(const char* fn, Kern kernel, const tg::FlipArgs& a, const Args& args, hipStream_t st) {
   const int SW = (a.S + 3) / 4, TS = (3 * SW) | 1;
   const size_t lds = static_cast<size_t>(a.K) * TS * 4 + ((static_cast<size_t>(a.K) + 15) & ~size_t{15});  // <= 12.7 KiB
   const int64_t resident = static_cast<int64_t>(32) * device_cu_count();
-  return launch(fn, kernel, static_cast<unsigned>(a.W < resident ? a.W : resident), 64, lds, st, a);
+  return launch(fn, kernel, static_cast<unsigned>(a.W < resident ? a.W : resident), 64, lds, st, args);
+}
+
+template <typename Kern>
+int launch_flip(const char* fn, Kern kernel, const tg::FlipArgs& a, hipStream_t st) {
+  return launch_flip(fn, kernel, a, a, st);
 }
 
 }  // namespace
@@ -553,4 +712,34 @@ extern "C" int tg_flip_advance(int8_t* cur, int32_t* cur_rank, int8_t* best, int
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (K <= 64) return launch_flip(fn, tg::flip_advance_kernel<1>, a, st);
   return launch_flip(fn, tg::flip_advance_kernel<2>, a, st);
+}
+
+extern "C" int tg_flip_plus_check(int64_t W, int K, int S, int shift, int bound, int64_t step0, int64_t n_steps,
+                                  int64_t plus_after, int64_t plus_slack) {
+  const char* fn = "tg_flip_plus_check";
+  if (const int rc = flip_sizes(fn, 0, W, K, S, shift, bound)) return rc;
+  if (const int rc = flip_steps(fn, step0, n_steps)) return rc;
+  return flip_plus_sizes(fn, plus_after, plus_slack);
+}
+
+extern "C" int tg_flip_advance_plus(int8_t* cur, int32_t* cur_rank, int8_t* best, int32_t* best_rank, int64_t* best_step,
+                                    int64_t* flips, int32_t* state, int32_t* since, int64_t* pluses, int64_t W, int K, int S,
+                                    int shift, int bound, uint64_t seed, uint64_t walk0, int64_t step0, int64_t n_steps,
+                                    int64_t plus_after, int64_t plus_slack, tg_stream_t stream) {
+  const char* fn = "tg_flip_advance_plus";
+  if (const int rc = flip_sizes(fn, 0, W, K, S, shift, bound)) return rc;
+  if (const int rc = flip_steps(fn, step0, n_steps)) return rc;
+  if (const int rc = flip_plus_sizes(fn, plus_after, plus_slack)) return rc;
+  if (W == 0) return TG_OK;
+  if (const int rc = flip_state_pointers(fn, cur, cur_rank, best, best_rank, best_step, flips, state)) return rc;
+  if (!since) return tg_internal_fail(TG_ERR_INVALID, "%s: null since", fn);
+  if (!pluses) return tg_internal_fail(TG_ERR_INVALID, "%s: null pluses", fn);
+  if (!aligned(since, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: since not 4-byte aligned", fn);
+  if (!aligned(pluses, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: pluses not 8-byte aligned", fn);
+  const tg::FlipArgs a{nullptr, nullptr, nullptr, 0, W, cur, cur_rank, best, best_rank, best_step, flips, state, nullptr,
+                       seed, walk0, step0, static_cast<int>(n_steps), K, S, shift, bound};
+  const tg::FlipPlusArgs pa{a, since, pluses, static_cast<int>(plus_after), static_cast<int>(plus_slack)};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (K <= 64) return launch_flip(fn, tg::flip_advance_plus_kernel<1>, a, pa, st);
+  return launch_flip(fn, tg::flip_advance_plus_kernel<2>, a, pa, st);
 }

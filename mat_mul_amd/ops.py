@@ -34,7 +34,7 @@ __all__ = [
     "solution_check", "solution_canon",
     "orbit_check", "orbit_fixes", "orbit_workspace_size", "orbit_canon",
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
-    "flip_check", "flip_begin", "flip_advance",
+    "flip_check", "flip_begin", "flip_advance", "flip_plus_check", "flip_advance_plus",
 ]
 
 
@@ -1633,11 +1633,15 @@ _FLIP_STATE = (("cur", torch.int8), ("cur_rank", torch.int32), ("best", torch.in
                ("best_step", torch.int64), ("flips", torch.int64), ("state", torch.int32))
 
 
-def _flip_state(given: dict, W: int, K: int, S: int, dev, fn: str) -> dict:
-    """The seven walk-state tensors of include/tensor_game_flips.h on ``dev``: ``given[name]`` held to the rule of
-    ``_flag``, or allocated where it is None."""
+# and the two tensor_game_flips_plus.h adds
+_FLIP_PLUS_STATE = _FLIP_STATE + (("since", torch.int32), ("pluses", torch.int64))
+
+
+def _flip_state(given: dict, W: int, K: int, S: int, dev, fn: str, names=_FLIP_STATE) -> dict:
+    """The walk-state tensors ``names`` (the seven of include/tensor_game_flips.h) on ``dev``: ``given[name]`` held to
+    the rule of ``_flag``, or allocated where it is None."""
     out = {}
-    for name, dtype in _FLIP_STATE:
+    for name, dtype in names:
         shape = (W, K, 3 * S) if dtype == torch.int8 else (W,)
         t = given.get(name)
         if t is not None:
@@ -1692,4 +1696,35 @@ def flip_advance(st: dict, n_steps: int, bound: int = 1, shift: int = 1, seed: i
     st = _flip_state({name: st[name] for name, _ in _FLIP_STATE}, W, K, S, cur.device, fn)
     _launch(cur.device, "tg_flip_advance", *[_ptr(st[name]) for name, _ in _FLIP_STATE], W, K, S, int(shift), int(bound),
             C.c_uint64(_u64(seed)), C.c_uint64(_u64(walk0)), int(step0), int(n_steps))
+    return st
+
+
+def flip_plus_check(W: int, K: int, S: int, shift: int = 1, bound: int = 1, step0: int = 0, n_steps: int = 1,
+                    plus_after: int = 1, plus_slack: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_flip_advance_plus takes these sizes.  Host only."""
+    call("tg_flip_plus_check", int(W), int(K), int(S), int(shift), int(bound), int(step0), int(n_steps), int(plus_after),
+         int(plus_slack))
+
+
+def flip_advance_plus(st: dict, n_steps: int, plus_after: int, plus_slack: int = 1, bound: int = 1, shift: int = 1,
+                      seed: int = 0, walk0: int = 0, step0: int = 0):
+    """``flip_advance`` with plus transitions (include/tensor_game_flips_plus.h): a walk that has no flip left, or has
+    not lowered its rank for ``plus_after`` steps, rewrites two terms into three while its list is shorter than
+    min(K, best_rank + plus_slack), and goes on.  ``st`` holds the seven tensors of ``flip_begin`` and ``since`` int32
+    (W,), ``pluses`` int64 (W,), zero for fresh walks (a missing one is a refusal: the counters carry from call to
+    call).  In place, one launch, no host sync.  Returns ``st``."""
+    fn = "flip_advance_plus"
+    cur = st["cur"]
+    _need_gpu(cur, "cur")
+    if cur.dtype != torch.int8 or cur.dim() != 3 or cur.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"cur must be int8 (W,K,3S), got {cur.dtype} {tuple(cur.shape)}")
+    W, K, S = cur.shape[0], cur.shape[1], cur.shape[2] // 3
+    flip_plus_check(W, K, S, shift, bound, step0, n_steps, plus_after, plus_slack)
+    for name in ("since", "pluses"):
+        if st.get(name) is None:
+            raise TensorGameError(fn, -1, f"{name} must be given (zeros for fresh walks)")
+    st = _flip_state({name: st[name] for name, _ in _FLIP_PLUS_STATE}, W, K, S, cur.device, fn, _FLIP_PLUS_STATE)
+    _launch(cur.device, "tg_flip_advance_plus", *[_ptr(st[name]) for name, _ in _FLIP_PLUS_STATE], W, K, S, int(shift),
+            int(bound), C.c_uint64(_u64(seed)), C.c_uint64(_u64(walk0)), int(step0), int(n_steps), int(plus_after),
+            int(plus_slack))
     return st

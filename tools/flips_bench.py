@@ -2,6 +2,7 @@
 
     python tools/flips_bench.py OUT_DIR [--reps 5] [--warmup 1] [--hist-steps 100000]
     python tools/flips_bench.py OUT_DIR --resources      (no GPU: where the library was built, its objects are at hand)
+    python tools/flips_bench.py OUT_DIR --plus-after N [--plus-slack M]    (tg_flip_advance_plus: walks with plus transitions)
 
 One process, one GPU.  Starting lists: the standard algorithms of <2,2,2> (S=4, K=8), <3,3,3> (S=9, K=27) and <4,4,4>
 (S=16, K=64), bound 1, shift 1.  Timing: W in {256, 4 096, 65 536} walks from one list, n_steps = 4 096 per launch;
@@ -9,7 +10,11 @@ every repetition starts again from the begin state (so all repetitions do the sa
 events) and is timed with HIP events around the one launch, after warm-up: median, p10, p90 in microseconds, ns per step
 per walk (over the steps walks really took: a stuck walk takes none), aggregate steps per second, and the accepted
 share.  Histogram: ``best_rank`` over 4 096 walks after ``--hist-steps`` steps from each start.  Also records the
-kernels' VGPRs, LDS and scratch from the code object.  Writes OUT_DIR/flips_bench.json.
+kernels' VGPRs, LDS and scratch from the code object.  Writes OUT_DIR/flips_bench.json.  With ``--plus-after`` the same
+through tg_flip_advance_plus (include/tensor_game_flips_plus.h; K one above the start's length where the start fills K,
+so that a plus has a slot), every row and histogram also with ``pluses`` and the stuck walks, written to
+OUT_DIR/flips_bench_plus_N_M.json.  (There ``steps_taken`` is exact only while no walk gets stuck after its best step:
+with plus_slack 0, or when stuck_walks is 0.)
 """
 from __future__ import annotations
 
@@ -34,17 +39,18 @@ DEV = "cuda:0"
 N_STEPS = 4096
 
 
-def standard_matmul(n, shift=1):
-    """The n^3 terms a_ij (x) b_jk (x) c_ik of <n,n,n> as tokens (K = n^3 rows)."""
+def standard_matmul(n, shift=1, spare=0):
+    """The n^3 terms a_ij (x) b_jk (x) c_ik of <n,n,n> as tokens (K = n^3 + spare rows)."""
     S = n * n
-    rows = np.zeros((n ** 3, 3 * S), dtype=np.int64)
+    rows = np.zeros((n ** 3 + spare, 3 * S), dtype=np.int64)
     t = 0
     for i in range(n):
         for j in range(n):
             for k in range(n):
                 rows[t, i * n + j] = rows[t, S + j * n + k] = rows[t, 2 * S + i * n + k] = 1
                 t += 1
-    return (rows + shift).astype(np.int8)
+    rows[:t] += shift
+    return rows.astype(np.int8)
 
 
 def stats(ts):
@@ -86,8 +92,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--hist-steps", type=int, default=100000)
     ap.add_argument("--walks", type=int, nargs="*", default=[256, 4096, 65536])
+    ap.add_argument("--plus-after", type=int, default=None, help="walk with plus transitions (tg_flip_advance_plus)")
+    ap.add_argument("--plus-slack", type=int, default=1)
     args = ap.parse_args()
-    out = Path(args.out) / "flips_bench.json"
+    plus = args.plus_after is not None
+    out = Path(args.out) / (f"flips_bench_plus_{args.plus_after}_{args.plus_slack}.json" if plus else "flips_bench.json")
+    start = dict(bound=1, shift=1, plus_after=args.plus_after, plus_slack=args.plus_slack)
     out.parent.mkdir(parents=True, exist_ok=True)
     if args.resources:
         res = json.loads(out.read_text()) if out.exists() else {}
@@ -97,12 +107,14 @@ def main():
         return
     res = {"torch": torch.__version__, "device": torch.cuda.get_device_name(0), "n_steps": N_STEPS, "resources": kernel_resources(),
            "rows": [], "histograms": []}
+    if plus:
+        res.update(plus_after=args.plus_after, plus_slack=args.plus_slack)
     for n in (2, 3, 4):
-        S, K = n * n, n ** 3
-        tokens = torch.from_numpy(standard_matmul(n)[None]).to(DEV)
-        lengths = torch.tensor([K], dtype=torch.int64, device=DEV)
+        S, K = n * n, n ** 3 + (args.plus_slack if plus else 0)
+        tokens = torch.from_numpy(standard_matmul(n, spare=K - n ** 3)[None]).to(DEV)
+        lengths = torch.tensor([n ** 3], dtype=torch.int64, device=DEV)
         for W in args.walks:
-            walks = FlipWalks.start(tokens, lengths, walks_per_list=W, bound=1, shift=1, seed=1)
+            walks = FlipWalks.start(tokens, lengths, walks_per_list=W, seed=1, **start)
             begin = {k: v.clone() for k, v in walks._st.items()}
             ts = []
             for rep in range(args.warmup + args.reps):
@@ -110,7 +122,10 @@ def main():
                     walks._st[k].copy_(v)
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-                ops.flip_advance(walks._st, N_STEPS, bound=1, shift=1, seed=1)
+                if plus:
+                    ops.flip_advance_plus(walks._st, N_STEPS, args.plus_after, args.plus_slack, bound=1, shift=1, seed=1)
+                else:
+                    ops.flip_advance(walks._st, N_STEPS, bound=1, shift=1, seed=1)
                 b.record()
                 b.synchronize()
                 if rep >= args.warmup:
@@ -124,9 +139,11 @@ def main():
                    "ns_per_step_per_walk": st["median_us"] * 1e3 / max(taken, 1),
                    "steps_per_s": taken / (st["median_us"] * 1e-6), "accepted_share": float(walks.flips.sum()) / max(taken, 1),
                    "stuck_walks": int(stuck.sum()), "min_best_rank": int(walks.best_rank.min())}
+            if plus:
+                row["pluses"] = int(walks.pluses.sum())
             res["rows"].append(row)
             print(json.dumps(row), flush=True)
-        walks = FlipWalks.start(tokens, lengths, walks_per_list=4096, bound=1, shift=1, seed=2)
+        walks = FlipWalks.start(tokens, lengths, walks_per_list=4096, seed=2, **start)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         walks.advance(args.hist_steps)
@@ -135,6 +152,8 @@ def main():
         ranks, counts = torch.unique(walks.best_rank, return_counts=True)
         hist = {"n": n, "S": S, "K": K, "W": 4096, "steps": args.hist_steps, "seconds": a.elapsed_time(b) * 1e-3,
                 "best_rank": {int(r): int(c) for r, c in zip(ranks.cpu(), counts.cpu())}, "stuck_walks": int((walks.state == 1).sum())}
+        if plus:
+            hist["pluses"] = int(walks.pluses.sum())
         res["histograms"].append(hist)
         print(json.dumps(hist), flush=True)
         out.write_text(json.dumps(res, indent=1) + "\n")
