@@ -20,7 +20,8 @@ tests.
   chunk loops: ``one25`` (n_steps 1) and ``odd25`` (n_steps 5) take one chunk in both blocks; ``xtail25`` (n_steps 5,
   c 16, whose resident ln2(ee) leaves the cross-attention two positions) takes one chunk in the self-attention and
   chunks of 2, 2 and 1 positions in the cross-attention; ``stail25`` (n_steps 31 with W 64, d 64, ff 256, one block)
-  takes chunks of 16 and 15 in the self-attention (and seven of 5, 5, .., 1 in the cross-attention).  ``REFUSED``: a25
+  takes chunks of 16 and 15 in the self-attention (and seven of 5, 5, .., 1 in the cross-attention).  ``t2_25`` is c25
+  with T = 2 frames (c25's chunks): the small row for float32 frames with T > 1.  ``REFUSED``: a25
   at dim_c 12 (inside the inference family), whose resident ln2(ee) leaves no room for one cross-attention position.
 """
 from net_family import LDS, scr_plan
@@ -39,6 +40,7 @@ ROWS = {
     "odd25": dict(_C25, n_steps=5),
     "xtail25": dict(_C25, c=16, n_steps=5),
     "stail25": dict(_C25, n_steps=31, W=64, d=64, ff=256, blocks=1),
+    "t2_25": dict(_C25, T=2),
 }
 REFUSED = {"wide25": dict(dims(CONFIGS["a25"]), c=12)}
 
