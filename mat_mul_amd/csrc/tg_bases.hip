@@ -17,7 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tensor_game_bases.h"
-#include "tg_host.h"
+#include "tg_lists.h"
 #include "tg_sol_copy.h"
 
 namespace tg {
@@ -175,12 +175,8 @@ int inverse_sizes(const char* fn, int64_t N, int S) {
 }
 
 int rebase_sizes(const char* fn, int64_t M, int K, int S, int64_t G, int shift) {
-  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (K < 1 || K > TG_SOL_MAX_K) return tg_internal_fail(TG_ERR_INVALID, "%s: K=%d outside [1,%d]", fn, K, TG_SOL_MAX_K);
-  if (shift < 0 || shift > TG_SOL_MAX_SHIFT)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: shift=%d outside [0,%d]", fn, shift, TG_SOL_MAX_SHIFT);
-  if (M < 0 || M > INT64_MAX / (static_cast<int64_t>(TG_SOL_MAX_K) * 3 * TG_MAX_S * TG_MAX_S))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld out of range", fn, (long long)M);
+  if (const int rc = check_lists(fn, K, S, shift, TG_SOL_MAX_K)) return rc;
+  if (const int rc = check_list_count(fn, M)) return rc;
   if (G < 0 || G > INT64_MAX / kTripleMax || (G == 0 && M != 0))
     return tg_internal_fail(TG_ERR_INVALID, "%s: G=%lld out of range (G >= 1 unless M = 0)", fn, (long long)G);
   return TG_OK;
@@ -205,9 +201,8 @@ extern "C" int tg_basis_inverse_i32(const int8_t* lower, const int8_t* upper, in
   if (!aligned(inv_out, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: inv_out not 4-byte aligned", fn);
   if (!aligned(status, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: status not 4-byte aligned", fn);
   const tg::InvArgs a{lower, upper, N, inv_out, bad, status, S};
-  const int64_t resident = 4ll * device_cu_count();  // 36 KiB of LDS per workgroup: four per CU
-  return launch(fn, tg::basis_inverse_kernel, static_cast<unsigned>(N < resident ? N : resident), tg::kInvThreads, 0,
-                static_cast<hipStream_t>(stream), a);
+  // 36 KiB of LDS per workgroup: four per CU
+  return launch_resident(fn, tg::basis_inverse_kernel, N, 4, tg::kInvThreads, 0, static_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int tg_solution_rebase(const int8_t* tokens, const int64_t* lengths, const int32_t* mats, const int64_t* index,
@@ -231,10 +226,9 @@ extern "C" int tg_solution_rebase(const int8_t* tokens, const int64_t* lengths, 
   if (!aligned(lengths_out, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: lengths_out not 8-byte aligned", fn);
   if (!aligned(mats, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: mats not 4-byte aligned", fn);
   if (!aligned(status, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: status not 4-byte aligned", fn);
-  const int img = (K * 3 * S + 15) & ~15;  // at most 24 KiB: with 3S rows of S | 1 words the LDS stays below 64 KiB
+  const int img = list_image_bytes(K, S);  // with 3S rows of S | 1 words the LDS stays below 64 KiB
   const int pitch = S | 1;
   const tg::RebaseArgs a{tokens, lengths, mats, index, M, G, tokens_out, lengths_out, bad, status, K, S, shift, img, pitch};
-  const int64_t resident = 16ll * device_cu_count();
-  return launch(fn, tg::solution_rebase_kernel, static_cast<unsigned>(M < resident ? M : resident), tg::kRebaseThreads,
-                2 * static_cast<size_t>(img) + static_cast<size_t>(3 * S) * pitch * 4, static_cast<hipStream_t>(stream), a);
+  return launch_resident(fn, tg::solution_rebase_kernel, M, 16, tg::kRebaseThreads,
+                         2 * static_cast<size_t>(img) + static_cast<size_t>(3 * S) * pitch * 4, static_cast<hipStream_t>(stream), a);
 }

@@ -26,7 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tensor_game_flips_plus.h"
-#include "tg_host.h"
+#include "tg_lists.h"
 
 namespace tg {
 
@@ -608,10 +608,7 @@ __global__ __launch_bounds__(64) void flip_advance_plus_kernel(FlipPlusArgs pa) 
 namespace {
 
 int flip_sizes(const char* fn, int64_t M, int64_t W, int K, int S, int shift, int bound) {
-  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (K < 1 || K > TG_FLIP_MAX_K) return tg_internal_fail(TG_ERR_INVALID, "%s: K=%d outside [1,%d]", fn, K, TG_FLIP_MAX_K);
-  if (shift < 0 || shift > TG_SOL_MAX_SHIFT)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: shift=%d outside [0,%d]", fn, shift, TG_SOL_MAX_SHIFT);
+  if (const int rc = check_lists(fn, K, S, shift, TG_FLIP_MAX_K)) return rc;
   if (bound < 1 || bound > TG_FLIP_MAX_BOUND)
     return tg_internal_fail(TG_ERR_INVALID, "%s: bound=%d outside [1,%d]", fn, bound, TG_FLIP_MAX_BOUND);
   const int64_t most = INT64_MAX / (static_cast<int64_t>(TG_FLIP_MAX_K) * 3 * TG_MAX_S);
@@ -661,8 +658,7 @@ template <typename Kern, typename Args>
 int launch_flip(const char* fn, Kern kernel, const tg::FlipArgs& a, const Args& args, hipStream_t st) {
   const int SW = (a.S + 3) / 4, TS = (3 * SW) | 1;
   const size_t lds = static_cast<size_t>(a.K) * TS * 4 + ((static_cast<size_t>(a.K) + 15) & ~size_t{15});  // <= 12.7 KiB
-  const int64_t resident = static_cast<int64_t>(32) * device_cu_count();
-  return launch(fn, kernel, static_cast<unsigned>(a.W < resident ? a.W : resident), 64, lds, st, args);
+  return launch_resident(fn, kernel, a.W, 32, 64, lds, st, args);
 }
 
 template <typename Kern>

@@ -11,7 +11,7 @@
 //              NORMALISED factor straight into the sort keys: P = 3S rounded up to 8 bytes per term, every byte with
 //              its sign bit flipped and every 8 bytes reversed, so unsigned 8-byte compares order the values as signed.
 //              g.X itself and its normalised image are never stored;
-//   order      the rank sort and merge of tg_solutions.hip: lower, equal-before and the run's sum of signs per term;
+//   order      the rank sort and merge tg_solutions.hip calls too (tg_sol_phases.h), as are the term signs and the key;
 //   emit       the kept terms go from the keys into the candidate image (negating w where the run's sum is negative);
 //   compare    every thread compares 16-byte chunks of the candidate and the running best and reports its first
 //              differing byte; the workgroup's minimum decides.  The smaller image stays by swapping two pointers.
@@ -36,7 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tensor_game_orbits.h"
-#include "tg_host.h"
+#include "tg_lists.h"
 #include "tg_sol_copy.h"
 #include "tg_sol_phases.h"
 #include "tg_sym_code.h"
@@ -127,15 +127,11 @@ template <int NT>
 __device__ __forceinline__ void orb_emit(const OrbArgs& a, int64_t m, const int8_t* best, int rank, int which, int stab,
                                          int nnz, uint64_t* red, int t) {
   const int A3 = 3 * a.S, n_row = a.K * A3;
-  const int n = rank * A3, words = (n + 7) / 8;  // the image is zero beyond n: the padding of the last word
-  uint64_t h = 0;
-  for (int k = t; k < words; k += NT)
-    h += fmix64(reinterpret_cast<const uint64_t*>(best)[k] + static_cast<uint64_t>(k + 1) * 0x9E3779B97F4A7C15ull);
-  h = sol_block_sum<NT>(h, red, t);
+  const uint64_t key = sol_image_key<NT>(best, rank * A3, red, t);
   sol_copy_out<NT>(a.canon + m * n_row, best, n_row, t);
   if (t == 0) {
     a.rank[m] = rank;
-    a.key[m] = hash_finish(h, n);
+    a.key[m] = key;
     a.which[m] = which;
     a.stab[m] = stab;
     if (a.residual) a.residual[m] = nnz;
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(NT) void orbit_canon_kernel(OrbArgs a) {
     }
     for (int x = t; x < L * P; x += NT) {  // the keys' padding behind 3S bytes: the same for every g
       const int r = x / P, e = x - r * P;
-      if (e >= A3) keys[r * P + (e & ~7) + 7 - (e & 7)] = 0;
+      if (e >= A3) keys[r * P + sol_key_at(e)] = 0;
     }
 
     int cur = 0, ext0 = 0, ext1 = 0;  // the best image is buf<cur>; buf<i> is zero from ext<i> on
@@ -229,68 +225,34 @@ __global__ __launch_bounds__(NT) void orbit_canon_kernel(OrbArgs a) {
           v = ((c & 128) != 0) != (first < 0) ? -v : v;
           const int tk = v + shift;
           if (tk < -128 || tk > 127) fc |= 4;
-          const int at = mm * S + e;
-          kd[(at & ~7) + 7 - (at & 7)] = static_cast<uint8_t>(tk ^ 0x80);
+          kd[sol_key_at(mm * S + e)] = sol_key_flip(tk);
         }
         fcode[q] = fc;
       }
       __syncthreads();
-      int bad = 0;
-      if (t < L) {
-        const int c0 = fcode[3 * t], c1 = fcode[3 * t + 1], c2 = fcode[3 * t + 2];
-        const bool alive = (c0 & 3) && (c1 & 3) && (c2 & 3);
-        const int flips = ((c0 & 3) == 2) + ((c1 & 3) == 2) + ((c2 & 3) == 2);
-        tsign[t] = alive ? ((flips & 1) ? -1 : 1) : 0;
-        bad = alive && ((c0 | c1 | c2) & 4);
-      }
+      int bad = sol_term_sign(fcode, tsign, L, t);
       __syncthreads();
 
       // ---- order and merge: thread t = term t (K <= NT)
-      const bool live = t < L && tsign[t] != 0;
-      int lower = 0, before = 0, c = 0;
-      if (live) {
-        const uint64_t* me = reinterpret_cast<const uint64_t*>(keys + t * P);
-        for (int j = 0; j < L; ++j) {
-          const int sj = tsign[j];
-          if (sj == 0) continue;
-          int d = 0;
-          if (j != t) {
-            const uint64_t* o = reinterpret_cast<const uint64_t*>(keys + j * P);
-            for (int w = 0; w < P / 8 && d == 0; ++w) {
-              const uint64_t x = o[w], y = me[w];
-              d = x < y ? -1 : x > y ? 1 : 0;
-            }
-          }
-          lower += d < 0;
-          if (d == 0) {
-            c += sj;
-            before += j < t;
-          }
-        }
-      }
-      const bool kept = live && before < (c < 0 ? -c : c);
-      const int place = lower + before;  // distinct over the live terms
-      if (live) keep[place] = kept;
+      const SolRank o = sol_rank(keys, tsign, keep, L, P, t);
       __syncthreads();
 
       // ---- emit into the image that is not the best
       int8_t* const cand = cur ? buf0 : buf1;
       const int extc = cur ? ext0 : ext1;
-      if (kept) {
-        int at = 0;
-        for (int q = 0; q < place; ++q) at += keep[q];
+      if (o.kept) {
         const uint8_t* me = keys + t * P;
-        int8_t* dst = cand + at * A3;
+        int8_t* dst = cand + sol_kept_below(keep, o.place) * A3;
         for (int e = 0; e < A3; ++e) {
-          int v = static_cast<int8_t>(me[(e & ~7) + 7 - (e & 7)] ^ 0x80);
-          if (e >= 2 * S && c < 0) {
+          int v = static_cast<int8_t>(sol_key_flip(me[sol_key_at(e)]));
+          if (e >= 2 * S && o.c < 0) {
             v = 2 * shift - v;
             bad |= v < -128 || v > 127;
           }
           dst[e] = static_cast<int8_t>(v);
         }
       }
-      const int rank = __syncthreads_count(kept);  // (also: the kept terms are in the image, the flags are read)
+      const int rank = __syncthreads_count(o.kept);  // (also: the kept terms are in the image, the flags are read)
       if (__syncthreads_or(bad)) {
         flags |= TG_ORBIT_BAD_NEGATION;
         continue;
@@ -430,35 +392,29 @@ __global__ __launch_bounds__(kBlock) void orbit_fixes_kernel(FixArgs a) {
 namespace {
 
 int orbit_sizes(const char* fn, int64_t M, int K, int S, int shift, int G) {
-  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (K < 1 || K > TG_SOL_MAX_K) return tg_internal_fail(TG_ERR_INVALID, "%s: K=%d outside [1,%d]", fn, K, TG_SOL_MAX_K);
-  if (K * 3 * S > TG_ORBIT_MAX_ROW)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: K*3S=%d above %d", fn, K * 3 * S, TG_ORBIT_MAX_ROW);
-  if (shift < 0 || shift > TG_SOL_MAX_SHIFT)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: shift=%d outside [0,%d]", fn, shift, TG_SOL_MAX_SHIFT);
+  if (const int rc = check_lists(fn, K, S, shift, TG_SOL_MAX_K, TG_ORBIT_MAX_ROW)) return rc;
   if (G < 1 || G > TG_ORBIT_MAX_G) return tg_internal_fail(TG_ERR_INVALID, "%s: G=%d outside [1,%d]", fn, G, TG_ORBIT_MAX_G);
-  if (M < 0 || M > INT64_MAX / (static_cast<int64_t>(TG_SOL_MAX_K) * 3 * TG_MAX_S * TG_MAX_S))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld out of range", fn, (long long)M);
-  return TG_OK;
+  return check_list_count(fn, M);
 }
 
 struct OrbitPlan {
-  int nt, img, region, rec, NS, per;
-  int64_t resident, bytes;
+  int nt, per_cu, img, region, rec, NS, per;
+  int64_t bytes;
 };
 
 // The decomposition for M lists: slices only while M workgroups leave the device idle, and of kOrbMinSlice elements at least.
 OrbitPlan orbit_plan(int64_t M, int K, int S, int G) {
   OrbitPlan p{};
   p.nt = K <= 64 ? 64 : 256;
-  p.resident = static_cast<int64_t>(p.nt == 64 ? 32 : 8) * device_cu_count();
-  p.img = (K * 3 * S + 15) & ~15;
+  p.per_cu = p.nt == 64 ? 32 : 8;
+  const int64_t resident = static_cast<int64_t>(p.per_cu) * device_cu_count();
+  p.img = list_image_bytes(K, S);
   const int P = (3 * S + 7) & ~7;
   p.region = (K * (P > tg::kSolWRow ? P : tg::kSolWRow) + 15) & ~15;
   p.rec = p.img + tg::kOrbHdr;
   int NS = 1;
-  if (M > 0 && M < p.resident) {
-    const int64_t want = p.resident / M, cap = G / tg::kOrbMinSlice;
+  if (M > 0 && M < resident) {
+    const int64_t want = resident / M, cap = G / tg::kOrbMinSlice;
     NS = static_cast<int>(want < cap ? want : cap);
     if (NS < 1) NS = 1;
   }
@@ -473,13 +429,9 @@ int launch_orbit(const tg::OrbArgs& a, const OrbitPlan& p, hipStream_t st) {
   const char* fn = "tg_orbit_canon";
   const size_t lds = 3 * static_cast<size_t>(a.img) + static_cast<size_t>(a.region);
   if (const int rc = lds_opt_in<tg::orbit_canon_kernel<NT>>(fn, lds)) return rc;
-  const int64_t jobs = a.M * a.NS;
-  if (const int rc = launch(fn, tg::orbit_canon_kernel<NT>, static_cast<unsigned>(jobs < p.resident ? jobs : p.resident), NT,
-                            lds, st, a))
-    return rc;
+  if (const int rc = launch_resident(fn, tg::orbit_canon_kernel<NT>, a.M * a.NS, p.per_cu, NT, lds, st, a)) return rc;
   if (a.NS == 1) return TG_OK;
-  const int64_t cap = 32ll * device_cu_count();
-  return launch(fn, tg::orbit_reduce_kernel<64>, static_cast<unsigned>(a.M < cap ? a.M : cap), 64, 0, st, a);
+  return launch_resident(fn, tg::orbit_reduce_kernel<64>, a.M, 32, 64, 0, st, a);
 }
 
 }  // namespace
@@ -509,9 +461,7 @@ extern "C" int tg_orbit_fixes(const int8_t* targets, int64_t M, int S, const uin
   if (!fixes) return tg_internal_fail(TG_ERR_INVALID, "%s: null fixes", fn);
   if (!aligned(status, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: status not 4-byte aligned", fn);
   const tg::FixArgs a{targets, M, sym, fixes, status, S, G};
-  const int64_t cap = 8ll * device_cu_count();
-  return launch(fn, tg::orbit_fixes_kernel, static_cast<unsigned>(M < cap ? M : cap), tg::kBlock, 0,
-                static_cast<hipStream_t>(stream), a);
+  return launch_resident(fn, tg::orbit_fixes_kernel, M, 8, tg::kBlock, 0, static_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int tg_orbit_canon(const int8_t* targets, const int8_t* tokens, const int64_t* lengths, int64_t M, int K, int S,
@@ -521,24 +471,8 @@ extern "C" int tg_orbit_canon(const int8_t* targets, const int8_t* tokens, const
   const char* fn = "tg_orbit_canon";
   if (const int rc = orbit_sizes(fn, M, K, S, shift, G)) return rc;
   if (M == 0) return TG_OK;
-  if (!tokens) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens", fn);
-  if (!lengths) return tg_internal_fail(TG_ERR_INVALID, "%s: null lengths", fn);
-  if (!sym) return tg_internal_fail(TG_ERR_INVALID, "%s: null sym", fn);
-  if (!canon) return tg_internal_fail(TG_ERR_INVALID, "%s: null canon", fn);
-  if (!rank) return tg_internal_fail(TG_ERR_INVALID, "%s: null rank", fn);
-  if (!key) return tg_internal_fail(TG_ERR_INVALID, "%s: null key", fn);
-  if (!which) return tg_internal_fail(TG_ERR_INVALID, "%s: null which", fn);
-  if (!stab) return tg_internal_fail(TG_ERR_INVALID, "%s: null stab", fn);
-  if (!targets && residual_nnz)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: residual_nnz needs targets (both NULL: no verification)", fn);
-  if (canon == tokens) return tg_internal_fail(TG_ERR_INVALID, "%s: canon == tokens: in-place operation is not supported", fn);
-  if (!aligned(lengths, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: lengths not 8-byte aligned", fn);
-  if (!aligned(key, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: key not 8-byte aligned", fn);
-  if (!aligned(rank, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: rank not 4-byte aligned", fn);
-  if (!aligned(residual_nnz, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: residual_nnz not 4-byte aligned", fn);
-  if (!aligned(which, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: which not 4-byte aligned", fn);
-  if (!aligned(stab, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: stab not 4-byte aligned", fn);
-  if (!aligned(status, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: status not 4-byte aligned", fn);
+  const tg::CanonPointers ptrs{targets, tokens, lengths, canon, rank, key, residual_nnz, status, true, sym, which, stab};
+  if (const int rc = check_canon_pointers(fn, ptrs)) return rc;
   OrbitPlan p = orbit_plan(M, K, S, G);
   if (!workspace || p.NS == 1) {
     p.NS = 1;

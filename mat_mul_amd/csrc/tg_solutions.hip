@@ -17,10 +17,12 @@
 //              the image leaves with 16-byte stores where the row is 16-byte aligned, byte stores otherwise.
 // Every output word is a function of its own list; the one atomic is the OR of the sticky bad-row bits into *status,
 // whose value does not depend on the order of the ORs.  No floating point.
+// The verifier, the keys' byte map, the term signs, the rank sort and merge, the kept terms' offsets and the key are the
+// functions of tg_sol_phases.h, which tg_orbits.hip calls too; the host checks the list entries share are tg_lists.h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/tensor_game_solutions.h"
-#include "tg_host.h"
+#include "tg_lists.h"
 #include "tg_sol_copy.h"
 #include "tg_sol_phases.h"
 
@@ -80,18 +82,9 @@ __global__ __launch_bounds__(NT) void solution_canon_kernel(SolArgs a) {
     // ---- verify, from the original terms
     int nnz = 0;
     if (a.residual) {  // (the host refuses residual_nnz without targets)
-      for (int x = t; x < L * kSolWRow; x += NT) {  // (the bytes beyond l = S - 1 only feed entries that are not counted)
-        const int r = x / kSolWRow, l = x - r * kSolWRow;
-        wq[x] = l < S ? tok[r * A3 + 2 * S + l] : static_cast<int8_t>(0);
-      }
+      sol_stage_w<NT>(tok, wq, L, S, t);
       __syncthreads();
-      const int8_t* target = a.targets + m * N3;
-      switch ((S + 7) / 8) {  // uniform
-        case 1: nnz = sol_residual_nnz<NT, 1>(tok, wq, target, L, S, shift, t); break;
-        case 2: nnz = sol_residual_nnz<NT, 2>(tok, wq, target, L, S, shift, t); break;
-        case 3: nnz = sol_residual_nnz<NT, 3>(tok, wq, target, L, S, shift, t); break;
-        default: nnz = sol_residual_nnz<NT, 4>(tok, wq, target, L, S, shift, t); break;
-      }
+      nnz = sol_verify<NT>(tok, wq, a.targets + m * N3, L, S, shift, t);
     }
     __syncthreads();  // the verifier is done with the original bytes
 
@@ -111,82 +104,44 @@ __global__ __launch_bounds__(NT) void solution_canon_kernel(SolArgs a) {
       fcode[q] = code;
     }
     __syncthreads();
-    int bad = 0;
-    if (t < L) {
-      const int c0 = fcode[3 * t], c1 = fcode[3 * t + 1], c2 = fcode[3 * t + 2];
-      const bool live = (c0 & 3) && (c1 & 3) && (c2 & 3);
-      const int flips = ((c0 & 3) == 2) + ((c1 & 3) == 2) + ((c2 & 3) == 2);
-      tsign[t] = live ? ((flips & 1) ? -1 : 1) : 0;
-      bad = live && ((c0 | c1 | c2) & 4);
-    }
-    // The sort keys: the normalised terms again, P = 3S rounded up to 8 bytes apart in the canon image and the w rows
-    // behind it (both idle here: K * P <= img + K * kSolWRow), every byte with its sign bit flipped and every 8 bytes
-    // reversed, so that comparing the 8-byte words as unsigned integers compares the values as signed, in order.
+    int bad = sol_term_sign(fcode, tsign, L, t);
+    // The sort keys (tg_sol_phases.h): the normalised terms again, P = 3S rounded up to 8 bytes apart in the canon image
+    // and the w rows behind it (both idle here: K * P <= img + K * kSolWRow).
     const int P = (A3 + 7) & ~7;
     for (int x = t; x < L * P; x += NT) {
       const int r = x / P, e = x - r * P;
-      out[r * P + (e & ~7) + 7 - (e & 7)] = e < A3 ? static_cast<int8_t>(tok[r * A3 + e] ^ 0x80) : static_cast<int8_t>(0);
+      out[r * P + sol_key_at(e)] = static_cast<int8_t>(e < A3 ? sol_key_flip(tok[r * A3 + e]) : 0);
     }
     __syncthreads();
 
     // ---- order and merge: thread t = term t (K <= NT)
-    const bool live = t < L && tsign[t] != 0;
-    int lower = 0, before = 0, c = 0;
-    if (live) {
-      const uint64_t* me = reinterpret_cast<const uint64_t*>(out + t * P);
-      for (int j = 0; j < L; ++j) {
-        const int sj = tsign[j];
-        if (sj == 0) continue;
-        int d = 0;
-        if (j != t) {
-          const uint64_t* o = reinterpret_cast<const uint64_t*>(out + j * P);
-          for (int w = 0; w < P / 8 && d == 0; ++w) {
-            const uint64_t x = o[w], y = me[w];
-            d = x < y ? -1 : x > y ? 1 : 0;
-          }
-        }
-        lower += d < 0;
-        if (d == 0) {
-          c += sj;
-          before += j < t;
-        }
-      }
-    }
-    const bool kept = live && before < (c < 0 ? -c : c);
-    const int place = lower + before;  // distinct over the live terms
-    if (live) keep[place] = kept;
+    const SolRank o = sol_rank(reinterpret_cast<const uint8_t*>(out), tsign, keep, L, P, t);
     __syncthreads();  // the sort keys are read
     for (int q = t; q < (a.img + K * kSolWRow) / 16; q += NT) reinterpret_cast<uint4*>(out)[q] = uint4{0, 0, 0, 0};
     __syncthreads();
-    if (kept) {
-      int at = 0;
-      for (int q = 0; q < place; ++q) at += keep[q];
+    if (o.kept) {
       const int8_t* me = tok + t * A3;
-      int8_t* dst = out + at * A3;
+      int8_t* dst = out + sol_kept_below(keep, o.place) * A3;
       for (int e = 0; e < 2 * S; ++e) dst[e] = me[e];
       for (int e = 2 * S; e < A3; ++e) {
-        const int v = c < 0 ? 2 * shift - me[e] : me[e];
+        const int v = o.c < 0 ? 2 * shift - me[e] : me[e];
         bad |= v < -128 || v > 127;
         dst[e] = static_cast<int8_t>(v);
       }
     }
-    const int rank = __syncthreads_count(kept);  // (also: the image is complete, the flags are read)
+    const int rank = __syncthreads_count(o.kept);  // (also: the image is complete, the flags are read)
     if (__syncthreads_or(bad)) {
       sol_bad_row<NT>(a, m, n_row, TG_SOL_BAD_NEGATION, t);
       continue;
     }
 
     // ---- key, outputs
-    const int n = rank * A3, words = (n + 7) / 8;  // the image is zero beyond n: the padding of the last word
-    uint64_t h = 0;
-    for (int k = t; k < words; k += NT)
-      h += fmix64(reinterpret_cast<const uint64_t*>(out)[k] + static_cast<uint64_t>(k + 1) * 0x9E3779B97F4A7C15ull);
-    h = sol_block_sum<NT>(h, red, t);
+    const uint64_t key = sol_image_key<NT>(out, rank * A3, red, t);
     const uint64_t total = sol_block_sum<NT>(static_cast<uint64_t>(nnz), red, t);
     sol_copy_out<NT>(a.canon + m * n_row, out, n_row, t);
     if (t == 0) {
       a.rank[m] = rank;
-      a.key[m] = hash_finish(h, n);
+      a.key[m] = key;
       if (a.residual) a.residual[m] = static_cast<int32_t>(total);
     }
     __syncthreads();  // the images, the w rows and the flags are free for the next list
@@ -198,20 +153,14 @@ __global__ __launch_bounds__(NT) void solution_canon_kernel(SolArgs a) {
 namespace {
 
 int solution_sizes(const char* fn, int64_t M, int K, int S, int shift) {
-  if (S < 1 || S > TG_MAX_S) return tg_internal_fail(TG_ERR_INVALID, "%s: S=%d outside [1,%d]", fn, S, TG_MAX_S);
-  if (K < 1 || K > TG_SOL_MAX_K) return tg_internal_fail(TG_ERR_INVALID, "%s: K=%d outside [1,%d]", fn, K, TG_SOL_MAX_K);
-  if (shift < 0 || shift > TG_SOL_MAX_SHIFT)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: shift=%d outside [0,%d]", fn, shift, TG_SOL_MAX_SHIFT);
-  if (M < 0 || M > INT64_MAX / (static_cast<int64_t>(TG_SOL_MAX_K) * 3 * TG_MAX_S * TG_MAX_S))
-    return tg_internal_fail(TG_ERR_INVALID, "%s: M=%lld out of range", fn, (long long)M);
-  return TG_OK;
+  if (const int rc = check_lists(fn, K, S, shift, TG_SOL_MAX_K)) return rc;
+  return check_list_count(fn, M);
 }
 
 template <int NT>
 int launch_solution(const tg::SolArgs& a, int per_cu, hipStream_t st) {
-  const int64_t resident = static_cast<int64_t>(per_cu) * device_cu_count();
-  return launch("tg_solution_canon", tg::solution_canon_kernel<NT>, static_cast<unsigned>(a.M < resident ? a.M : resident),
-                NT, 2 * static_cast<size_t>(a.img) + static_cast<size_t>(a.K) * tg::kSolWRow, st, a);
+  return launch_resident("tg_solution_canon", tg::solution_canon_kernel<NT>, a.M, per_cu, NT,
+                         2 * static_cast<size_t>(a.img) + static_cast<size_t>(a.K) * tg::kSolWRow, st, a);
 }
 
 }  // namespace
@@ -226,20 +175,8 @@ extern "C" int tg_solution_canon(const int8_t* targets, const int8_t* tokens, co
   const char* fn = "tg_solution_canon";
   if (const int rc = solution_sizes(fn, M, K, S, shift)) return rc;
   if (M == 0) return TG_OK;
-  if (!tokens) return tg_internal_fail(TG_ERR_INVALID, "%s: null tokens", fn);
-  if (!lengths) return tg_internal_fail(TG_ERR_INVALID, "%s: null lengths", fn);
-  if (!canon) return tg_internal_fail(TG_ERR_INVALID, "%s: null canon", fn);
-  if (!rank) return tg_internal_fail(TG_ERR_INVALID, "%s: null rank", fn);
-  if (!key) return tg_internal_fail(TG_ERR_INVALID, "%s: null key", fn);
-  if (!targets && residual_nnz)
-    return tg_internal_fail(TG_ERR_INVALID, "%s: residual_nnz needs targets (both NULL: no verification)", fn);
-  if (canon == tokens) return tg_internal_fail(TG_ERR_INVALID, "%s: canon == tokens: in-place operation is not supported", fn);
-  if (!aligned(lengths, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: lengths not 8-byte aligned", fn);
-  if (!aligned(key, 8)) return tg_internal_fail(TG_ERR_INVALID, "%s: key not 8-byte aligned", fn);
-  if (!aligned(rank, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: rank not 4-byte aligned", fn);
-  if (!aligned(residual_nnz, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: residual_nnz not 4-byte aligned", fn);
-  if (!aligned(status, 4)) return tg_internal_fail(TG_ERR_INVALID, "%s: status not 4-byte aligned", fn);
-  const int img = (K * 3 * S + 15) & ~15;  // at most 24 KiB: two images, 8 KiB of w rows and the static LDS stay below 64 KiB
+  if (const int rc = check_canon_pointers(fn, {targets, tokens, lengths, canon, rank, key, residual_nnz, status})) return rc;
+  const int img = list_image_bytes(K, S);  // two images, 8 KiB of w rows and the static LDS stay below 64 KiB
   const tg::SolArgs a{targets, tokens, lengths, M, canon, rank, key, residual_nnz, status, K, S, shift, img};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (K <= 64) return launch_solution<64>(a, 32, st);  // a wavefront per list

@@ -625,6 +625,47 @@ def symmetry_apply(state_i8, action_i8, sym, dtype=torch.float32, shift: int = 1
     return out, actions_out
 
 
+def _list_shape(tokens, fn: str, name: str = "tokens", lead: str = "M") -> Tuple[int, int, int]:
+    """(M, K, S) of the tokens int8 (M,K,3S) of M action lists."""
+    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
+        raise TensorGameError(fn, -1, f"{name} must be int8 ({lead},K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+    return tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+
+
+def _list_tokens(tokens, fn: str):
+    """(tokens made contiguous, M, K, S, device) of M action lists on a ROCm device."""
+    _need_gpu(tokens, "tokens")
+    return (tokens if tokens.is_contiguous() else tokens.contiguous(), *_list_shape(tokens, fn), tokens.device)
+
+
+def _list_lengths(lengths, M: int, dev) -> torch.Tensor:
+    _need_gpu(lengths, "lengths")
+    return _flag(lengths, (M,), torch.int64, dev, "lengths")
+
+
+def _list_targets(targets, residual_nnz, M: int, S: int, dev, fn: str):
+    """The targets of the canon entries, made contiguous; None (no verification) refuses a ``residual_nnz`` output."""
+    if targets is None:
+        if residual_nnz is not None:
+            raise TensorGameError(fn, -1, "residual_nnz needs targets")
+        return None
+    _need_gpu(targets, "targets")
+    if targets.dtype != torch.int8 or tuple(targets.shape) != (M, S, S, S) or targets.device != dev:
+        raise TensorGameError(fn, -1, f"targets must be int8 {(M, S, S, S)} on {dev}, got {targets.dtype} "
+                                      f"{tuple(targets.shape)} on {targets.device}")
+    return targets if targets.is_contiguous() else targets.contiguous()
+
+
+def _canon_outputs(canon, rank, key, residual_nnz, verify: bool, M: int, K: int, S: int, dev):
+    """(canon, rank, key, residual_nnz) of the canon entries; residual_nnz only with targets (``verify``)."""
+    canon = _out(canon, (M, K, 3 * S), torch.int8, dev, "canon")
+    rank = _out(rank, (M,), torch.int32, dev, "rank")
+    key = _out(key, (M,), torch.int64, dev, "key")
+    if verify:
+        residual_nnz = _out(residual_nnz, (M,), torch.int32, dev, "residual_nnz")
+    return canon, rank, key, residual_nnz
+
+
 def solution_check(M: int, K: int, S: int, shift: int = 1) -> None:
     """Raise TensorGameError (naming the argument) unless tg_solution_canon takes these sizes.  Host only."""
     call("tg_solution_check", int(M), int(K), int(S), int(shift))
@@ -640,29 +681,11 @@ def solution_canon(targets, tokens, lengths, shift: int = 1, canon=None, rank=No
     negation that leaves int8 is all zero, with rank 0, key 0 and residual_nnz -1, and sets bit 0 / bit 1 of ``status``
     uint32 (1,).  No host sync."""
     fn = "solution_canon"
-    _need_gpu(tokens, "tokens")
-    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
-    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
-    dev = tokens.device
+    tokens, M, K, S, dev = _list_tokens(tokens, fn)
     solution_check(M, K, S, shift)
-    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
-    if targets is not None:
-        _need_gpu(targets, "targets")
-        if targets.dtype != torch.int8 or tuple(targets.shape) != (M, S, S, S) or targets.device != dev:
-            raise TensorGameError(fn, -1, f"targets must be int8 {(M, S, S, S)} on {dev}, got {targets.dtype} "
-                                          f"{tuple(targets.shape)} on {targets.device}")
-        targets = targets if targets.is_contiguous() else targets.contiguous()
-    elif residual_nnz is not None:
-        raise TensorGameError(fn, -1, "residual_nnz needs targets")
-    _need_gpu(lengths, "lengths")
-    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
-        raise TensorGameError(fn, -1, "lengths must be given")
-    canon = _out(canon, (M, K, 3 * S), torch.int8, dev, "canon")
-    rank = _out(rank, (M,), torch.int32, dev, "rank")
-    key = _out(key, (M,), torch.int64, dev, "key")
-    if targets is not None:
-        residual_nnz = _out(residual_nnz, (M,), torch.int32, dev, "residual_nnz")
+    targets = _list_targets(targets, residual_nnz, M, S, dev, fn)
+    lengths = _list_lengths(lengths, M, dev)
+    canon, rank, key, residual_nnz = _canon_outputs(canon, rank, key, residual_nnz, targets is not None, M, K, S, dev)
     status = _flag(status, (1,), torch.uint32, dev, "status")
     _launch(dev, "tg_solution_canon", _ptr(targets), _ptr(tokens), _ptr(lengths), M, K, S, int(shift), _ptr(canon),
             _ptr(rank), _ptr(key), _ptr(residual_nnz), _ptr(status))
@@ -718,32 +741,14 @@ def orbit_canon(targets, tokens, lengths, sym, shift: int = 1, canon=None, rank=
     for (uint8, a small batch is then spread over the device: two launches), False uses none (one launch), or a uint8
     tensor of that size.  The outputs do not depend on it.  No host sync."""
     fn = "orbit_canon"
-    _need_gpu(tokens, "tokens")
-    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
-    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
-    dev = tokens.device
+    tokens, M, K, S, dev = _list_tokens(tokens, fn)
     sym = _group_rows(sym, S, dev, fn)
     G = sym.shape[0]
     orbit_check(M, K, S, shift, G)
-    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
-    if targets is not None:
-        _need_gpu(targets, "targets")
-        if targets.dtype != torch.int8 or tuple(targets.shape) != (M, S, S, S) or targets.device != dev:
-            raise TensorGameError(fn, -1, f"targets must be int8 {(M, S, S, S)} on {dev}, got {targets.dtype} "
-                                          f"{tuple(targets.shape)} on {targets.device}")
-        targets = targets if targets.is_contiguous() else targets.contiguous()
-    elif residual_nnz is not None:
-        raise TensorGameError(fn, -1, "residual_nnz needs targets")
-    _need_gpu(lengths, "lengths")
-    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
-        raise TensorGameError(fn, -1, "lengths must be given")
-    canon = _out(canon, (M, K, 3 * S), torch.int8, dev, "canon")
-    rank = _out(rank, (M,), torch.int32, dev, "rank")
-    key = _out(key, (M,), torch.int64, dev, "key")
-    if targets is not None:
-        residual_nnz = _out(residual_nnz, (M,), torch.int32, dev, "residual_nnz")
-    which = _out(which, (M,), torch.int32, dev, "which")
+    targets = _list_targets(targets, residual_nnz, M, S, dev, fn)
+    lengths = _list_lengths(lengths, M, dev)
+    canon, rank, key, residual_nnz = _canon_outputs(canon, rank, key, residual_nnz, targets is not None, M, K, S, dev)
+    which =_out(which, (M,), torch.int32, dev, "which")
     stab = _out(stab, (M,), torch.int32, dev, "stab")
     status = _flag(status, (1,), torch.uint32, dev, "status")
     if workspace is False:
@@ -818,9 +823,7 @@ def solution_rebase(tokens, lengths, mats, index=None, shift: int = 1, tokens_ou
     this carries lists found in a changed basis back; with ``BasisSet.forward`` it moves known lists into it.
     ``bad=False`` passes no flag buffer.  Out of place; no host sync."""
     fn = "solution_rebase"
-    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
-    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
+    M, K, S = _list_shape(tokens, fn)  # (this entry checks every shape before any device, in words of its own)
     if mats.dtype != torch.int32 or mats.dim() != 4 or tuple(mats.shape[1:]) != (3, S, S):
         raise TensorGameError(fn, -1, f"mats must be int32 (G,3,{S},{S}), got {mats.dtype} {tuple(mats.shape)}")
     G = mats.shape[0]
@@ -1137,8 +1140,8 @@ def replay_add_lists(buf, starts, tokens, lengths, groups=None, shift: int = 1, 
     if tokens.dim() != 3:
         raise TensorGameError("replay_add_lists", -1, f"tokens must be int8 (M,K,3S), got {tuple(tokens.shape)}")
     M, K = tokens.shape[0], tokens.shape[1]
-    tokens = _tokens(tokens, (M, K), buf.S, dev, "tokens")
-    lengths = _flag(lengths, (M,), torch.int64, dev, "lengths")
+    tokens = _tokens(tokens, (M, K), buf.S, dev, "tokens")  # (S is the buffer's here, and the words are _tokens's)
+    lengths = _list_lengths(lengths, M, dev)
     if groups is None:
         if M > G:
             raise TensorGameError("replay_add_lists", -1, f"groups: without it list m starts from starts[m], but M={M} "
@@ -1658,15 +1661,8 @@ def flip_begin(tokens, lengths, src=None, bound: int = 1, shift: int = 1, status
     int64 (W,) (any of them may be passed in by name).  A bad row (length outside [0,K]: bit 0 of ``status`` uint32 (1,);
     a factor value outside [-bound,bound]: bit 1; a ``src`` outside [0,M): bit 2) gets state -1.  No host sync."""
     fn = "flip_begin"
-    _need_gpu(tokens, "tokens")
-    if tokens.dtype != torch.int8 or tokens.dim() != 3 or tokens.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"tokens must be int8 (M,K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
-    M, K, S = tokens.shape[0], tokens.shape[1], tokens.shape[2] // 3
-    dev = tokens.device
-    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
-    _need_gpu(lengths, "lengths")
-    if _flag(lengths, (M,), torch.int64, dev, "lengths") is None:
-        raise TensorGameError(fn, -1, "lengths must be given")
+    tokens, M, K, S, dev = _list_tokens(tokens, fn)
+    lengths = _list_lengths(lengths, M, dev)
     W = M
     if src is not None:
         _need_gpu(src, "src")
@@ -1689,9 +1685,7 @@ def flip_advance(st: dict, n_steps: int, bound: int = 1, shift: int = 1, seed: i
     fn = "flip_advance"
     cur = st["cur"]
     _need_gpu(cur, "cur")
-    if cur.dtype != torch.int8 or cur.dim() != 3 or cur.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"cur must be int8 (W,K,3S), got {cur.dtype} {tuple(cur.shape)}")
-    W, K, S = cur.shape[0], cur.shape[1], cur.shape[2] // 3
+    W, K, S = _list_shape(cur, fn, "cur", "W")
     flip_check(0, W, K, S, shift, bound, step0, n_steps)
     st = _flip_state({name: st[name] for name, _ in _FLIP_STATE}, W, K, S, cur.device, fn)
     _launch(cur.device, "tg_flip_advance", *[_ptr(st[name]) for name, _ in _FLIP_STATE], W, K, S, int(shift), int(bound),
@@ -1716,9 +1710,7 @@ def flip_advance_plus(st: dict, n_steps: int, plus_after: int, plus_slack: int =
     fn = "flip_advance_plus"
     cur = st["cur"]
     _need_gpu(cur, "cur")
-    if cur.dtype != torch.int8 or cur.dim() != 3 or cur.shape[2] % 3:
-        raise TensorGameError(fn, -1, f"cur must be int8 (W,K,3S), got {cur.dtype} {tuple(cur.shape)}")
-    W, K, S = cur.shape[0], cur.shape[1], cur.shape[2] // 3
+    W, K, S = _list_shape(cur, fn, "cur", "W")
     flip_plus_check(W, K, S, shift, bound, step0, n_steps, plus_after, plus_slack)
     for name in ("since", "pluses"):
         if st.get(name) is None:
