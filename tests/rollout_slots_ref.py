@@ -1,6 +1,7 @@
 """numpy restatement of the solution search over a queue of start states (tg_rollout_advance_slots and tg_rollout_refill
 of include/tensor_game_rollout_slots.h, ``solve_stream`` of mat_mul_amd/rollout.py), on top of tests/rollout_ref.py and
-tests/rollout_masked_ref.py.  Shared by test_rollout_slots_cpu.py and test_gpu_rollout_slots.py."""
+tests/rollout_masked_ref.py.  Shared by test_rollout_slots_cpu.py, test_gpu_rollout_slots.py and
+test_gpu_rollout_sizes.py; the case tables of those tests are in rollout_slots_cases.py."""
 import copy
 
 import numpy as np

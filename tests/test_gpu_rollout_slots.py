@@ -14,6 +14,7 @@ from guarded_buffers import CANARY, GUARD
 from net_ref import CONFIGS as CONFIGS_S4, P, make_weights
 from net_s9_ref import CONFIGS as CONFIGS_S9
 from rollout_ref import strassen_scripts
+from rollout_slots_cases import ADVANCE_CASES, REFILL_CASES, REFILL_SEED, RefillRun, advance_launches, check_advance
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -66,137 +67,71 @@ def same_slots(ds, sl, what):
 
 
 # ---- the step against the restatement -------------------------------------------------------------------------------
-EMPTY, SOLVED, EXHAUSTED, LIVE0, LIVE2, LIVE_LAST = range(6)
-
-# (S, T, n, R, misalign): many small groups per workgroup; the dword path with a 3-byte tail, misaligned frames; S = 9;
-# one group per workgroup with 16-byte items; T = 8
-ADVANCE_CASES = [(4, 2, 4, 37, 0), (3, 1, 1, 9, 1), (9, 3, 3, 7, 0), (16, 2, 64, 2, 0), (5, 8, 2, 6, 0)]
+def run_advance(sl, tokens, misalign, shift, what):
+    """One launch on guarded copies of ``sl`` and ``tokens`` beside the restatement (which steps ``sl`` in place): every
+    slot buffer equal, the tokens as they were, no guard touched.  Returns the device slots and their guard buffers."""
+    bufs, ds = device_slots(sl, misalign)
+    buf_tok, d_tok = guarded_from(tokens)
+    SR.advance_slots(sl, tokens, shift)
+    ops.rollout_advance_slots(ds, d_tok, shift=shift)
+    same_slots(ds, sl, what)
+    assert np.array_equal(host(d_tok), tokens)
+    for name, buf in (*bufs.items(), ("tokens in", buf_tok)):
+        check_guards(buf, misalign if name == "frames" else 0, name)
+    return bufs, ds
 
 
 @pytest.mark.parametrize("S,T,n,R_,misalign", ADVANCE_CASES)
 def test_advance_slots_equals_the_restatement(S, T, n, R_, misalign):
     rng = np.random.default_rng(1000 * S + 10 * n + R_)
-    K, dim_s, B = 4, 2, R_ * n
     seen = set()
-    for rot in range(0, 6, min(R_, 6)):      # R < 6: as many launches as it takes to meet all six kinds of slot
-        kinds = (np.arange(R_) + rot) % 6
+    for rot, kinds, sl, tokens in advance_launches(S, T, n, R_, rng):   # R < 6: as many launches as all six kinds take
         seen |= set(kinds.tolist())
-        sl = SR.Slots(R_, n, S, T, dim_s, K)
-        sl.frames[:] = rng.integers(-2, 3, size=sl.frames.shape)
-        sl.scalars[:] = rng.integers(0, 5, size=sl.scalars.shape)
-        sl.nnz[:] = rng.integers(1, 9, size=B)
-        sl.active[:] = rng.integers(0, 2, size=B)
-        sl.actions[:] = rng.integers(0, 3, size=sl.actions.shape)
-        sl.rows[:] = np.arange(B) + 11
-        sl.best_nnz[:] = rng.integers(1, S ** 3, size=R_)
-        sl.slot_state[:] = np.where(kinds == EMPTY, -1, rng.integers(0, 50, size=R_))
-        sl.solved_step[:] = np.where(kinds == SOLVED, 1, -1)
-        sl.solved_sample[:] = np.where(kinds == SOLVED, 0, -1)
-        sl.hits[:] = kinds == SOLVED
-        sl.slot_step[:] = np.choose(kinds, [1, 2, K, 0, 2, K - 1])
-        tokens = rng.integers(0, 3, size=(B, 3 * S)).astype(np.int8)
-        for g in np.nonzero(kinds == LIVE2)[0]:   # solved by this step: the head is the tensor of the row's action
-            b = g * n + g % n
-            tokens[b] = rng.choice([0, 2], size=3 * S)
-            sl.frames[b, 0] = np.asarray(R.O.action_to_tensor(tokens[b][None], 1))[0]
-        live = np.repeat(SR.live_slots(sl), n)
-        assert np.array_equal(SR.live_slots(sl), kinds >= LIVE0)
-        tokens[~live] = 127                       # what a row that is not live offers must not be read
-        bufs, ds = device_slots(sl, misalign)
-        buf_tok, d_tok = guarded_from(tokens)
         before = sl.copy()
-        SR.advance_slots(sl, tokens, 1)
-        ops.rollout_advance_slots(ds, d_tok, shift=1)
-        same_slots(ds, sl, rot)
-        assert np.array_equal(host(d_tok), tokens)
-        for name, buf in (*bufs.items(), ("tokens in", buf_tok)):
-            check_guards(buf, misalign if name == "frames" else 0, name)
-        # what the restatement must have done for the cases to mean anything
-        gl = kinds >= LIVE0
-        assert np.array_equal(sl.slot_step[gl], before.slot_step[gl] + 1)
-        assert np.array_equal(sl.slot_step[~gl], before.slot_step[~gl])
-        assert (sl.solved_step[kinds == LIVE2] == 2).all() and (sl.solved_sample[kinds == LIVE2] ==
-                                                                 (np.arange(R_) % n)[kinds == LIVE2]).all()
-        assert np.array_equal(sl.frames[~live], before.frames[~live])
-        assert not live.any() or (sl.frames[live] != before.frames[live]).any()
+        run_advance(sl, tokens, misalign, 1, rot)
+        check_advance(kinds, n, before, sl)     # what the restatement must have done for the cases to mean anything
     assert seen == set(range(6))
 
 
 # ---- the refill against the restatement ---------------------------------------------------------------------------------
-# (S, T, n, R, N, K, first_state, misalign): 16-byte copies; R = 1 on the dword path (27-byte rows); 729*T-byte rows and
-# n = 64; R crosses a scan thread's 64 slots and the queue runs dry inside a tick; R > N; R crosses wavefronts; the
-# maximum R; misaligned frames at S = 4 (the dword path without a tail)
-REFILL_CASES = [(4, 2, 4, 5, 40, 4, 7, 0), (3, 1, 1, 1, 6, 3, 0, 0), (9, 3, 64, 3, 7, 2, 3, 0),
-                (3, 2, 4, 65, 100, 3, 1, 1), (4, 1, 2, 9, 4, 3, 5, 0), (2, 1, 1, 5000, 12000, 3, 2, 0),
-                (1, 1, 1, 65536, 100000, 2, 0, 0), (4, 2, 2, 6, 20, 3, 0, 4)]
-
-
-def play(sl, rng):
-    """What some steps of the search could leave behind: about half of the occupied slots solved, some exhausted, the
-    others somewhere on their way, with arbitrary records, actions, counts and a few overflow flags."""
-    R_, n, K, B = len(sl.slot_state), sl.n, sl.K, len(sl.nnz)
-    held = sl.slot_state >= 0
-    fate = rng.integers(0, 4, size=R_)           # 0, 1: solved; 2: exhausted; 3: on its way
-    solved, done = held & (fate <= 1), held & (fate == 2)
-    sl.slot_step[held] = rng.integers(1, K, size=int(held.sum())) if K > 1 else 1
-    sl.slot_step[done] = K
-    sl.solved_step[solved] = sl.slot_step[solved] - 1
-    sl.slot_step[solved & (fate == 1)] = K       # solved by its last step
-    sl.solved_step[solved & (fate == 1)] = K - 1
-    sl.solved_sample[solved] = rng.integers(0, n, size=int(solved.sum()))
-    sl.hits[solved] = 1
-    sl.best_nnz[held] = np.where(solved, 0, rng.integers(1, sl.S ** 3 + 1, size=R_))[held]
-    sl.actions[:] = rng.integers(1, 4, size=sl.actions.shape)
-    sl.nnz[:] = rng.integers(0, 9, size=B)
-    sl.overflow[:] = rng.integers(0, 8, size=B) == 0
-    sl.frames[:] = rng.integers(-2, 3, size=sl.frames.shape)
-    sl.scalars[:] += 1
-
-
 @pytest.mark.parametrize("S,T,n,R_,N,K,first_state,misalign", REFILL_CASES)
 def test_refill_equals_the_restatement(S, T, n, R_, N, K, first_state, misalign):
-    rng = np.random.default_rng(S + 10 * n + R_)
-    dim_s, seed = 2, 0x1234567887654321
-    q_states = rng.integers(-2, 3, size=(N, T, S, S, S)).astype(np.int8)
-    q_scalars = rng.integers(0, 9, size=(N, dim_s)).astype(np.float32)
-    buf_qs, d_qs = guarded_from(q_states, misalign)
-    buf_qc, d_qc = guarded_from(q_scalars)
-    sl, out = SR.Slots(R_, n, S, T, dim_s, K), SR.Out(N, S, K, fill=77)
-    sl.uniforms[:] = 2.0                         # no draw is 2: the rows that get none keep it
+    run = run_refill(S, T, n, R_, N, K, first_state, misalign)
+    if (R_, N) in ((65, 100), (9, 4)):
+        assert run.dry or R_ > N                  # the queue ran dry inside a tick / could never fill the slots
+
+
+def run_refill(S, T, n, R_, N, K, first_state, misalign, after_tick=None):
+    """The three ticks of a refill case on the device beside the restatement's (rollout_slots_cases.RefillRun), every
+    buffer guarded, then one refill without uniforms; ``after_tick(tick, device slots, run)`` sees every tick."""
+    run = RefillRun(S, T, n, R_, N, K, first_state, misalign)
+    sl, out, seed = run.slots, run.out, REFILL_SEED
+    buf_qs, d_qs = guarded_from(run.q_states, misalign)
+    buf_qc, d_qc = guarded_from(run.q_scalars)
     out_bufs, d_out = zip(*[guarded_from(getattr(out, name)) for name in SR.OUT_FIELDS])
-    dry = False
-    for tick in range(3):
-        if tick:
-            play(sl, rng)
-        wanting = int(((sl.slot_state < 0) | (sl.solved_step >= 0) | (sl.slot_step >= K)).sum())
-        dry |= 0 < N - int(sl.head[0]) < wanting
-        bufs, ds = device_slots(sl, misalign)
-        SR.refill(sl, out, q_states, q_scalars, seed, first_state, True)
+    for tick, before in run.ticks():
+        bufs, ds = device_slots(before, misalign)
         ops.rollout_refill(ds, d_qs, d_qc, d_out, seed=seed, first_state=first_state)
         same_slots(ds, sl, tick)
         for name, t in zip(SR.OUT_FIELDS, d_out):
             assert np.array_equal(host(t), getattr(out, name)), (name, tick)
         for name, buf in bufs.items():
             check_guards(buf, misalign if name == "frames" else 0, name)
-        holds = sl.slot_state >= 0
-        assert sl.live[0] == holds.sum() and np.array_equal(sl.active, np.repeat(holds, n))
-        assert (sl.rows[np.repeat(holds, n)] >= first_state * n).all() and (sl.rows[~np.repeat(holds, n)] == -1).all()
-        assert (sl.uniforms[np.repeat(holds, n)] < 1).all()
+        if after_tick:
+            after_tick(tick, ds, run)
     for name, buf in (*zip(SR.OUT_FIELDS, out_bufs), ("q_states", buf_qs), ("q_scalars", buf_qc)):
         check_guards(buf, misalign if name == "q_states" else 0, name)
-    assert np.array_equal(host(d_qs), q_states)
-    assert 0 < sl.head[0] <= N
-    if (R_, N) in ((65, 100), (9, 4)):
-        assert dry or R_ > N                      # the queue ran dry inside a tick / could never fill the slots
-    assert (out.best_nnz != 77).any() and (out.tokens[out.solved_step == 77] == 77).all()
+    assert np.array_equal(host(d_qs), run.q_states)
+    run.check_end()
     # without uniforms: the same, and the uniforms stay as they are
     bufs, ds = device_slots(sl, misalign)
     ds.head.zero_()
     ds.slot_state.fill_(-1)
     sl.head[:], sl.slot_state[:] = 0, -1
-    SR.refill(sl, out, q_states, q_scalars, seed, first_state, False)
+    SR.refill(sl, out, run.q_states, run.q_scalars, seed, first_state, False)
     ops.rollout_refill(ds, d_qs, d_qc, d_out, seed=seed, first_state=first_state, uniforms=False)
     same_slots(ds, sl, "no uniforms")
+    return run
 
 
 # ---- table policies through solve_stream --------------------------------------------------------------------------------
@@ -278,17 +213,17 @@ def test_solve_stream_ticks_and_empty_dataset(golden):
 
 
 # ---- the fused network ------------------------------------------------------------------------------------------------
-def fused_setup(name, G):
+def fused_setup(name, G, configs=NET_CONFIGS, cls=FusedAlphaTensor):
     """The arrangement of test_gpu_rollout_masked.py: a network that depends on its input and likes the zero factor
     (the last layer of the policy head scaled down, its bias favouring the token of 0), so a row plays the null action
     often and a start state that is zero is solved by it at once; every third start state is zero, the others hold
     random entries."""
-    cfg = NET_CONFIGS[name]
+    cfg = configs[name]
     sd = make_weights(cfg, 77)
     sd[P + "li1.weight"] = sd[P + "li1.weight"] * 0.25
     assert cfg["n_logits"] == 3                                  # tokens 0, 1, 2 are the factors -1, 0, 1
     sd[P + "li1.bias"] = np.array([0.0, 3.0, 0.0], np.float32)
-    net = FusedAlphaTensor.from_state_dict(sd, cfg["n_samples"], device=DEV)
+    net = cls.from_state_dict(sd, cfg["n_samples"], device=DEV)
     S, T = cfg["dim_3d"], cfg["dim_t"]
     rng = np.random.default_rng(S)
     states = np.zeros((G, T, S, S, S), np.int8)

@@ -1,8 +1,8 @@
 """CPU checks of the solution search over a queue of start states: the C ABI of include/tensor_game_rollout_slots.h
 (declared, bound, exported; the host checks of both entries through ctypes, in their order), the property that makes
 the feature checkable -- per start state the refilled search finds exactly what the chunked one finds, for every number
-of slots -- between the numpy restatements (tests/rollout_slots_ref.py) on the recorded factorisations, and the argument
-errors of solve_stream."""
+of slots -- between the numpy restatements (tests/rollout_slots_ref.py) on the recorded factorisations, what the case
+tables of the GPU tests (tests/rollout_slots_cases.py) are there for, and the argument errors of solve_stream."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -13,6 +13,7 @@ import pytest
 from mat_mul_amd import _lib
 
 import rollout_ref as R
+import rollout_slots_cases as CS
 import rollout_slots_ref as SR
 from rollout_ref import demo_cases, strassen_scripts
 
@@ -219,6 +220,75 @@ def test_restated_uniforms_follow_the_sampling_rule():
     assert sl.live[0] == 2 and sl.head[0] == 2 and list(sl.slot_state) == [0, 1, -1]
     assert np.array_equal(sl.uniforms[:4], philox_uniforms(9, np.arange(200, 204), 0, 1, 12).astype(np.float32))
     assert not sl.uniforms[4:].any()
+
+
+# ---- the case tables of the GPU tests, through the restatement alone (tests/rollout_slots_cases.py) -------------------
+@pytest.mark.parametrize("S,T,n,R_,misalign", CS.ADVANCE_CASES + CS.SIZE_CASES)
+def test_advance_cases_meet_all_six_kinds(S, T, n, R_, misalign):
+    rng = np.random.default_rng(1000 * S + 10 * n + R_)
+    seen = set()
+    for rot, kinds, sl, tokens in CS.advance_launches(S, T, n, R_, rng):
+        seen |= set(kinds.tolist())
+        before = sl.copy()
+        SR.advance_slots(sl, tokens, 1)
+        CS.check_advance(kinds, n, before, sl)
+        assert (tokens[np.repeat(kinds < CS.LIVE0, n)] == 127).all()
+    assert seen == set(range(6))
+    gpw = CS.groups_per_workgroup(S, n, R_, misalign)
+    if (S, T, n, R_, misalign) in CS.WIDE_CASES:
+        assert gpw > 64 and R_ > gpw and R_ % gpw           # several scan passes, a partial last workgroup
+    else:
+        assert gpw <= 64
+
+
+def test_planted_case_has_its_live_slots_behind_200_dead_ones():
+    S, T, n, R_, misalign = CS.PLANTED_CASE
+    assert CS.groups_per_workgroup(S, n, R_, misalign) == R_ == 256       # one workgroup, four scan passes
+    kinds = CS.planted_kinds()
+    assert (kinds[:200] < CS.LIVE0).all() and (kinds[200:] >= CS.LIVE0).all() and set(kinds.tolist()) == set(range(6))
+    sl, tokens = CS.advance_inputs(S, T, n, kinds, np.random.default_rng(256))
+    before = sl.copy()
+    SR.advance_slots(sl, tokens, 1)
+    CS.check_advance(kinds, n, before, sl)
+    for name in SR.ROW_FIELDS + SR.SLOT_FIELDS:
+        assert np.array_equal(getattr(sl, name)[:200], getattr(before, name)[:200]), name
+
+
+@pytest.mark.parametrize("S,T,n,R_", CS.OVERFLOW_CASES)
+def test_overflow_cases_flag_some_live_rows_and_not_others(S, T, n, R_):
+    sl, tokens, q_states, q_scalars = CS.overflow_inputs(S, T, n, R_, np.random.default_rng(S + R_))
+    before = sl.copy()
+    SR.advance_slots(sl, tokens, CS.OVERFLOW_SHIFT)
+    CS.check_overflow_step(n, before, sl, tokens)
+    stepped, out = sl.copy(), SR.Out(len(q_states), S, 1, fill=77)
+    SR.refill(sl, out, q_states, q_scalars, 5, 0, True)
+    CS.check_overflow_flush(n, stepped, sl, out)
+
+
+# the new cases whose queue runs dry inside a tick that still has states to hand out: on the 16-byte path at S = 16 and
+# S = 32, on the dword path without a tail, and on the dword path with a tail at S = 25
+DRY_CASES = {(16, 2, 8, 5, 12, 3, 1, 0), (16, 1, 2, 4, 9, 2, 0, 4), (32, 1, 64, 2, 5, 2, 0, 0), (25, 1, 4, 3, 7, 2, 0, 0)}
+assert DRY_CASES <= set(CS.REFILL_SIZE_CASES)
+
+
+@pytest.mark.parametrize("case", [c for c in CS.REFILL_CASES + CS.REFILL_SIZE_CASES if c[3] <= 100])
+def test_refill_cases_run_dry_and_cross_the_key_word(case):
+    S, T, n, R_, N, K, first_state, misalign = case
+    run = CS.RefillRun(*case)
+    for tick, before in run.ticks():
+        if case == CS.KEY_CASE and tick == 0:                # the row keys cross 2^32 inside the first tick
+            want = CS.check_key_crossing(run.slots, n, first_state)
+            assert np.array_equal(run.slots.uniforms, want)
+    run.check_end()
+    if case in DRY_CASES or (R_, N) == (65, 100):
+        assert run.dry
+
+
+def test_refill_size_cases_have_every_tail():
+    tails = sorted(T * S ** 3 % 4 for S, T, *_ in CS.REFILL_SIZE_CASES if S == 25)
+    assert tails == [1, 2, 3]                               # bytes behind the last whole dword of a row
+    assert any(S % 4 == 0 and mis % 16 for S, *_, mis in CS.REFILL_SIZE_CASES)
+    assert any(S % 4 == 0 and mis % 16 for S, *_, mis in CS.SIZE_CASES)
 
 
 # ---- Python argument errors (no device) -------------------------------------------------------------------------------
