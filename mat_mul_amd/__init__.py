@@ -18,9 +18,9 @@ __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameE
            "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
            "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits",
-           "FlipWalks", "reduce_archive", "flips"]
+           "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "bilinear"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips", "bilinear"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -49,6 +49,7 @@ _ATTRS = {
     "SymmetryGroup": "orbits",
     "FlipWalks": "flips",
     "reduce_archive": "flips",
+    "BilinearMatmul": "bilinear",
 }
 
 

@@ -225,6 +225,16 @@ FLIP_PLUS_SIGNATURES = {
     "tg_flip_advance_plus": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _i64, _i64, _i64, _p],
 }
 TG_FLIP_MAX_PLUS_AFTER = 2 ** 31 - 1
+# name -> argtypes; every symbol include/tensor_game_bilinear.h declares
+BILINEAR_SIGNATURES = {
+    "tg_bilinear_check": [_i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i],
+    "tg_bilinear_encode_f32": [_p, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _i, _i, _p, _p],
+    "tg_bilinear_decode_f32": [_p, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _i, _p, _p],
+}
+BILINEAR_SIGNATURES["tg_bilinear_encode_f64"] = BILINEAR_SIGNATURES["tg_bilinear_encode_f32"]
+BILINEAR_SIGNATURES["tg_bilinear_decode_f64"] = BILINEAR_SIGNATURES["tg_bilinear_decode_f32"]
+# limits of include/tensor_game_bilinear.h (R and shift are held to TG_SOL_MAX_K and TG_SOL_MAX_SHIFT)
+TG_BILINEAR_MIN_N, TG_BILINEAR_MAX_N = 2, 5
 # limits and status bits of include/tensor_game_flips.h
 TG_FLIP_MAX_K, TG_FLIP_MAX_BOUND, TG_FLIP_MAX_STEPS = 128, 63, 65536
 TG_FLIP_BAD_LENGTH, TG_FLIP_BAD_RANGE, TG_FLIP_BAD_SRC = 1, 2, 4
@@ -288,7 +298,8 @@ def _load() -> C.CDLL:
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
-                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES}.items():
+                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES,
+                           **BILINEAR_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -1,0 +1,171 @@
+"""``BilinearMatmul``: a proven factorisation of <n,n,n> run as what it is, a matrix multiplication.
+
+A list of R terms (u_r, v_r, w_r) that sums to the matmul tensor in the index convention of ``build_matmul_tensor``
+(a = i*n+j, b = j*n+k, c = i*n+k) multiplies matrices cut into n x n row-major blocks with R block products instead of
+n^3:
+
+    C_c = sum_r w_r[c] * (sum_a u_r[a] * A_a) (sum_b v_r[b] * B_b)
+
+The two sums over blocks are ``ops.bilinear_encode`` (include/tensor_game_bilinear.h), the sum over r is
+``ops.bilinear_decode``; the block products go to ``leaf`` (``torch.bmm``), or, with ``levels`` > 1, through the same
+algorithm again: the (batch,R,h,w) output of one encode is the (batch*R,h,w) input of the next.
+
+    alg = BilinearMatmul(tokens, rank, n=2, shift=1, levels=2)    # tokens int8 (K,3S) on the device
+    alg = BilinearMatmul.from_archive(arch, index=None, levels=1) # index None: the lowest-rank entry (first of equals)
+    C = alg(A, B)                                                 # A (..., P, Q), B (..., Q, T), float32 or float64
+    C = alg(A, B, out=C, pad=True, leaf=torch.bmm)
+    alg.n, alg.rank, alg.levels, alg.products                     # products = rank ** levels (against n ** (3*levels))
+
+Construction proves the list (``ops.solution_canon`` against ``build_matmul_tensor(1, n, n, n)``) and runs the canonical
+form, so null terms and a term followed by its negative cost no products; there is no way round the proof.  The kernels'
+arithmetic is defined bit for bit by the header; the result as a whole is as exact as the algorithm is: integer inputs
+whose intermediates stay below 2^24 (2^53 in float64) give the exact product, real inputs the error growth of the list.
+Not done here: a leaf GEMM of our own, half-precision operands, rectangular <n,m,p>, choosing ``levels``.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from . import functional, ops
+from ._lib import TG_BILINEAR_MAX_N, TG_BILINEAR_MIN_N, TensorGameError
+
+__all__ = ["BilinearMatmul"]
+
+
+def _byte_range(t: torch.Tensor):
+    """[first, one past the last) byte of a tensor's elements (strides of either sign)."""
+    lo = hi = 0
+    for size, stride in zip(t.shape, t.stride()):
+        if size == 0:
+            return t.data_ptr(), t.data_ptr()
+        lo, hi = lo + min(0, (size - 1) * stride), hi + max(0, (size - 1) * stride)
+    return t.data_ptr() + lo * t.element_size(), t.data_ptr() + (hi + 1) * t.element_size()
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    (a0, a1), (b0, b1) = _byte_range(a), _byte_range(b)
+    return a0 < b1 and b0 < a1
+
+
+class BilinearMatmul:
+    def __init__(self, tokens: torch.Tensor, rank: int, n: int = 2, shift: int = 1, levels: int = 1):
+        """``tokens`` int8 (K,3n^2) on a ROCm device, of which the first ``rank`` rows are the list.  Raises
+        TensorGameError unless the list is proven against <n,n,n>.  One host sync (the proof's verdict)."""
+        fn = "BilinearMatmul"
+        if not tokens.is_cuda:
+            raise TensorGameError(fn, -1, f"tokens must live on a ROCm device (got {tokens.device}); there is no CPU path")
+        self.n, self.shift, self.levels = int(n), int(shift), int(levels)
+        if not TG_BILINEAR_MIN_N <= self.n <= TG_BILINEAR_MAX_N:
+            raise TensorGameError(fn, -1, f"n={n} outside [{TG_BILINEAR_MIN_N},{TG_BILINEAR_MAX_N}]")
+        if self.levels < 1:
+            raise TensorGameError(fn, -1, f"levels={levels} < 1")
+        S = self.n * self.n
+        if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] != 3 * S:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * S}) for n={n}, got {tokens.dtype} "
+                                          f"{tuple(tokens.shape)}")
+        dev = tokens.device
+        target = functional.build_matmul_tensor(1, self.n, self.n, self.n, device=dev)
+        lengths = torch.full((1,), int(rank), dtype=torch.int64, device=dev)
+        canon, crank, _, res = ops.solution_canon(target, tokens[None], lengths, shift=self.shift)
+        res, crank = torch.stack((res, crank)).flatten().tolist()      # the one host sync
+        if res != 0:
+            what = "a bad row (its length, or a negation that leaves int8)" if res < 0 else f"residual_nnz={res}"
+            raise TensorGameError(fn, -1, f"the list is no factorisation of <{n},{n},{n}>: {what}")
+        self.rank = int(crank)
+        self.tokens = canon[0, :self.rank].contiguous()
+        self.device = dev
+
+    @classmethod
+    def from_archive(cls, arch, index: Optional[int] = None, levels: int = 1) -> "BilinearMatmul":
+        """The algorithm of entry ``index`` of a ``SolutionArchive`` (None: the entry of lowest rank, the first of
+        equals).  The entry is proven again, against <n,n,n> with n = sqrt(arch.S): an archive may hold factorisations
+        of other targets.  Synchronises (``entries``)."""
+        fn = "BilinearMatmul.from_archive"
+        n = math.isqrt(arch.S)
+        if n * n != arch.S:
+            raise TensorGameError(fn, -1, f"the archive is of S={arch.S}, which is no square: no <n,n,n>")
+        tokens, rank, _, _ = arch.entries()
+        ranks = rank.tolist()
+        if not ranks:
+            raise TensorGameError(fn, -1, "the archive is empty")
+        if index is None:
+            index = ranks.index(min(ranks))
+        if not 0 <= index < len(ranks):
+            raise TensorGameError(fn, -1, f"index={index} outside [0,{len(ranks)})")
+        return cls(tokens[index].contiguous(), ranks[index], n=n, shift=arch.shift, levels=levels)
+
+    @property
+    def products(self) -> int:
+        """Leaf block products of one call: rank ** levels, where the schoolbook method takes n ** (3 * levels)."""
+        return self.rank ** self.levels
+
+    def __call__(self, A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None, pad: bool = False,
+                 leaf=torch.bmm) -> torch.Tensor:
+        """A (...,P,Q) times B (...,Q,T), float32 or float64 on the list's device, equal leading dimensions.  P, Q and T
+        must be multiples of n^levels, or ``pad`` zero-pads them up (with torch) and slices the result.  ``leaf`` takes
+        two (batch * rank^levels, ., .) operands and returns their batched product.  ``out`` (...,P,T) may not overlap
+        A or B.  No host sync; capturable on one stream."""
+        fn = "BilinearMatmul"
+        for t, name in ((A, "A"), (B, "B")):
+            if not t.is_cuda:
+                raise TensorGameError(fn, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
+            if t.device != self.device:
+                raise TensorGameError(fn, -1, f"{name} is on {t.device}, the list on {self.device}")
+            if t.dim() < 2:
+                raise TensorGameError(fn, -1, f"{name} must have at least two dimensions, got {tuple(t.shape)}")
+        if A.dtype != B.dtype:
+            raise TensorGameError(fn, -1, f"mixed dtypes: A is {A.dtype}, B is {B.dtype}")
+        if A.dtype not in (torch.float32, torch.float64):
+            raise TensorGameError(fn, -1, f"A and B must be float32 or float64, got {A.dtype}")
+        lead, (P, Q), (Q2, T) = tuple(A.shape[:-2]), A.shape[-2:], B.shape[-2:]
+        if tuple(B.shape[:-2]) != lead or Q2 != Q:
+            raise TensorGameError(fn, -1, f"A {tuple(A.shape)} and B {tuple(B.shape)} do not multiply: equal leading "
+                                          "dimensions and Q are required")
+        if out is not None:
+            if out.dtype != A.dtype or tuple(out.shape) != (*lead, P, T) or out.device != A.device:
+                raise TensorGameError(fn, -1, f"out must be {A.dtype} {(*lead, P, T)} on {A.device}, got {out.dtype} "
+                                              f"{tuple(out.shape)} on {out.device}")
+            for t, name in ((A, "A"), (B, "B")):
+                if _overlap(out, t):
+                    raise TensorGameError(fn, -1, f"out overlaps {name}: in-place operation is not supported")
+        D = self.n ** self.levels
+        up = {name: -size % D for name, size in (("P", P), ("Q", Q), ("T", T))}
+        if any(up.values()) and not pad:
+            name = next(k for k, v in up.items() if v)
+            raise TensorGameError(fn, -1, f"{name}={dict(P=P, Q=Q, T=T)[name]} is no multiple of n^levels={D} (pad=True "
+                                          "pads with zeros)")
+        batch = math.prod(lead)
+        a, b = A.reshape(batch, P, Q), B.reshape(batch, Q, T)
+        if any(up.values()):
+            a = torch.nn.functional.pad(a, (0, up["Q"], 0, up["P"]))
+            b = torch.nn.functional.pad(b, (0, up["T"], 0, up["Q"]))
+        a = a if a.stride(2) == 1 else a.contiguous()
+        b = b if b.stride(2) == 1 else b.contiguous()
+        for _ in range(self.levels):
+            a = ops.bilinear_encode(a, self.tokens, self.rank, self.n, 0, self.shift).flatten(0, 1)
+            b = ops.bilinear_encode(b, self.tokens, self.rank, self.n, 1, self.shift).flatten(0, 1)
+        m = leaf(a, b)
+        if tuple(m.shape) != (a.shape[0], a.shape[1], b.shape[2]) or m.dtype != A.dtype:
+            raise TensorGameError(fn, -1, f"leaf returned {m.dtype} {tuple(m.shape)}, expected {A.dtype} "
+                                          f"{(a.shape[0], a.shape[1], b.shape[2])}")
+        m = m.contiguous()
+        direct = None                                   # the last decode writes into `out` itself where it can
+        if out is not None and not any(up.values()) and out.stride(-1) == 1:
+            try:
+                direct = out.view(batch, P, T)
+            except RuntimeError:
+                pass
+        for level in range(self.levels):
+            m = m.view(m.shape[0] // self.rank, self.rank, m.shape[1], m.shape[2])
+            m = ops.bilinear_decode(m, self.tokens, self.rank, self.n, self.shift,
+                                    out=direct if level == self.levels - 1 else None)
+        if direct is not None:
+            return out
+        m = m[:, :P, :T].reshape(*lead, P, T)
+        if out is None:
+            return m
+        out.copy_(m)
+        return out

@@ -35,6 +35,7 @@ __all__ = [
     "orbit_check", "orbit_fixes", "orbit_workspace_size", "orbit_canon",
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
     "flip_check", "flip_begin", "flip_advance", "flip_plus_check", "flip_advance_plus",
+    "bilinear_check", "bilinear_encode", "bilinear_decode",
 ]
 
 
@@ -1720,3 +1721,82 @@ def flip_advance_plus(st: dict, n_steps: int, plus_after: int, plus_slack: int =
             int(bound), C.c_uint64(_u64(seed)), C.c_uint64(_u64(walk0)), int(step0), int(n_steps), int(plus_after),
             int(plus_slack))
     return st
+
+
+_BILINEAR_DTYPES = {torch.float32: ("f32", 4), torch.float64: ("f64", 8)}
+
+
+def bilinear_check(batch: int, rows: int, cols: int, ld: Optional[int] = None, batch_stride: Optional[int] = None,
+                   R: int = 1, n: int = 2, mode: int = 0, shift: int = 1, elem_bytes: int = 4) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_bilinear_encode_* / tg_bilinear_decode_* take these sizes
+    (``ld`` defaults to ``cols``, ``batch_stride`` to ``rows * ld``).  Host only."""
+    ld = cols if ld is None else ld
+    call("tg_bilinear_check", int(batch), int(rows), int(cols), int(ld),
+         int(rows * ld if batch_stride is None else batch_stride), int(R), int(n), int(mode), int(shift), int(elem_bytes))
+
+
+def _bilinear_matrices(t: torch.Tensor, name: str, fn: str):
+    """(batch, rows, cols, ld, batch_stride, entry suffix, element bytes) of a strided (batch,rows,cols) view, which is
+    taken as it is (no copy): only the column stride is held to 1."""
+    _need_gpu(t, name)
+    if t.dtype not in _BILINEAR_DTYPES or t.dim() != 3:
+        raise TensorGameError(fn, -1, f"{name} must be float32 or float64 (batch,rows,cols), got {t.dtype} "
+                                      f"{tuple(t.shape)}")
+    if t.stride(2) != 1:
+        raise TensorGameError(fn, -1, f"{name}: the column stride must be 1, got {t.stride(2)}")
+    batch, rows, cols = t.shape
+    ld = t.stride(1) if rows > 1 else max(t.stride(1), cols)
+    return (batch, rows, cols, ld, t.stride(0) if batch > 1 else rows * ld, *_BILINEAR_DTYPES[t.dtype])
+
+
+def _bilinear_list(tokens: torch.Tensor, R: int, n: int, dev, fn: str) -> torch.Tensor:
+    """The list of a bilinear entry: int8 (K,3n^2) on ``dev`` with K >= R, made contiguous."""
+    _need_gpu(tokens, "tokens")
+    if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] != 3 * n * n or tokens.device != dev:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * n * n}) on {dev}, got {tokens.dtype} "
+                                      f"{tuple(tokens.shape)} on {tokens.device}")
+    if R > tokens.shape[0]:
+        raise TensorGameError(fn, -1, f"R={R} above the K={tokens.shape[0]} rows of tokens")
+    return tokens if tokens.is_contiguous() else tokens.contiguous()
+
+
+def bilinear_encode(X, tokens, R: int, n: int, mode: int, shift: int = 1, out=None) -> torch.Tensor:
+    """The R block combinations of ``batch`` matrices in one launch (include/tensor_game_bilinear.h): X float32 or
+    float64 (batch,rows,cols), any row and batch stride (a view is not copied), cut into n x n blocks of (h,w);
+    tokens int8 (K,3n^2), of which rows 0 .. R-1 and part ``mode`` (0: u, for the left operand; 1: v, for the right
+    one) are used.  Returns ``out`` (batch,R,h,w), contiguous: out[b][r] = sum_a (tokens[r][mode*S+a] - shift) * block a
+    of X[b], by the header's arithmetic rule.  No host sync."""
+    fn = "bilinear_encode"
+    batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(X, "X", fn)
+    bilinear_check(batch, rows, cols, ld, stride, R, n, mode, shift, eb)
+    tokens = _bilinear_list(tokens, R, n, X.device, fn)
+    if out is not None:
+        _need_gpu(out, "out")
+    out = _out(out, (batch, int(R), rows // n, cols // n), X.dtype, X.device, "out")
+    _launch(X.device, f"tg_bilinear_encode_{suffix}", _ptr(X), batch, rows, cols, ld, stride, _ptr(tokens), int(R), int(n),
+            int(mode), int(shift), _ptr(out))
+    return out
+
+
+def bilinear_decode(M, tokens, R: int, n: int, shift: int = 1, out=None) -> torch.Tensor:
+    """The n x n blocks of ``batch`` result matrices from the R block products, in one launch: M float32 or float64
+    (batch,R,h,w), contiguous; part 2 (w) of rows 0 .. R-1 of tokens is used.  Returns ``out`` (batch,n*h,n*w), which
+    may be a strided view when given (column stride 1): block c of out[b] = sum_r (tokens[r][2S+c] - shift) * M[b][r].
+    Every element is written.  No host sync."""
+    fn = "bilinear_decode"
+    _need_gpu(M, "M")
+    if M.dtype not in _BILINEAR_DTYPES or M.dim() != 4 or M.shape[1] != R or not M.is_contiguous():
+        raise TensorGameError(fn, -1, f"M must be contiguous float32 or float64 (batch,R={R},h,w), got {M.dtype} "
+                                      f"{tuple(M.shape)}")
+    shape = (M.shape[0], n * M.shape[2], n * M.shape[3])
+    if out is None:
+        out = torch.empty(shape, dtype=M.dtype, device=M.device)
+    elif out.dtype != M.dtype or tuple(out.shape) != shape or out.device != M.device:
+        raise TensorGameError(fn, -1, f"out must be {M.dtype} {shape} on {M.device}, got {out.dtype} {tuple(out.shape)} "
+                                      f"on {out.device}")
+    batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(out, "out", fn)
+    bilinear_check(batch, rows, cols, ld, stride, R, n, 0, shift, eb)
+    tokens = _bilinear_list(tokens, R, n, M.device, fn)
+    _launch(M.device, f"tg_bilinear_decode_{suffix}", _ptr(M), batch, rows, cols, ld, stride, _ptr(tokens), int(R), int(n),
+            int(shift), _ptr(out))
+    return out

@@ -1,0 +1,141 @@
+"""BilinearMatmul (mat_mul_amd/bilinear.py, include/tensor_game_bilinear.h) next to torch.matmul, and the two kernels
+next to a copy.
+
+    python tools/bilinear_bench.py OUT_DIR [--sizes 2048 4096 8192] [--reps 7] [--warmup 2]
+
+One process, one GPU, float32 square matrices.  Algorithms: Strassen's list (tests/golden/strassen.npz) at levels 1, 2
+and 3, and the standard list of <2,2,2> (8 products: the same arithmetic as the schoolbook method, so what it loses
+against torch.matmul is the cost of the encodes, the decode and the smaller leaf products alone).  A size is skipped
+when its temporaries would not fit in the free memory.
+
+Rows "matmul": ``alg(A, B, out=C)`` and ``torch.matmul(A, B, out=D)``, alternating, each repetition between two device
+events after warm-up of both; median, p10 and p90 in microseconds, the ratio of the medians, and the largest deviation of
+the two results over the largest entry (the inputs are standard normal).
+
+Rows "encode" and "decode": the first level of the same call alone, its bytes (every input byte read once, every output
+byte written once: (N^2 + R (N/2)^2) * 4) over its time, alternating with a device copy of the same byte count (``copy_``
+between two contiguous float32 tensors of half that many bytes each, which moves 16 bytes per lane), and the ratio of the
+two rates.  Writes OUT_DIR/bilinear_bench.json.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+from mat_mul_amd import BilinearMatmul, ops  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def standard_2x2(shift=1):
+    rows = np.zeros((8, 12), dtype=np.int64)
+    t = 0
+    for i in range(2):
+        for j in range(2):
+            for k in range(2):
+                rows[t, i * 2 + j] = rows[t, 4 + j * 2 + k] = rows[t, 8 + i * 2 + k] = 1
+                t += 1
+    return (rows + shift).astype(np.int8)
+
+
+def stats(ts):
+    ts = sorted(ts)
+    q = lambda f: ts[min(len(ts) - 1, int(f * len(ts)))]  # noqa: E731
+    return {"median_us": statistics.median(ts), "p10_us": q(0.1), "p90_us": q(0.9), "reps": len(ts)}
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3
+
+
+def alternate(fns, warmup, reps):
+    """Each of ``fns`` warmed up, then timed in turn ``reps`` times; a list of stats, one per function."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            ts[i].append(timed(fn))
+    return [stats(t) for t in ts]
+
+
+def temporaries_bytes(N, rank, levels):
+    """float32 bytes ``alg(A, B)`` allocates at size N: both operands' encodes and every level's products."""
+    total, side, count = 0, N, 1
+    for _ in range(levels):
+        side, count = side // 2, count * rank
+        total += 3 * count * side * side * 4
+    return total
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--sizes", type=int, nargs="*", default=[2048, 4096, 8192])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    out = Path(args.out) / "bilinear_bench.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    strassen = np.load(ROOT / "tests" / "golden" / "strassen.npz")["tokens"].astype(np.int8)
+    lists = [("strassen", strassen, 7, (1, 2, 3)), ("standard2", standard_2x2(), 8, (1,))]
+    res = {"torch": torch.__version__, "device": torch.cuda.get_device_name(0), "dtype": "float32", "rows": []}
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for N in args.sizes:
+        A = torch.randn((N, N), device=DEV, generator=gen)
+        B = torch.randn((N, N), device=DEV, generator=gen)
+        C, D = torch.empty_like(A), torch.empty_like(A)
+        for name, tokens, rank, all_levels in lists:
+            tok = torch.from_numpy(tokens).to(DEV)
+            for levels in all_levels:
+                free = torch.cuda.mem_get_info(0)[0]
+                if N % 2 ** levels or 2 * temporaries_bytes(N, rank, levels) > free:
+                    print(json.dumps({"kind": "matmul", "list": name, "levels": levels, "N": N, "skipped": "memory or size"}))
+                    continue
+                alg = BilinearMatmul(tok, rank, n=2, shift=1, levels=levels)
+                ours, theirs = alternate([lambda: alg(A, B, out=C), lambda: torch.matmul(A, B, out=D)], args.warmup, args.reps)
+                row = {"kind": "matmul", "list": name, "levels": levels, "N": N, "products": alg.products,
+                       "bilinear": ours, "torch_matmul": theirs, "ratio": ours["median_us"] / theirs["median_us"],
+                       "max_deviation": float((C - D).abs().max() / D.abs().max())}
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+                torch.cuda.empty_cache()
+            # the kernels alone: the first level of this list at this size
+            nbytes = (N * N + rank * (N // 2) ** 2) * 4
+            src, dst = (torch.empty(nbytes // 8, dtype=torch.float32, device=DEV) for _ in range(2))
+            src.normal_(generator=gen)
+            Y = torch.empty((1, rank, N // 2, N // 2), device=DEV)
+            ops.bilinear_encode(A[None], tok, rank, 2, 0, out=Y)
+            enc, cp1, dec, cp2 = alternate([lambda: ops.bilinear_encode(A[None], tok, rank, 2, 0, out=Y), lambda: dst.copy_(src),
+                                            lambda: ops.bilinear_decode(Y, tok, rank, 2, out=C[None]), lambda: dst.copy_(src)],
+                                           args.warmup, args.reps)
+            for kind, mine, copy in (("encode", enc, cp1), ("decode", dec, cp2)):
+                row = {"kind": kind, "list": name, "N": N, "R": rank, "bytes": nbytes, **mine,
+                       "TB_per_s": nbytes / mine["median_us"] * 1e-6, "copy": copy,
+                       "copy_TB_per_s": nbytes / copy["median_us"] * 1e-6, "share_of_copy": copy["median_us"] / mine["median_us"]}
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+            del src, dst, Y
+            torch.cuda.empty_cache()
+        out.write_text(json.dumps(res, indent=1) + "\n")
+    out.write_text(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
