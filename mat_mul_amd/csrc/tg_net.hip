@@ -552,6 +552,11 @@ int check_cfg(const char* fn, const tg_net_config* c, bool s25 = false) {
   if (s25 && c->n_steps > TG_NET_WIDE3_MAX_STEPS)
     return tg_internal_fail(TG_ERR_UNSUPPORTED, "%s: n_steps=%d above TG_NET_WIDE3_MAX_STEPS=%d (dim_3d=%d)", fn,
                             c->n_steps, TG_NET_WIDE3_MAX_STEPS, c->S);
+  if (!s25 && c->S == TG_NET_WIDE3_S)
+    return tg_internal_fail(TG_ERR_UNSUPPORTED,
+                            "%s: dim_3d=%d above TG_NET_MAX_S=%d: the entries of tensor_game_net_s25.h (tg_net_s25_check; "
+                            "FusedAlphaTensor25) serve TG_NET_WIDE3_S=%d",
+                            fn, c->S, TG_NET_MAX_S, TG_NET_WIDE3_S);
   if (!s25 && c->S > TG_NET_MAX_S && !wide)
     return tg_internal_fail(TG_ERR_UNSUPPORTED,
                             "%s: dim_3d=%d above TG_NET_MAX_S=%d, and not exactly TG_NET_WIDE_S=%d or TG_NET_WIDE2_S=%d",
