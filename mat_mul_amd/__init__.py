@@ -18,9 +18,10 @@ __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameE
            "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
            "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits",
-           "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "bilinear"]
+           "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "bilinear",
+           "Mod2Walks", "Mod2Result", "reduce_mod2", "reduce_archive_mod2", "flips_mod2"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips", "bilinear"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips", "bilinear", "flips_mod2"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -50,6 +51,10 @@ _ATTRS = {
     "FlipWalks": "flips",
     "reduce_archive": "flips",
     "BilinearMatmul": "bilinear",
+    "Mod2Walks": "flips_mod2",
+    "Mod2Result": "flips_mod2",
+    "reduce_mod2": "flips_mod2",
+    "reduce_archive_mod2": "flips_mod2",
 }
 
 

@@ -225,6 +225,14 @@ FLIP_PLUS_SIGNATURES = {
     "tg_flip_advance_plus": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _i64, _i64, _i64, _p],
 }
 TG_FLIP_MAX_PLUS_AFTER = 2 ** 31 - 1
+# name -> argtypes; every symbol include/tensor_game_flips_mod2.h declares
+FLIP2_SIGNATURES = {
+    "tg_flip2_check": [_i64, _i64, _i, _i, _i, _i64, _i64, _i64, _i64],
+    "tg_flip2_begin": [_p, _p, _i64, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "tg_flip2_advance": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _u64, _u64, _i64, _i64, _i64, _i64, _p],
+    "tg_flip2_residual": [_p, _p, _p, _i64, _i, _i, _p, _p],
+}
+TG_FLIP2_DOMAIN, TG_FLIP2_MAX_PLUS_AFTER = 0x46320000, 2 ** 31 - 1
 # name -> argtypes; every symbol include/tensor_game_bilinear.h declares
 BILINEAR_SIGNATURES = {
     "tg_bilinear_check": [_i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i],
@@ -298,7 +306,7 @@ def _load() -> C.CDLL:
                            **TRAIN_S25_SIGNATURES,
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
-                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES,
+                           **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES, **FLIP2_SIGNATURES,
                            **BILINEAR_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)

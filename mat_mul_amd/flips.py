@@ -21,7 +21,8 @@ A walk without a match is stuck: flips only move inside one component of the gra
 follow include/tensor_game_flips_plus.h instead: a walk that has no flip left, or has not lowered its rank for N steps,
 rewrites two terms into three with the same sum (a "plus" transition) while its list is shorter than
 min(K, best_rank + plus_slack), and goes on in another component.  ``plus_after=None`` (the default) gives the plain
-walks, unchanged.  Not done here: walks over Z_2, choosing the entries to walk adaptively, reviving stuck walks.
+walks, unchanged.  The same walks over the field with two elements are ``Mod2Walks`` (flips_mod2.py).  Not done here:
+choosing the entries to walk adaptively, reviving stuck walks.
 """
 from __future__ import annotations
 

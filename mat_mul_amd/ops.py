@@ -35,6 +35,7 @@ __all__ = [
     "orbit_check", "orbit_fixes", "orbit_workspace_size", "orbit_canon",
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
     "flip_check", "flip_begin", "flip_advance", "flip_plus_check", "flip_advance_plus",
+    "flip2_check", "flip2_begin", "flip2_advance", "flip2_residual",
     "bilinear_check", "bilinear_encode", "bilinear_decode",
 ]
 
@@ -1641,12 +1642,18 @@ _FLIP_STATE = (("cur", torch.int8), ("cur_rank", torch.int32), ("best", torch.in
 _FLIP_PLUS_STATE = _FLIP_STATE + (("since", torch.int32), ("pluses", torch.int64))
 
 
-def _flip_state(given: dict, W: int, K: int, S: int, dev, fn: str, names=_FLIP_STATE) -> dict:
+# the nine of include/tensor_game_flips_mod2.h: the two lists are rows of three mask words
+_FLIP2_STATE = (("cur", torch.int32), ("cur_rank", torch.int32), ("best", torch.int32), ("best_rank", torch.int32),
+                ("best_step", torch.int64), ("flips", torch.int64), ("state", torch.int32), ("since", torch.int32),
+                ("pluses", torch.int64))
+
+
+def _flip_state(given: dict, W: int, K: int, S: int, dev, fn: str, names=_FLIP_STATE, row=None) -> dict:
     """The walk-state tensors ``names`` (the seven of include/tensor_game_flips.h) on ``dev``: ``given[name]`` held to
-    the rule of ``_flag``, or allocated where it is None."""
+    the rule of ``_flag``, or allocated where it is None.  ``row``: the width of a row of the two lists (3S tokens)."""
     out = {}
     for name, dtype in names:
-        shape = (W, K, 3 * S) if dtype == torch.int8 else (W,)
+        shape = (W, K, 3 * S if row is None else row) if name in ("cur", "best") else (W,)
         t = given.get(name)
         if t is not None:
             _need_gpu(t, name)
@@ -1721,6 +1728,93 @@ def flip_advance_plus(st: dict, n_steps: int, plus_after: int, plus_slack: int =
             int(bound), C.c_uint64(_u64(seed)), C.c_uint64(_u64(walk0)), int(step0), int(n_steps), int(plus_after),
             int(plus_slack))
     return st
+
+
+def flip2_check(M: int, W: int, K: int, S: int, shift: int = 1, step0: int = 0, n_steps: int = 1, plus_after: int = 0,
+                plus_slack: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_flip2_begin / tg_flip2_advance take these sizes.  Host only."""
+    call("tg_flip2_check", int(M), int(W), int(K), int(S), int(shift), int(step0), int(n_steps), int(plus_after),
+         int(plus_slack))
+
+
+def _flip2_lists(lists, fn: str, name: str, lead: str) -> Tuple[int, int]:
+    """(W, K) of the mask rows int32 (W,K,3) of W lists over Z_2 on a ROCm device."""
+    _need_gpu(lists, name)
+    if lists.dtype != torch.int32 or lists.dim() != 3 or lists.shape[2] != 3:
+        raise TensorGameError(fn, -1, f"{name} must be int32 ({lead},K,3), got {lists.dtype} {tuple(lists.shape)}")
+    return lists.shape[0], lists.shape[1]
+
+
+def flip2_begin(tokens, lengths, src=None, shift: int = 1, status=None, **state):
+    """Start W flip-graph walks over Z_2 in one launch (include/tensor_game_flips_mod2.h).  tokens int8 (M,K,3S) and
+    lengths int64 (M,) as ``solutions()`` or an archive's ``entries()`` give them; ``src`` int64 (W,): the list walk w
+    starts from (None: walk w starts from list w).  Each list is taken mod 2 (a factor becomes one mask word), loses its
+    null terms and is reduced.  Returns the walk state, a dict of device tensors: cur, best int32 (W,K,3); cur_rank,
+    best_rank, state, since int32 (W,); best_step, flips, pluses int64 (W,) (any of them may be passed in by name).  A
+    bad row (length outside [0,K]: bit 0 of ``status`` uint32 (1,); a ``src`` outside [0,M): bit 2) gets state -1; there
+    is no range error.  No host sync."""
+    fn = "flip2_begin"
+    tokens, M, K, S, dev = _list_tokens(tokens, fn)
+    lengths = _list_lengths(lengths, M, dev)
+    W = M
+    if src is not None:
+        _need_gpu(src, "src")
+        if src.dim() != 1:
+            raise TensorGameError(fn, -1, f"src must be int64 (W,), got {tuple(src.shape)}")
+        W = src.shape[0]
+        src = _flag(src, (W,), torch.int64, dev, "src")
+    flip2_check(M, W, K, S, shift)
+    st = _flip_state(state, W, K, S, dev, fn, _FLIP2_STATE, row=3)
+    status = _flag(status, (1,), torch.uint32, dev, "status")
+    _launch(dev, "tg_flip2_begin", _ptr(tokens), _ptr(lengths), M, _ptr(src), W, K, S, int(shift),
+            *[_ptr(st[name]) for name, _ in _FLIP2_STATE], _ptr(status))
+    return st
+
+
+def flip2_advance(st: dict, n_steps: int, S: int, plus_after: int = 0, plus_slack: int = 1, seed: int = 0, walk0: int = 0,
+                  step0: int = 0):
+    """``n_steps`` steps (at most TG_FLIP_MAX_STEPS) of the Z_2 walks ``st`` (the dict ``flip2_begin`` returned, of lists
+    over S values) in place, in one launch: steps step0 .. step0 + n_steps - 1 of the walks with global ids walk0 ..
+    walk0 + W - 1, drawn from Philox keyed by (seed, id, step).  No flip is ever refused.  With ``plus_after`` > 0 a walk
+    that has no flip left, or has not lowered its rank for that many steps, takes a plus transition while its list is
+    shorter than min(K, best_rank + plus_slack).  Walks of state 1 (stuck) or -1 (bad) are left alone.  Returns ``st``.
+    No host sync."""
+    fn = "flip2_advance"
+    W, K = _flip2_lists(st["cur"], fn, "cur", "W")
+    dev = st["cur"].device
+    flip2_check(0, W, K, S, 0, step0, n_steps, plus_after, plus_slack)
+    for name, _ in _FLIP2_STATE:
+        if st.get(name) is None:
+            raise TensorGameError(fn, -1, f"{name} must be given (flip2_begin makes it)")
+    st = _flip_state({name: st[name] for name, _ in _FLIP2_STATE}, W, K, S, dev, fn, _FLIP2_STATE, row=3)
+    _launch(dev, "tg_flip2_advance", *[_ptr(st[name]) for name, _ in _FLIP2_STATE], W, K, int(S), C.c_uint64(_u64(seed)),
+            C.c_uint64(_u64(walk0)), int(step0), int(n_steps), int(plus_after), int(plus_slack))
+    return st
+
+
+def flip2_residual(targets, lists, ranks, residual=None):
+    """The proof of lists over Z_2 (tg_flip2_residual), one launch, exact: int32 (M,), per list the number of cells of
+    ``targets`` int8 (M,S,S,S) whose parity differs from that of the sum of the first ``ranks[m]`` (int32 (M,)) terms of
+    ``lists`` int32 (M,K,3); -1 for a rank outside [0,K].  No host sync."""
+    fn = "flip2_residual"
+    M, K = _flip2_lists(lists, fn, "lists", "M")
+    dev = lists.device
+    _need_gpu(targets, "targets")
+    if targets.dtype != torch.int8 or targets.dim() != 4 or targets.shape[0] != M or targets.device != dev \
+            or not (targets.shape[1] == targets.shape[2] == targets.shape[3]):
+        raise TensorGameError(fn, -1, f"targets must be int8 ({M},S,S,S) on {dev}, got {targets.dtype} "
+                                      f"{tuple(targets.shape)} on {targets.device}")
+    S = targets.shape[1]
+    flip2_check(M, 0, K, S, 0)
+    targets = targets if targets.is_contiguous() else targets.contiguous()
+    lists = _flag(lists, (M, K, 3), torch.int32, dev, "lists")
+    _need_gpu(ranks, "ranks")
+    ranks = _flag(ranks, (M,), torch.int32, dev, "ranks")
+    if residual is not None:
+        _need_gpu(residual, "residual")
+    residual = _out(residual, (M,), torch.int32, dev, "residual")
+    _launch(dev, "tg_flip2_residual", _ptr(targets), _ptr(lists), _ptr(ranks), M, K, S, _ptr(residual))
+    return residual
 
 
 _BILINEAR_DTYPES = {torch.float32: ("f32", 4), torch.float64: ("f64", 8)}
