@@ -19,9 +19,10 @@ __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameE
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
            "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits",
            "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "bilinear",
-           "Mod2Walks", "Mod2Result", "reduce_mod2", "reduce_archive_mod2", "flips_mod2"]
+           "Mod2Walks", "Mod2Result", "reduce_mod2", "reduce_archive_mod2", "flips_mod2",
+           "lift_signs", "LiftResult", "reduce_archive_lifted", "lift"]
 
-_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips", "bilinear", "flips_mod2"}
+_SUBMODULES = {"_lib", "ops", "functional", "env", "generator", "sharding", "demo_io", "build", "tree", "search", "replay", "net", "train", "rollout", "replay_io", "augment", "solutions", "bases", "orbits", "flips", "bilinear", "flips_mod2", "lift"}
 _ATTRS = {
     "TensorGameEnv": "env",
     "SyntheticDemos": "generator",
@@ -55,6 +56,9 @@ _ATTRS = {
     "Mod2Result": "flips_mod2",
     "reduce_mod2": "flips_mod2",
     "reduce_archive_mod2": "flips_mod2",
+    "lift_signs": "lift",
+    "LiftResult": "lift",
+    "reduce_archive_lifted": "lift",
 }
 
 

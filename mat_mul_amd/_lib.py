@@ -233,6 +233,15 @@ FLIP2_SIGNATURES = {
     "tg_flip2_residual": [_p, _p, _p, _i64, _i, _i, _p, _p],
 }
 TG_FLIP2_DOMAIN, TG_FLIP2_MAX_PLUS_AFTER = 0x46320000, 2 ** 31 - 1
+# name -> argtypes; every symbol include/tensor_game_lift.h declares (tg_lift2_workspace_bytes returns an int64)
+LIFT2_SIGNATURES = {
+    "tg_lift2_workspace_bytes": [_i, _i],
+    "tg_lift2_check": [_i64, _i, _i, _i, _i64, _i64],
+    "tg_lift2_signs": [_p, _p, _p, _i64, _i, _i, _i, _u64, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
+}
+# limits and status values of include/tensor_game_lift.h
+TG_LIFT2_DOMAIN, TG_LIFT2_MAX_TRIES, TG_LIFT2_MAX_WS_LISTS = 0x4C320000, 1024, 65536
+TG_LIFT2_OK, TG_LIFT2_NOT_MOD2, TG_LIFT2_INCONSISTENT, TG_LIFT2_NOT_EXACT = 0, 1, 2, 3
 # name -> argtypes; every symbol include/tensor_game_bilinear.h declares
 BILINEAR_SIGNATURES = {
     "tg_bilinear_check": [_i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i],
@@ -307,13 +316,13 @@ def _load() -> C.CDLL:
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
                            **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES, **FLIP2_SIGNATURES,
-                           **BILINEAR_SIGNATURES}.items():
+                           **LIFT2_SIGNATURES, **BILINEAR_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes
-        fn.restype = C.c_char_p if name == "tg_last_error" else C.c_int
+        fn.restype = C.c_char_p if name == "tg_last_error" else C.c_int64 if name == "tg_lift2_workspace_bytes" else C.c_int
     rts = _hip_runtimes_mapped()
     if len(rts) > 1:
         raise ImportError(f"two HIP runtimes are mapped ({rts}); libtensorgame.so must share PyTorch's")

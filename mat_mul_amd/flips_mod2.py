@@ -16,12 +16,16 @@ every other walk, and a function of (its list, seed, walk id, step) alone:
     res = reduce_archive_mod2(arch, n_steps=100_000)                       # the same from an archive's entries
     save_run(..., extra={"mod2": walks.state_dict()}); Mod2Walks.from_state_dict(sd, "cuda:0").advance(n)  # bit for bit
 
+    walks.lift(int_targets)                                                # mat_mul_amd.lift: the sign lift to {-1,0,1}
+
 A list is reported as proven only through ``tg_flip2_residual``: the exact count of cells where the list's sum and the
 target differ mod 2.  Z_2 lists do NOT enter ``SolutionArchive``: its proof is over the integers, and a list that is
-right mod 2 need not be right there.
+right mod 2 need not be right there.  ``mat_mul_amd.lift`` lifts a Z_2 list to integer coefficients in {-1, 0, 1}
+where such a lift exists and its system's solutions find it; what it lifts enters the archive through the archive's own
+proof (``reduce_archive_lifted``).
 
-Not done here: Hensel lifting of a Z_2 list to the integers, an archive and a canonical form for Z_2 lists, choosing the
-entries to walk adaptively.
+Not done here: lifting beyond +-1 coefficients, an archive and a canonical form for Z_2 lists, choosing the entries to
+walk adaptively.
 """
 from __future__ import annotations
 
@@ -116,6 +120,13 @@ class Mod2Walks:
         per walk: 0 where the list sums to its target mod 2."""
         lists, rank = self._which(which, "Mod2Walks.residual")
         return ops.flip2_residual(targets, lists, rank)
+
+    def lift(self, targets: torch.Tensor, which: str = "best", tries: int = 32, seed: Optional[int] = None):
+        """``lift.lift_signs`` of the ``best`` (or ``cur``) lists against the INTEGER ``targets`` int8 (W,S,S,S), one per
+        walk, with list0 = walk0 and the walks' seed unless ``seed`` is given: a ``LiftResult``.  No host sync."""
+        from .lift import lift_signs
+        lists, rank = self._which(which, "Mod2Walks.lift")
+        return lift_signs(lists, rank, targets, tries=tries, seed=self.seed if seed is None else seed, list0=self.walk0)
 
     def state_dict(self) -> dict:
         """Host tensors and plain scalars (loads with ``weights_only=True``); synchronises."""

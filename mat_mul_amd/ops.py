@@ -36,6 +36,7 @@ __all__ = [
     "basis_inverse_check", "solution_rebase_check", "basis_inverse", "solution_rebase",
     "flip_check", "flip_begin", "flip_advance", "flip_plus_check", "flip_advance_plus",
     "flip2_check", "flip2_begin", "flip2_advance", "flip2_residual",
+    "lift2_check", "lift2_workspace_bytes", "lift2_signs",
     "bilinear_check", "bilinear_encode", "bilinear_decode",
 ]
 
@@ -1815,6 +1816,72 @@ def flip2_residual(targets, lists, ranks, residual=None):
     residual = _out(residual, (M,), torch.int32, dev, "residual")
     _launch(dev, "tg_flip2_residual", _ptr(targets), _ptr(lists), _ptr(ranks), M, K, S, _ptr(residual))
     return residual
+
+
+_LIFT2_OUT = ("status", "try_used", "unknowns", "sys_rank", "miss")
+
+
+def lift2_workspace_bytes(K: int, S: int) -> int:
+    """Bytes of scratch ``lift2_signs`` needs per concurrently resident list of up to K terms over S values
+    (tg_lift2_workspace_bytes); 0 where the system fits in LDS.  Host only."""
+    n = _lib.lib.tg_lift2_workspace_bytes(int(K), int(S))
+    if n < 0:
+        raise TensorGameError("tg_lift2_workspace_bytes", int(n), _lib.lib.tg_last_error().decode("utf-8", "replace"))
+    return int(n)
+
+
+def lift2_check(W: int, K: int, S: int, shift: int = 1, tries: int = 1, ws_lists: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_lift2_signs takes these sizes.  Host only."""
+    call("tg_lift2_check", int(W), int(K), int(S), int(shift), int(tries), int(ws_lists))
+
+
+def lift2_signs(targets, lists, ranks, tries: int = 32, seed: int = 0, list0: int = 0, shift: int = 1, workspace=None,
+                ws_lists: Optional[int] = None, tokens=None, **out):
+    """The sign lift of W lists over Z_2 to the integers, one launch (include/tensor_game_lift.h).  ``targets`` int8
+    (W,S,S,S): the INTEGER targets; ``lists`` int32 (W,K,3) and ``ranks`` int32 (W,) as the Z_2 walks hold them.  Returns
+    (tokens int8 (W,K,3S), dict of status, try_used, unknowns, sys_rank, miss int32 (W,)); any of them may be passed in
+    by name.  ``workspace``: a uint8 tensor of at least ``ws_lists * lift2_workspace_bytes(K, S)`` bytes, needed where
+    that size is not 0 (``ws_lists`` defaults to what the tensor holds).  No host sync, no allocation beyond the outputs
+    that were not given."""
+    fn = "lift2_signs"
+    W, K = _flip2_lists(lists, fn, "lists", "W")
+    dev = lists.device
+    _need_gpu(targets, "targets")
+    if targets.dtype != torch.int8 or targets.dim() != 4 or targets.shape[0] != W or targets.device != dev \
+            or not (targets.shape[1] == targets.shape[2] == targets.shape[3]):
+        raise TensorGameError(fn, -1, f"targets must be int8 ({W},S,S,S) on {dev}, got {targets.dtype} "
+                                      f"{tuple(targets.shape)} on {targets.device}")
+    S = targets.shape[1]
+    per_list = 0 if not (1 <= K <= _lib.TG_FLIP_MAX_K and 1 <= S <= _lib.TG_MAX_S) else lift2_workspace_bytes(K, S)
+    if workspace is not None:
+        _need_gpu(workspace, "workspace")
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.device != dev or not workspace.is_contiguous():
+            raise TensorGameError(fn, -1, f"workspace must be contiguous uint8 (bytes,) on {dev}")
+    if ws_lists is None:
+        ws_lists = 0 if workspace is None or per_list == 0 else min(workspace.numel() // per_list, _lib.TG_LIFT2_MAX_WS_LISTS)
+    lift2_check(W, K, S, shift, tries, ws_lists)
+    if per_list and W and (workspace is None or workspace.numel() < int(ws_lists) * per_list):
+        raise TensorGameError(fn, -1, f"workspace must hold ws_lists={int(ws_lists)} x {per_list} bytes, got "
+                                      f"{0 if workspace is None else workspace.numel()}")
+    targets = targets if targets.is_contiguous() else targets.contiguous()
+    lists = _flag(lists, (W, K, 3), torch.int32, dev, "lists")
+    _need_gpu(ranks, "ranks")
+    ranks = _flag(ranks, (W,), torch.int32, dev, "ranks")
+    if tokens is not None:
+        _need_gpu(tokens, "tokens")
+    tokens = _out(tokens, (W, K, 3 * S), torch.int8, dev, "tokens")
+    res = {}
+    for name in _LIFT2_OUT:
+        t = out.pop(name, None)
+        if t is not None:
+            _need_gpu(t, name)
+        res[name] = _out(t, (W,), torch.int32, dev, name)
+    if out:
+        raise TensorGameError(fn, -1, f"unknown outputs {sorted(out)}")
+    _launch(dev, "tg_lift2_signs", _ptr(targets), _ptr(lists), _ptr(ranks), W, K, S, int(shift), C.c_uint64(_u64(seed)),
+            C.c_uint64(_u64(list0)), int(tries), _ptr(tokens), *[_ptr(res[name]) for name in _LIFT2_OUT],
+            _ptr(workspace if per_list else None), int(ws_lists))
+    return tokens, res
 
 
 _BILINEAR_DTYPES = {torch.float32: ("f32", 4), torch.float64: ("f64", 8)}
