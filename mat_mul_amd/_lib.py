@@ -252,6 +252,15 @@ BILINEAR_SIGNATURES["tg_bilinear_encode_f64"] = BILINEAR_SIGNATURES["tg_bilinear
 BILINEAR_SIGNATURES["tg_bilinear_decode_f64"] = BILINEAR_SIGNATURES["tg_bilinear_decode_f32"]
 # limits of include/tensor_game_bilinear.h (R and shift are held to TG_SOL_MAX_K and TG_SOL_MAX_SHIFT)
 TG_BILINEAR_MIN_N, TG_BILINEAR_MAX_N = 2, 5
+# name -> argtypes; every symbol include/tensor_game_rect.h declares (its limits are TG_MAX_S, TG_SOL_MAX_K, TG_SOL_MAX_SHIFT)
+RECT_SIGNATURES = {
+    "tg_reset_matmul_rect_i8": [_p, _i64, _i, _i, _i, _i, _i64, _p],
+    "tg_bilinear_rect_check": [_i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i],
+    "tg_bilinear_rect_encode_f32": [_p, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _p, _p],
+    "tg_bilinear_rect_decode_f32": [_p, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _i, _i, _i, _p, _p],
+}
+RECT_SIGNATURES["tg_bilinear_rect_encode_f64"] = RECT_SIGNATURES["tg_bilinear_rect_encode_f32"]
+RECT_SIGNATURES["tg_bilinear_rect_decode_f64"] = RECT_SIGNATURES["tg_bilinear_rect_decode_f32"]
 # limits and status bits of include/tensor_game_flips.h
 TG_FLIP_MAX_K, TG_FLIP_MAX_BOUND, TG_FLIP_MAX_STEPS = 128, 63, 65536
 TG_FLIP_BAD_LENGTH, TG_FLIP_BAD_RANGE, TG_FLIP_BAD_SRC = 1, 2, 4
@@ -316,7 +325,7 @@ def _load() -> C.CDLL:
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
                            **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES, **FLIP2_SIGNATURES,
-                           **LIFT2_SIGNATURES, **BILINEAR_SIGNATURES}.items():
+                           **LIFT2_SIGNATURES, **BILINEAR_SIGNATURES, **RECT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

@@ -20,7 +20,10 @@ Construction proves the list (``ops.solution_canon`` against ``build_matmul_tens
 form, so null terms and a term followed by its negative cost no products; there is no way round the proof.  The kernels'
 arithmetic is defined bit for bit by the header; the result as a whole is as exact as the algorithm is: integer inputs
 whose intermediates stay below 2^24 (2^53 in float64) give the exact product, real inputs the error growth of the list.
-Not done here: a leaf GEMM of our own, half-precision operands, rectangular <n,m,p>, choosing ``levels``.
+Not done here: a leaf GEMM of our own, half-precision operands, choosing ``levels``.
+
+``RectBilinearMatmul`` is the same for a rectangular <n,m,p> (include/tensor_game_rect.h: A in n x m blocks, B in m x p,
+C in n x p, a list of any cube size S >= max(n*m, m*p, n*p)), and ``standard_rect`` its schoolbook list.
 """
 from __future__ import annotations
 
@@ -30,9 +33,9 @@ from typing import Optional
 import torch
 
 from . import functional, ops
-from ._lib import TG_BILINEAR_MAX_N, TG_BILINEAR_MIN_N, TensorGameError
+from ._lib import TG_BILINEAR_MAX_N, TG_BILINEAR_MIN_N, TG_MAX_S, TG_SOL_MAX_SHIFT, TensorGameError
 
-__all__ = ["BilinearMatmul"]
+__all__ = ["BilinearMatmul", "RectBilinearMatmul", "standard_rect"]
 
 
 def _byte_range(t: torch.Tensor):
@@ -168,4 +171,165 @@ class BilinearMatmul:
         if out is None:
             return m
         out.copy_(m)
+        return out
+
+
+def standard_rect(n: int, m: int, p: int, S: Optional[int] = None, shift: int = 1) -> torch.Tensor:
+    """The schoolbook algorithm for <n,m,p> (include/tensor_game_rect.h) as archive-format tokens: int8 (n*m*p,3S) on the
+    host, term (i,j,k) in ascending order with u[i*m+j] = v[j*p+k] = w[i*p+k] = 1, every other coefficient 0.  S
+    defaults to max(n*m, m*p, n*p).  A proven list to start walks from, or to run."""
+    n, m, p = int(n), int(m), int(p)
+    if min(n, m, p) < 1:
+        raise TensorGameError("standard_rect", -1, f"n={n}, m={m}, p={p}: every dimension must be at least 1")
+    need = max(n * m, m * p, n * p)
+    S = need if S is None else int(S)
+    if not need <= S <= TG_MAX_S:
+        raise TensorGameError("standard_rect", -1, f"S={S} outside [max(n*m, m*p, n*p)={need},{TG_MAX_S}]")
+    if not 0 <= shift <= TG_SOL_MAX_SHIFT:
+        raise TensorGameError("standard_rect", -1, f"shift={shift} outside [0,{TG_SOL_MAX_SHIFT}]")
+    i, j, k = (x.reshape(-1) for x in torch.meshgrid(torch.arange(n), torch.arange(m), torch.arange(p), indexing="ij"))
+    tokens = torch.full((n * m * p, 3 * S), int(shift), dtype=torch.int8)
+    t = torch.arange(n * m * p)
+    tokens[t, i * m + j] = tokens[t, S + j * p + k] = tokens[t, 2 * S + i * p + k] = int(shift) + 1
+    return tokens
+
+
+class RectBilinearMatmul:
+    """A proven factorisation of the rectangular tensor <n,m,p> in a cube of size S, run as a matrix multiplication:
+    A is cut into n x m blocks, B into m x p, C into n x p, and R block products replace n*m*p.
+
+        alg = RectBilinearMatmul(tokens, rank, n=2, m=2, p=3, S=None, shift=1, levels=1)   # tokens int8 (K,3S), device
+        alg = RectBilinearMatmul.from_archive(arch, 2, 2, 3, index=None, levels=1)
+        C = alg(A, B, out=None, pad=False, leaf=torch.bmm)        # A (...,P,Q) @ B (...,Q,T), float32 or float64
+        alg.n, alg.m, alg.p, alg.S, alg.rank, alg.levels, alg.products
+
+    Construction proves the list (``ops.solution_canon`` against ``functional.matmul_target(1, n, m, p, S)``) and runs
+    the canonical form; there is no way round the proof.  The encodes and decodes are ``ops.bilinear_rect_encode`` and
+    ``ops.bilinear_rect_decode`` (include/tensor_game_rect.h states their arithmetic bit for bit); the padding entries
+    of the list (beyond n*m, m*p, n*p) are not read."""
+
+    def __init__(self, tokens: torch.Tensor, rank: int, n: int, m: int, p: int, S: Optional[int] = None, shift: int = 1,
+                 levels: int = 1):
+        """``tokens`` int8 (K,3S) on a ROCm device, of which the first ``rank`` rows are the list; S defaults to the
+        width of ``tokens``.  Raises TensorGameError unless the list is proven against <n,m,p> in that cube.  One host
+        sync (the proof's verdict)."""
+        fn = "RectBilinearMatmul"
+        if not tokens.is_cuda:
+            raise TensorGameError(fn, -1, f"tokens must live on a ROCm device (got {tokens.device}); there is no CPU path")
+        self.n, self.m, self.p, self.shift, self.levels = int(n), int(m), int(p), int(shift), int(levels)
+        if min(self.n, self.m, self.p) < 1:
+            raise TensorGameError(fn, -1, f"n={n}, m={m}, p={p}: every dimension must be at least 1")
+        if self.levels < 1:
+            raise TensorGameError(fn, -1, f"levels={levels} < 1")
+        need = max(self.n * self.m, self.m * self.p, self.n * self.p)
+        if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] % 3:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+        self.S = tokens.shape[1] // 3 if S is None else int(S)
+        if not need <= self.S <= TG_MAX_S:
+            raise TensorGameError(fn, -1, f"S={self.S} outside [max(n*m, m*p, n*p)={need},{TG_MAX_S}] for "
+                                          f"<{n},{m},{p}>")
+        if tokens.shape[1] != 3 * self.S:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * self.S}) for S={self.S}, got "
+                                          f"{tuple(tokens.shape)}")
+        dev = tokens.device
+        target = functional.matmul_target(1, self.n, self.m, self.p, self.S, device=dev)
+        lengths = torch.full((1,), int(rank), dtype=torch.int64, device=dev)
+        canon, crank, _, res = ops.solution_canon(target, tokens[None], lengths, shift=self.shift)
+        res, crank = torch.stack((res, crank)).flatten().tolist()      # the one host sync
+        if res != 0:
+            what = "a bad row (its length, or a negation that leaves int8)" if res < 0 else f"residual_nnz={res}"
+            raise TensorGameError(fn, -1, f"the list is no factorisation of <{n},{m},{p}> at S={self.S}: {what}")
+        self.rank = int(crank)
+        self.tokens = canon[0, :self.rank].contiguous()
+        self.device = dev
+
+    @classmethod
+    def from_archive(cls, arch, n: int, m: int, p: int, index: Optional[int] = None,
+                     levels: int = 1) -> "RectBilinearMatmul":
+        """The algorithm of entry ``index`` of a ``SolutionArchive`` of cube size arch.S (None: the entry of lowest rank,
+        the first of equals).  The entry is proven again, against <n,m,p>.  Synchronises (``entries``)."""
+        fn = "RectBilinearMatmul.from_archive"
+        tokens, rank, _, _ = arch.entries()
+        ranks = rank.tolist()
+        if not ranks:
+            raise TensorGameError(fn, -1, "the archive is empty")
+        if index is None:
+            index = ranks.index(min(ranks))
+        if not 0 <= index < len(ranks):
+            raise TensorGameError(fn, -1, f"index={index} outside [0,{len(ranks)})")
+        return cls(tokens[index].contiguous(), ranks[index], n, m, p, S=arch.S, shift=arch.shift, levels=levels)
+
+    @property
+    def products(self) -> int:
+        """Leaf block products of one call: rank ** levels, where the schoolbook method takes (n*m*p) ** levels."""
+        return self.rank ** self.levels
+
+    def __call__(self, A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None, pad: bool = False,
+                 leaf=torch.bmm) -> torch.Tensor:
+        """A (...,P,Q) times B (...,Q,T), float32 or float64 on the list's device, equal leading dimensions.  P must be
+        a multiple of n^levels, Q of m^levels and T of p^levels, or ``pad`` zero-pads them up (with torch) and slices the
+        result.  ``leaf`` takes two (batch * rank^levels, ., .) operands and returns their batched product.  ``out``
+        (...,P,T) may not overlap A or B.  No host sync; capturable on one stream."""
+        fn = "RectBilinearMatmul"
+        for t, name in ((A, "A"), (B, "B")):
+            if not t.is_cuda:
+                raise TensorGameError(fn, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
+            if t.device != self.device:
+                raise TensorGameError(fn, -1, f"{name} is on {t.device}, the list on {self.device}")
+            if t.dim() < 2:
+                raise TensorGameError(fn, -1, f"{name} must have at least two dimensions, got {tuple(t.shape)}")
+        if A.dtype != B.dtype:
+            raise TensorGameError(fn, -1, f"mixed dtypes: A is {A.dtype}, B is {B.dtype}")
+        if A.dtype not in (torch.float32, torch.float64):
+            raise TensorGameError(fn, -1, f"A and B must be float32 or float64, got {A.dtype}")
+        lead, (P, Q), (Q2, T) = tuple(A.shape[:-2]), A.shape[-2:], B.shape[-2:]
+        if tuple(B.shape[:-2]) != lead or Q2 != Q:
+            raise TensorGameError(fn, -1, f"A {tuple(A.shape)} and B {tuple(B.shape)} do not multiply: equal leading "
+                                          "dimensions and Q are required")
+        if out is not None:
+            if out.dtype != A.dtype or tuple(out.shape) != (*lead, P, T) or out.device != A.device:
+                raise TensorGameError(fn, -1, f"out must be {A.dtype} {(*lead, P, T)} on {A.device}, got {out.dtype} "
+                                              f"{tuple(out.shape)} on {out.device}")
+            for t, name in ((A, "A"), (B, "B")):
+                if _overlap(out, t):
+                    raise TensorGameError(fn, -1, f"out overlaps {name}: in-place operation is not supported")
+        n, m, p, R = self.n, self.m, self.p, self.rank
+        sizes = {"P": (P, n, "n"), "Q": (Q, m, "m"), "T": (T, p, "p")}
+        up = {name: -size % d ** self.levels for name, (size, d, _) in sizes.items()}
+        if any(up.values()) and not pad:
+            name = next(k for k, v in up.items() if v)
+            size, d, letter = sizes[name]
+            raise TensorGameError(fn, -1, f"{name}={size} is no multiple of {letter}^levels={d ** self.levels} (pad=True "
+                                          "pads with zeros)")
+        batch = math.prod(lead)
+        a, b = A.reshape(batch, P, Q), B.reshape(batch, Q, T)
+        if any(up.values()):
+            a = torch.nn.functional.pad(a, (0, up["Q"], 0, up["P"]))
+            b = torch.nn.functional.pad(b, (0, up["T"], 0, up["Q"]))
+        a = a if a.stride(2) == 1 else a.contiguous()
+        b = b if b.stride(2) == 1 else b.contiguous()
+        for _ in range(self.levels):
+            a = ops.bilinear_rect_encode(a, self.tokens, R, n, m, 0, self.shift).flatten(0, 1)
+            b = ops.bilinear_rect_encode(b, self.tokens, R, m, p, 1, self.shift).flatten(0, 1)
+        mm = leaf(a, b)
+        if tuple(mm.shape) != (a.shape[0], a.shape[1], b.shape[2]) or mm.dtype != A.dtype:
+            raise TensorGameError(fn, -1, f"leaf returned {mm.dtype} {tuple(mm.shape)}, expected {A.dtype} "
+                                          f"{(a.shape[0], a.shape[1], b.shape[2])}")
+        mm = mm.contiguous()
+        direct = None                                   # the last decode writes into `out` itself where it can
+        if out is not None and not any(up.values()) and out.stride(-1) == 1:
+            try:
+                direct = out.view(batch, P, T)
+            except RuntimeError:
+                pass
+        for level in range(self.levels):
+            mm = mm.view(mm.shape[0] // R, R, mm.shape[1], mm.shape[2])
+            mm = ops.bilinear_rect_decode(mm, self.tokens, R, n, p, self.shift,
+                                          out=direct if level == self.levels - 1 else None)
+        if direct is not None:
+            return out
+        mm = mm[:, :P, :T].reshape(*lead, P, T)
+        if out is None:
+            return mm
+        out.copy_(mm)
         return out

@@ -7,12 +7,12 @@ errors and never range-checks tokens, utils.py:64-66).
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
-from ._lib import TensorGameError
+from ._lib import TG_MAX_S, TensorGameError
 
 
 def _as_state(t: torch.Tensor) -> torch.Tensor:
@@ -112,6 +112,18 @@ def build_matmul_tensor(dim_t: int, dim_i: int, dim_j: int, dim_k: int, device="
     S = dim_i * dim_i
     out = torch.zeros((dim_t, S, S, S), dtype=torch.int8, device=device)
     ops.reset_matmul(out[:1], dim_i)
+    return out
+
+
+def matmul_target(dim_t: int, n: int, m: int, p: int, S: Optional[int] = None, device="cuda") -> torch.Tensor:
+    """<n,m,p> (A n x m, B m x p, C n x p; include/tensor_game_rect.h) in frame 0 of int8 (dim_t,S,S,S), zeros
+    elsewhere: entry (i*m+j, j*p+k, i*p+k) is 1.  S defaults to max(n*m, m*p, n*p), the smallest cube that holds it."""
+    n, m, p = int(n), int(m), int(p)
+    S = max(n * m, m * p, n * p, 1) if S is None else int(S)
+    if not 1 <= S <= TG_MAX_S:
+        raise TensorGameError("matmul_target", -1, f"S={S} outside [1,{TG_MAX_S}]")
+    out = torch.zeros((dim_t, S, S, S), dtype=torch.int8, device=device)
+    ops.reset_matmul_rect(out[:1], n, m, p)
     return out
 
 

@@ -38,6 +38,7 @@ __all__ = [
     "flip2_check", "flip2_begin", "flip2_advance", "flip2_residual",
     "lift2_check", "lift2_workspace_bytes", "lift2_signs",
     "bilinear_check", "bilinear_encode", "bilinear_decode",
+    "reset_matmul_rect", "bilinear_rect_check", "bilinear_rect_encode", "bilinear_rect_decode",
 ]
 
 
@@ -1960,4 +1961,76 @@ def bilinear_decode(M, tokens, R: int, n: int, shift: int = 1, out=None) -> torc
     tokens = _bilinear_list(tokens, R, n, M.device, fn)
     _launch(M.device, f"tg_bilinear_decode_{suffix}", _ptr(M), batch, rows, cols, ld, stride, _ptr(tokens), int(R), int(n),
             int(shift), _ptr(out))
+    return out
+
+
+def reset_matmul_rect(out, n: int, m: int, p: int):
+    """The target <n,m,p> of include/tensor_game_rect.h into every game of ``out`` int8 (B,S,S,S), in one launch: entry
+    (i*m+j, j*p+k, i*p+k) is 1, every other entry 0.  S >= max(n*m, m*p, n*p); the bytes between games stay."""
+    B, S, stride = _state_layout(out, "out")
+    _launch(out.device, "tg_reset_matmul_rect_i8", _ptr(out), B, int(n), int(m), int(p), S, stride)
+    return out
+
+
+def bilinear_rect_check(batch: int, rows: int, cols: int, ld: Optional[int] = None, batch_stride: Optional[int] = None,
+                        R: int = 1, S: int = 4, gr: int = 2, gc: int = 2, part: int = 0, shift: int = 1,
+                        elem_bytes: int = 4) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_bilinear_rect_encode_* / tg_bilinear_rect_decode_* take
+    these sizes (``ld`` defaults to ``cols``, ``batch_stride`` to ``rows * ld``).  Host only."""
+    ld = cols if ld is None else ld
+    call("tg_bilinear_rect_check", int(batch), int(rows), int(cols), int(ld),
+         int(rows * ld if batch_stride is None else batch_stride), int(R), int(S), int(gr), int(gc), int(part), int(shift),
+         int(elem_bytes))
+
+
+def _bilinear_rect_list(tokens: torch.Tensor, R: int, dev, fn: str):
+    """(tokens made contiguous, S) of a list of cube size S: int8 (K,3S) on ``dev`` with K >= R."""
+    _need_gpu(tokens, "tokens")
+    if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] % 3 or tokens.device != dev:
+        raise TensorGameError(fn, -1, f"tokens must be int8 (K,3S) on {dev}, got {tokens.dtype} {tuple(tokens.shape)} on "
+                                      f"{tokens.device}")
+    if R > tokens.shape[0]:
+        raise TensorGameError(fn, -1, f"R={R} above the K={tokens.shape[0]} rows of tokens")
+    return (tokens if tokens.is_contiguous() else tokens.contiguous()), tokens.shape[1] // 3
+
+
+def bilinear_rect_encode(X, tokens, R: int, gr: int, gc: int, part: int, shift: int = 1, out=None) -> torch.Tensor:
+    """The R block combinations of ``batch`` matrices in one launch (include/tensor_game_rect.h): X float32 or float64
+    (batch,rows,cols), any row and batch stride (a view is not copied), cut into gr x gc blocks of (h,w); tokens int8
+    (K,3S) with S >= gr*gc, of which rows 0 .. R-1 and the first gr*gc entries of part ``part`` (0: u, 1: v) are used.
+    Returns ``out`` (batch,R,h,w), contiguous: out[b][r] = sum_e (tokens[r][part*S+e] - shift) * block e of X[b], by the
+    header's arithmetic rule.  No host sync."""
+    fn = "bilinear_rect_encode"
+    batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(X, "X", fn)
+    tokens, S = _bilinear_rect_list(tokens, R, X.device, fn)
+    bilinear_rect_check(batch, rows, cols, ld, stride, R, S, gr, gc, part, shift, eb)
+    if out is not None:
+        _need_gpu(out, "out")
+    out = _out(out, (batch, int(R), rows // gr, cols // gc), X.dtype, X.device, "out")
+    _launch(X.device, f"tg_bilinear_rect_encode_{suffix}", _ptr(X), batch, rows, cols, ld, stride, _ptr(tokens), int(R), S,
+            int(gr), int(gc), int(part), int(shift), _ptr(out))
+    return out
+
+
+def bilinear_rect_decode(M, tokens, R: int, gr: int, gc: int, shift: int = 1, out=None) -> torch.Tensor:
+    """The gr x gc blocks of ``batch`` result matrices from the R block products, in one launch: M float32 or float64
+    (batch,R,h,w), contiguous; the first gr*gc entries of part 2 (w) of rows 0 .. R-1 of tokens are used.  Returns ``out``
+    (batch,gr*h,gc*w), which may be a strided view when given (column stride 1): block e of out[b] = sum_r
+    (tokens[r][2S+e] - shift) * M[b][r].  Every element is written.  No host sync."""
+    fn = "bilinear_rect_decode"
+    _need_gpu(M, "M")
+    if M.dtype not in _BILINEAR_DTYPES or M.dim() != 4 or M.shape[1] != R or not M.is_contiguous():
+        raise TensorGameError(fn, -1, f"M must be contiguous float32 or float64 (batch,R={R},h,w), got {M.dtype} "
+                                      f"{tuple(M.shape)}")
+    shape = (M.shape[0], gr * M.shape[2], gc * M.shape[3])
+    if out is None:
+        out = torch.empty(shape, dtype=M.dtype, device=M.device)
+    elif out.dtype != M.dtype or tuple(out.shape) != shape or out.device != M.device:
+        raise TensorGameError(fn, -1, f"out must be {M.dtype} {shape} on {M.device}, got {out.dtype} {tuple(out.shape)} "
+                                      f"on {out.device}")
+    batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(out, "out", fn)
+    tokens, S = _bilinear_rect_list(tokens, R, M.device, fn)
+    bilinear_rect_check(batch, rows, cols, ld, stride, R, S, gr, gc, 2, shift, eb)
+    _launch(M.device, f"tg_bilinear_rect_decode_{suffix}", _ptr(M), batch, rows, cols, ld, stride, _ptr(tokens), int(R), S,
+            int(gr), int(gc), int(shift), _ptr(out))
     return out

@@ -169,6 +169,67 @@ class SymmetryGroup:
                 gens.append(sandwich(ar, ar, ar, *sg))
         return cls.generate(np.stack(gens), S, device)
 
+    @classmethod
+    def matmul_rect(cls, n: int, m: int, p: int, S: Optional[int] = None, device=None, signs: bool = True) -> "SymmetryGroup":
+        """The symmetries of the rectangular tensor <n,m,p> in a cube of size S (include/tensor_game_rect.h:
+        T[i*m+j, j*p+k, i*p+k] = 1, S >= max(n*m, m*p, n*p), the default) that keep the vocabulary.  The sandwich elements
+        are those of ``matmul`` with P in S_n, Q in S_m, R in S_p: pi_0[i*m+j] = P(i)*m+Q(j), pi_1[j*p+k] = Q(j)*p+R(k),
+        pi_2[i*p+k] = P(i)*p+R(k), signs a_i*b_j, b_j*c_k, a_i*c_k.  A mode element exists only where two dimensions agree:
+        n == m: rho = (0,2,1) with (tr, id, id); n == p: rho = (1,0,2) with (tr, tr, tr); m == p: rho = (2,1,0) with
+        (id, tr, id), tr the transpose of the mode's own r x c grid, x*c+y -> y*r+x.  A padding index (at or beyond its
+        mode's size) maps to itself with sign +1.  Without signs the order is n! m! p! times the number of permutations
+        of the triple (n,m,p) that leave it unchanged: 1 296 at (3,3,3), which is ``matmul(3, signs=False)``, 48 at
+        (2,2,3), 12 at (2,3,1); with signs (2,2,3) has 3 072 elements, above TG_ORBIT_MAX_G, and is refused."""
+        fn = "SymmetryGroup.matmul_rect"
+        n, m, p = int(n), int(m), int(p)
+        if min(n, m, p) < 1:
+            raise TensorGameError(fn, -1, f"n={n}, m={m}, p={p}: every dimension must be at least 1")
+        need = max(n * m, m * p, n * p)
+        S = need if S is None else int(S)
+        if not need <= S <= TG_MAX_S:
+            raise TensorGameError(fn, -1, f"S={S} outside [max(n*m, m*p, n*p)={need},{TG_MAX_S}]")
+        grids = [(n, m), (m, p), (n, p)]                                   # mode d is an r x c grid
+
+        def padded(part, fill):
+            """(3,S) from the three modes' own entries, ``fill`` (None: the index itself) on the padding."""
+            out = np.tile(np.arange(S), (3, 1)) if fill is None else np.full((3, S), fill, np.int64)
+            for d in range(3):
+                out[d, :part[d].shape[0]] = part[d]
+            return out
+
+        def tr(d):
+            r, c = grids[d]
+            return (np.arange(c)[None, :] * r + np.arange(r)[:, None]).reshape(-1)   # x*c+y -> y*r+x
+
+        ident = [np.arange(r * c) for r, c in grids]
+        one = np.ones((3, S), np.int64)
+        gens = []
+        if n == m:
+            gens.append(_encode((0, 2, 1), padded([tr(0), ident[1], ident[2]], None), one))
+        if n == p:
+            gens.append(_encode((1, 0, 2), padded([tr(0), tr(1), tr(2)], None), one))
+        if m == p:
+            gens.append(_encode((2, 1, 0), padded([ident[0], tr(1), ident[2]], None), one))
+
+        def sandwich(P, Q, R, a, b, c):
+            pi = [(P[:, None] * m + Q[None, :]).reshape(-1), (Q[:, None] * p + R[None, :]).reshape(-1),
+                  (P[:, None] * p + R[None, :]).reshape(-1)]
+            sg = [np.outer(a, b).reshape(-1), np.outer(b, c).reshape(-1), np.outer(a, c).reshape(-1)]
+            return _encode((0, 1, 2), padded(pi, None), padded(sg, 1))
+
+        dims = (n, m, p)
+        for which in range(3):
+            for i in range(dims[which] - 1):
+                perm = [np.arange(d) for d in dims]
+                perm[which][[i, i + 1]] = [i + 1, i]
+                gens.append(sandwich(*perm, *[np.ones(d, np.int64) for d in dims]))
+            for i in range(dims[which] if signs else 0):
+                sg = [np.ones(d, np.int64) for d in dims]
+                sg[which][i] = -1
+                gens.append(sandwich(*[np.arange(d) for d in dims], *sg))
+        gens = np.stack(gens) if gens else np.empty((0, 3 * S + 1), np.uint8)
+        return cls.generate(gens, S, device)
+
     # ---- the set
     @property
     def order(self) -> int:

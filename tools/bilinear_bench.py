@@ -16,6 +16,17 @@ Rows "encode" and "decode": the first level of the same call alone, its bytes (e
 byte written once: (N^2 + R (N/2)^2) * 4) over its time, alternating with a device copy of the same byte count (``copy_``
 between two contiguous float32 tensors of half that many bytes each, which moves 16 bytes per lane), and the ratio of the
 two rates.  Writes OUT_DIR/bilinear_bench.json.
+
+    python tools/bilinear_bench.py OUT_DIR --rect [--sizes ...] [--reps 7] [--warmup 2]
+
+The rectangular entries (include/tensor_game_rect.h) instead, with the same method; writes OUT_DIR/bilinear_rect_bench.json.
+Rows "square": the standard list of <n,n,n>, n = 2..5, at N rounded down to a multiple of 4n (so that every call takes
+16-byte packs), through the square entries and through the rectangular ones on the grid n x n, alternating in one loop,
+five times over: five medians of each, the spread (lowest to highest median) of the square entry, and whether the median
+of the rectangular entry's medians lies inside it.  Rows "footprint": the grids 4 x 5 and 5 x 6 (blocks of N/gr x N/gc,
+the width rounded down to a multiple of 4; R = 2 gr gc terms with a third of the coefficients +-1), encode and decode,
+next to ``copy_`` of the same byte count.  Every row gives its bytes (each read or written once) and the share of the
+8 TB/s HBM peak they reach.
 """
 from __future__ import annotations
 
@@ -31,9 +42,10 @@ import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-from mat_mul_amd import BilinearMatmul, ops  # noqa: E402
+from mat_mul_amd import BilinearMatmul, ops, standard_rect  # noqa: E402
 
 DEV = "cuda:0"
+HBM_PEAK_TB_PER_S = 8.0
 
 
 def standard_2x2(shift=1):
@@ -84,13 +96,86 @@ def temporaries_bytes(N, rank, levels):
     return total
 
 
+def rate(nbytes, st):
+    tb = nbytes / st["median_us"] * 1e-6
+    return {"TB_per_s": tb, "share_of_hbm_peak": tb / HBM_PEAK_TB_PER_S}
+
+
+def rect_rows(args):
+    """The --rect rows (the module's text says what they are)."""
+    out = Path(args.out) / "bilinear_rect_bench.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    res = {"torch": torch.__version__, "device": torch.cuda.get_device_name(0), "dtype": "float32",
+           "hbm_peak_TB_per_s": HBM_PEAK_TB_PER_S, "rows": []}
+    gen = torch.Generator(device=DEV).manual_seed(0)
+
+    def emit(row):
+        res["rows"].append(row)
+        print(json.dumps(row), flush=True)
+        out.write_text(json.dumps(res, indent=1) + "\n")
+
+    for n in (2, 3, 4, 5):
+        tok, R = standard_rect(n, n, n).to(DEV), n ** 3
+        for N in args.sizes:
+            N = N // (4 * n) * (4 * n)
+            nbytes = (N * N + R * (N // n) ** 2) * 4
+            if 3 * nbytes > torch.cuda.mem_get_info(0)[0]:
+                emit({"kind": "square", "n": n, "N": N, "skipped": "memory"})
+                continue
+            X = torch.randn((1, N, N), device=DEV, generator=gen)
+            Y = torch.empty((1, R, N // n, N // n), device=DEV)
+            C = torch.empty_like(X)
+            fns = [lambda: ops.bilinear_encode(X, tok, R, n, 0, out=Y), lambda: ops.bilinear_rect_encode(X, tok, R, n, n, 0, out=Y),
+                   lambda: ops.bilinear_decode(Y, tok, R, n, out=C), lambda: ops.bilinear_rect_decode(Y, tok, R, n, n, out=C)]
+            rounds = [alternate(fns, args.warmup, args.reps) for _ in range(5)]
+            for half, (sq, re) in (("encode", (0, 1)), ("decode", (2, 3))):
+                sq_med = [r[sq]["median_us"] for r in rounds]
+                re_med = [r[re]["median_us"] for r in rounds]
+                mid = statistics.median(re_med)
+                emit({"kind": "square", "half": half, "n": n, "N": N, "R": R, "bytes": nbytes, "square_medians_us": sq_med,
+                      "rect_medians_us": re_med, "square_spread_us": [min(sq_med), max(sq_med)], "rect_median_us": mid,
+                      "rect_inside_square_spread": min(sq_med) <= mid <= max(sq_med),
+                      "rect_over_square": mid / statistics.median(sq_med),
+                      "square": rate(nbytes, {"median_us": statistics.median(sq_med)}), "rect": rate(nbytes, {"median_us": mid})})
+            del X, Y, C
+            torch.cuda.empty_cache()
+    for gr, gc in ((4, 5), (5, 6)):
+        S, R = gr * gc, 2 * gr * gc
+        f = torch.randint(0, 6, (R, 3 * S), generator=torch.Generator().manual_seed(gr))
+        tok = (torch.where(f == 0, 1, 0) - torch.where(f == 1, 1, 0) + 1).to(torch.int8).to(DEV)   # a third +-1
+        for N in args.sizes:
+            h, w = N // gr, N // gc // 4 * 4
+            nbytes = (gr * h * gc * w + R * h * w) * 4
+            if 3 * nbytes > torch.cuda.mem_get_info(0)[0]:
+                emit({"kind": "footprint", "grid": [gr, gc], "N": N, "skipped": "memory"})
+                continue
+            X = torch.randn((1, gr * h, gc * w), device=DEV, generator=gen)
+            Y = torch.empty((1, R, h, w), device=DEV)
+            C = torch.empty_like(X)
+            src, dst = (torch.empty(nbytes // 8, dtype=torch.float32, device=DEV) for _ in range(2))
+            src.normal_(generator=gen)
+            ops.bilinear_rect_encode(X, tok, R, gr, gc, 0, out=Y)
+            enc, cp1, dec, cp2 = alternate([lambda: ops.bilinear_rect_encode(X, tok, R, gr, gc, 0, out=Y), lambda: dst.copy_(src),
+                                            lambda: ops.bilinear_rect_decode(Y, tok, R, gr, gc, out=C), lambda: dst.copy_(src)],
+                                           args.warmup, args.reps)
+            for half, mine, copy in (("encode", enc, cp1), ("decode", dec, cp2)):
+                emit({"kind": "footprint", "half": half, "grid": [gr, gc], "rows": gr * h, "cols": gc * w, "R": R,
+                      "bytes": nbytes, **mine, **rate(nbytes, mine), "copy": copy, "copy_TB_per_s": rate(nbytes, copy)["TB_per_s"],
+                      "share_of_copy": copy["median_us"] / mine["median_us"]})
+            del X, Y, C, src, dst
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
     ap.add_argument("--sizes", type=int, nargs="*", default=[2048, 4096, 8192])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rect", action="store_true", help="the rectangular entries instead (bilinear_rect_bench.json)")
     args = ap.parse_args()
+    if args.rect:
+        return rect_rows(args)
     out = Path(args.out) / "bilinear_bench.json"
     out.parent.mkdir(parents=True, exist_ok=True)
     strassen = np.load(ROOT / "tests" / "golden" / "strassen.npz")["tokens"].astype(np.int8)
