@@ -53,43 +53,31 @@ def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b1 and b0 < a1
 
 
-class BilinearMatmul:
-    def __init__(self, tokens: torch.Tensor, rank: int, n: int = 2, shift: int = 1, levels: int = 1):
-        """``tokens`` int8 (K,3n^2) on a ROCm device, of which the first ``rank`` rows are the list.  Raises
-        TensorGameError unless the list is proven against <n,n,n>.  One host sync (the proof's verdict)."""
-        fn = "BilinearMatmul"
-        if not tokens.is_cuda:
-            raise TensorGameError(fn, -1, f"tokens must live on a ROCm device (got {tokens.device}); there is no CPU path")
-        self.n, self.shift, self.levels = int(n), int(shift), int(levels)
-        if not TG_BILINEAR_MIN_N <= self.n <= TG_BILINEAR_MAX_N:
-            raise TensorGameError(fn, -1, f"n={n} outside [{TG_BILINEAR_MIN_N},{TG_BILINEAR_MAX_N}]")
-        if self.levels < 1:
-            raise TensorGameError(fn, -1, f"levels={levels} < 1")
-        S = self.n * self.n
-        if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] != 3 * S:
-            raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * S}) for n={n}, got {tokens.dtype} "
-                                          f"{tuple(tokens.shape)}")
-        dev = tokens.device
-        target = functional.build_matmul_tensor(1, self.n, self.n, self.n, device=dev)
-        lengths = torch.full((1,), int(rank), dtype=torch.int64, device=dev)
+def _need_device(fn: str, t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise TensorGameError(fn, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
+
+
+class _Bilinear:
+    """What the two classes share: the proof, the index choice of ``from_archive`` and the call.  A class gives ``_fn`` (its
+    name in messages), ``_grid()`` (the three grid sizes and what a message calls them), ``_encode`` and ``_decode``."""
+
+    def _prove(self, tokens: torch.Tensor, rank: int, target: torch.Tensor, what: str) -> None:
+        """Sets ``rank``, ``tokens`` (the canonical form) and ``device``, or raises: the list is no factorisation of
+        ``what``.  One host sync."""
+        lengths = torch.full((1,), int(rank), dtype=torch.int64, device=tokens.device)
         canon, crank, _, res = ops.solution_canon(target, tokens[None], lengths, shift=self.shift)
         res, crank = torch.stack((res, crank)).flatten().tolist()      # the one host sync
         if res != 0:
-            what = "a bad row (its length, or a negation that leaves int8)" if res < 0 else f"residual_nnz={res}"
-            raise TensorGameError(fn, -1, f"the list is no factorisation of <{n},{n},{n}>: {what}")
+            why = "a bad row (its length, or a negation that leaves int8)" if res < 0 else f"residual_nnz={res}"
+            raise TensorGameError(self._fn, -1, f"the list is no factorisation of {what}: {why}")
         self.rank = int(crank)
         self.tokens = canon[0, :self.rank].contiguous()
-        self.device = dev
+        self.device = tokens.device
 
-    @classmethod
-    def from_archive(cls, arch, index: Optional[int] = None, levels: int = 1) -> "BilinearMatmul":
-        """The algorithm of entry ``index`` of a ``SolutionArchive`` (None: the entry of lowest rank, the first of
-        equals).  The entry is proven again, against <n,n,n> with n = sqrt(arch.S): an archive may hold factorisations
-        of other targets.  Synchronises (``entries``)."""
-        fn = "BilinearMatmul.from_archive"
-        n = math.isqrt(arch.S)
-        if n * n != arch.S:
-            raise TensorGameError(fn, -1, f"the archive is of S={arch.S}, which is no square: no <n,n,n>")
+    @staticmethod
+    def _entry(fn: str, arch, index: Optional[int]):
+        """(tokens, rank) of entry ``index`` of an archive (None: the entry of lowest rank, the first of equals)."""
         tokens, rank, _, _ = arch.entries()
         ranks = rank.tolist()
         if not ranks:
@@ -98,23 +86,23 @@ class BilinearMatmul:
             index = ranks.index(min(ranks))
         if not 0 <= index < len(ranks):
             raise TensorGameError(fn, -1, f"index={index} outside [0,{len(ranks)})")
-        return cls(tokens[index].contiguous(), ranks[index], n=n, shift=arch.shift, levels=levels)
+        return tokens[index].contiguous(), ranks[index]
 
     @property
     def products(self) -> int:
-        """Leaf block products of one call: rank ** levels, where the schoolbook method takes n ** (3 * levels)."""
+        """Leaf block products of one call: rank ** levels, where the schoolbook method takes (n*m*p) ** levels
+        (n ** (3 * levels) on the square grid)."""
         return self.rank ** self.levels
 
     def __call__(self, A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None, pad: bool = False,
                  leaf=torch.bmm) -> torch.Tensor:
-        """A (...,P,Q) times B (...,Q,T), float32 or float64 on the list's device, equal leading dimensions.  P, Q and T
-        must be multiples of n^levels, or ``pad`` zero-pads them up (with torch) and slices the result.  ``leaf`` takes
-        two (batch * rank^levels, ., .) operands and returns their batched product.  ``out`` (...,P,T) may not overlap
-        A or B.  No host sync; capturable on one stream."""
-        fn = "BilinearMatmul"
+        """A (...,P,Q) times B (...,Q,T), float32 or float64 on the list's device, equal leading dimensions.  P must be
+        a multiple of n^levels, Q of m^levels and T of p^levels (m = p = n in the square class), or ``pad`` zero-pads
+        them up (with torch) and slices the result.  ``leaf`` takes two (batch * rank^levels, ., .) operands and returns
+        their batched product.  ``out`` (...,P,T) may not overlap A or B.  No host sync; capturable on one stream."""
+        fn = self._fn
         for t, name in ((A, "A"), (B, "B")):
-            if not t.is_cuda:
-                raise TensorGameError(fn, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
+            _need_device(fn, t, name)
             if t.device != self.device:
                 raise TensorGameError(fn, -1, f"{name} is on {t.device}, the list on {self.device}")
             if t.dim() < 2:
@@ -134,11 +122,12 @@ class BilinearMatmul:
             for t, name in ((A, "A"), (B, "B")):
                 if _overlap(out, t):
                     raise TensorGameError(fn, -1, f"out overlaps {name}: in-place operation is not supported")
-        D = self.n ** self.levels
-        up = {name: -size % D for name, size in (("P", P), ("Q", Q), ("T", T))}
+        sizes = {name: (size, d, letter) for name, size, (d, letter) in zip("PQT", (P, Q, T), self._grid())}
+        up = {name: -size % d ** self.levels for name, (size, d, _) in sizes.items()}
         if any(up.values()) and not pad:
             name = next(k for k, v in up.items() if v)
-            raise TensorGameError(fn, -1, f"{name}={dict(P=P, Q=Q, T=T)[name]} is no multiple of n^levels={D} (pad=True "
+            size, d, letter = sizes[name]
+            raise TensorGameError(fn, -1, f"{name}={size} is no multiple of {letter}^levels={d ** self.levels} (pad=True "
                                           "pads with zeros)")
         batch = math.prod(lead)
         a, b = A.reshape(batch, P, Q), B.reshape(batch, Q, T)
@@ -148,8 +137,8 @@ class BilinearMatmul:
         a = a if a.stride(2) == 1 else a.contiguous()
         b = b if b.stride(2) == 1 else b.contiguous()
         for _ in range(self.levels):
-            a = ops.bilinear_encode(a, self.tokens, self.rank, self.n, 0, self.shift).flatten(0, 1)
-            b = ops.bilinear_encode(b, self.tokens, self.rank, self.n, 1, self.shift).flatten(0, 1)
+            a = self._encode(a, 0).flatten(0, 1)
+            b = self._encode(b, 1).flatten(0, 1)
         m = leaf(a, b)
         if tuple(m.shape) != (a.shape[0], a.shape[1], b.shape[2]) or m.dtype != A.dtype:
             raise TensorGameError(fn, -1, f"leaf returned {m.dtype} {tuple(m.shape)}, expected {A.dtype} "
@@ -163,8 +152,7 @@ class BilinearMatmul:
                 pass
         for level in range(self.levels):
             m = m.view(m.shape[0] // self.rank, self.rank, m.shape[1], m.shape[2])
-            m = ops.bilinear_decode(m, self.tokens, self.rank, self.n, self.shift,
-                                    out=direct if level == self.levels - 1 else None)
+            m = self._decode(m, direct if level == self.levels - 1 else None)
         if direct is not None:
             return out
         m = m[:, :P, :T].reshape(*lead, P, T)
@@ -172,6 +160,48 @@ class BilinearMatmul:
             return m
         out.copy_(m)
         return out
+
+
+class BilinearMatmul(_Bilinear):
+    _fn = "BilinearMatmul"
+
+    def __init__(self, tokens: torch.Tensor, rank: int, n: int = 2, shift: int = 1, levels: int = 1):
+        """``tokens`` int8 (K,3n^2) on a ROCm device, of which the first ``rank`` rows are the list.  Raises
+        TensorGameError unless the list is proven against <n,n,n>.  One host sync (the proof's verdict)."""
+        fn = self._fn
+        _need_device(fn, tokens, "tokens")
+        self.n, self.shift, self.levels = int(n), int(shift), int(levels)
+        if not TG_BILINEAR_MIN_N <= self.n <= TG_BILINEAR_MAX_N:
+            raise TensorGameError(fn, -1, f"n={n} outside [{TG_BILINEAR_MIN_N},{TG_BILINEAR_MAX_N}]")
+        if self.levels < 1:
+            raise TensorGameError(fn, -1, f"levels={levels} < 1")
+        S = self.n * self.n
+        if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] != 3 * S:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * S}) for n={n}, got {tokens.dtype} "
+                                          f"{tuple(tokens.shape)}")
+        target = functional.build_matmul_tensor(1, self.n, self.n, self.n, device=tokens.device)
+        self._prove(tokens, rank, target, f"<{n},{n},{n}>")
+
+    @classmethod
+    def from_archive(cls, arch, index: Optional[int] = None, levels: int = 1) -> "BilinearMatmul":
+        """The algorithm of entry ``index`` of a ``SolutionArchive`` (None: the entry of lowest rank, the first of
+        equals).  The entry is proven again, against <n,n,n> with n = sqrt(arch.S): an archive may hold factorisations
+        of other targets.  Synchronises (``entries``)."""
+        fn = "BilinearMatmul.from_archive"
+        n = math.isqrt(arch.S)
+        if n * n != arch.S:
+            raise TensorGameError(fn, -1, f"the archive is of S={arch.S}, which is no square: no <n,n,n>")
+        tokens, rank = cls._entry(fn, arch, index)
+        return cls(tokens, rank, n=n, shift=arch.shift, levels=levels)
+
+    def _grid(self):
+        return ((self.n, "n"),) * 3
+
+    def _encode(self, x, part):
+        return ops.bilinear_encode(x, self.tokens, self.rank, self.n, part, self.shift)
+
+    def _decode(self, m, out):
+        return ops.bilinear_decode(m, self.tokens, self.rank, self.n, self.shift, out=out)
 
 
 def standard_rect(n: int, m: int, p: int, S: Optional[int] = None, shift: int = 1) -> torch.Tensor:
@@ -194,7 +224,7 @@ def standard_rect(n: int, m: int, p: int, S: Optional[int] = None, shift: int = 
     return tokens
 
 
-class RectBilinearMatmul:
+class RectBilinearMatmul(_Bilinear):
     """A proven factorisation of the rectangular tensor <n,m,p> in a cube of size S, run as a matrix multiplication:
     A is cut into n x m blocks, B into m x p, C into n x p, and R block products replace n*m*p.
 
@@ -207,15 +237,15 @@ class RectBilinearMatmul:
     the canonical form; there is no way round the proof.  The encodes and decodes are ``ops.bilinear_rect_encode`` and
     ``ops.bilinear_rect_decode`` (include/tensor_game_rect.h states their arithmetic bit for bit); the padding entries
     of the list (beyond n*m, m*p, n*p) are not read."""
+    _fn = "RectBilinearMatmul"
 
     def __init__(self, tokens: torch.Tensor, rank: int, n: int, m: int, p: int, S: Optional[int] = None, shift: int = 1,
                  levels: int = 1):
         """``tokens`` int8 (K,3S) on a ROCm device, of which the first ``rank`` rows are the list; S defaults to the
         width of ``tokens``.  Raises TensorGameError unless the list is proven against <n,m,p> in that cube.  One host
         sync (the proof's verdict)."""
-        fn = "RectBilinearMatmul"
-        if not tokens.is_cuda:
-            raise TensorGameError(fn, -1, f"tokens must live on a ROCm device (got {tokens.device}); there is no CPU path")
+        fn = self._fn
+        _need_device(fn, tokens, "tokens")
         self.n, self.m, self.p, self.shift, self.levels = int(n), int(m), int(p), int(shift), int(levels)
         if min(self.n, self.m, self.p) < 1:
             raise TensorGameError(fn, -1, f"n={n}, m={m}, p={p}: every dimension must be at least 1")
@@ -231,105 +261,23 @@ class RectBilinearMatmul:
         if tokens.shape[1] != 3 * self.S:
             raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * self.S}) for S={self.S}, got "
                                           f"{tuple(tokens.shape)}")
-        dev = tokens.device
-        target = functional.matmul_target(1, self.n, self.m, self.p, self.S, device=dev)
-        lengths = torch.full((1,), int(rank), dtype=torch.int64, device=dev)
-        canon, crank, _, res = ops.solution_canon(target, tokens[None], lengths, shift=self.shift)
-        res, crank = torch.stack((res, crank)).flatten().tolist()      # the one host sync
-        if res != 0:
-            what = "a bad row (its length, or a negation that leaves int8)" if res < 0 else f"residual_nnz={res}"
-            raise TensorGameError(fn, -1, f"the list is no factorisation of <{n},{m},{p}> at S={self.S}: {what}")
-        self.rank = int(crank)
-        self.tokens = canon[0, :self.rank].contiguous()
-        self.device = dev
+        target = functional.matmul_target(1, self.n, self.m, self.p, self.S, device=tokens.device)
+        self._prove(tokens, rank, target, f"<{n},{m},{p}> at S={self.S}")
 
     @classmethod
     def from_archive(cls, arch, n: int, m: int, p: int, index: Optional[int] = None,
                      levels: int = 1) -> "RectBilinearMatmul":
         """The algorithm of entry ``index`` of a ``SolutionArchive`` of cube size arch.S (None: the entry of lowest rank,
         the first of equals).  The entry is proven again, against <n,m,p>.  Synchronises (``entries``)."""
-        fn = "RectBilinearMatmul.from_archive"
-        tokens, rank, _, _ = arch.entries()
-        ranks = rank.tolist()
-        if not ranks:
-            raise TensorGameError(fn, -1, "the archive is empty")
-        if index is None:
-            index = ranks.index(min(ranks))
-        if not 0 <= index < len(ranks):
-            raise TensorGameError(fn, -1, f"index={index} outside [0,{len(ranks)})")
-        return cls(tokens[index].contiguous(), ranks[index], n, m, p, S=arch.S, shift=arch.shift, levels=levels)
+        tokens, rank = cls._entry("RectBilinearMatmul.from_archive", arch, index)
+        return cls(tokens, rank, n, m, p, S=arch.S, shift=arch.shift, levels=levels)
 
-    @property
-    def products(self) -> int:
-        """Leaf block products of one call: rank ** levels, where the schoolbook method takes (n*m*p) ** levels."""
-        return self.rank ** self.levels
+    def _grid(self):
+        return (self.n, "n"), (self.m, "m"), (self.p, "p")
 
-    def __call__(self, A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None, pad: bool = False,
-                 leaf=torch.bmm) -> torch.Tensor:
-        """A (...,P,Q) times B (...,Q,T), float32 or float64 on the list's device, equal leading dimensions.  P must be
-        a multiple of n^levels, Q of m^levels and T of p^levels, or ``pad`` zero-pads them up (with torch) and slices the
-        result.  ``leaf`` takes two (batch * rank^levels, ., .) operands and returns their batched product.  ``out``
-        (...,P,T) may not overlap A or B.  No host sync; capturable on one stream."""
-        fn = "RectBilinearMatmul"
-        for t, name in ((A, "A"), (B, "B")):
-            if not t.is_cuda:
-                raise TensorGameError(fn, -1, f"{name} must live on a ROCm device (got {t.device}); there is no CPU path")
-            if t.device != self.device:
-                raise TensorGameError(fn, -1, f"{name} is on {t.device}, the list on {self.device}")
-            if t.dim() < 2:
-                raise TensorGameError(fn, -1, f"{name} must have at least two dimensions, got {tuple(t.shape)}")
-        if A.dtype != B.dtype:
-            raise TensorGameError(fn, -1, f"mixed dtypes: A is {A.dtype}, B is {B.dtype}")
-        if A.dtype not in (torch.float32, torch.float64):
-            raise TensorGameError(fn, -1, f"A and B must be float32 or float64, got {A.dtype}")
-        lead, (P, Q), (Q2, T) = tuple(A.shape[:-2]), A.shape[-2:], B.shape[-2:]
-        if tuple(B.shape[:-2]) != lead or Q2 != Q:
-            raise TensorGameError(fn, -1, f"A {tuple(A.shape)} and B {tuple(B.shape)} do not multiply: equal leading "
-                                          "dimensions and Q are required")
-        if out is not None:
-            if out.dtype != A.dtype or tuple(out.shape) != (*lead, P, T) or out.device != A.device:
-                raise TensorGameError(fn, -1, f"out must be {A.dtype} {(*lead, P, T)} on {A.device}, got {out.dtype} "
-                                              f"{tuple(out.shape)} on {out.device}")
-            for t, name in ((A, "A"), (B, "B")):
-                if _overlap(out, t):
-                    raise TensorGameError(fn, -1, f"out overlaps {name}: in-place operation is not supported")
-        n, m, p, R = self.n, self.m, self.p, self.rank
-        sizes = {"P": (P, n, "n"), "Q": (Q, m, "m"), "T": (T, p, "p")}
-        up = {name: -size % d ** self.levels for name, (size, d, _) in sizes.items()}
-        if any(up.values()) and not pad:
-            name = next(k for k, v in up.items() if v)
-            size, d, letter = sizes[name]
-            raise TensorGameError(fn, -1, f"{name}={size} is no multiple of {letter}^levels={d ** self.levels} (pad=True "
-                                          "pads with zeros)")
-        batch = math.prod(lead)
-        a, b = A.reshape(batch, P, Q), B.reshape(batch, Q, T)
-        if any(up.values()):
-            a = torch.nn.functional.pad(a, (0, up["Q"], 0, up["P"]))
-            b = torch.nn.functional.pad(b, (0, up["T"], 0, up["Q"]))
-        a = a if a.stride(2) == 1 else a.contiguous()
-        b = b if b.stride(2) == 1 else b.contiguous()
-        for _ in range(self.levels):
-            a = ops.bilinear_rect_encode(a, self.tokens, R, n, m, 0, self.shift).flatten(0, 1)
-            b = ops.bilinear_rect_encode(b, self.tokens, R, m, p, 1, self.shift).flatten(0, 1)
-        mm = leaf(a, b)
-        if tuple(mm.shape) != (a.shape[0], a.shape[1], b.shape[2]) or mm.dtype != A.dtype:
-            raise TensorGameError(fn, -1, f"leaf returned {mm.dtype} {tuple(mm.shape)}, expected {A.dtype} "
-                                          f"{(a.shape[0], a.shape[1], b.shape[2])}")
-        mm = mm.contiguous()
-        direct = None                                   # the last decode writes into `out` itself where it can
-        if out is not None and not any(up.values()) and out.stride(-1) == 1:
-            try:
-                direct = out.view(batch, P, T)
-            except RuntimeError:
-                pass
-        for level in range(self.levels):
-            mm = mm.view(mm.shape[0] // R, R, mm.shape[1], mm.shape[2])
-            mm = ops.bilinear_rect_decode(mm, self.tokens, R, n, p, self.shift,
-                                          out=direct if level == self.levels - 1 else None)
-        if direct is not None:
-            return out
-        mm = mm[:, :P, :T].reshape(*lead, P, T)
-        if out is None:
-            return mm
-        out.copy_(mm)
-        return out
+    def _encode(self, x, part):
+        gr, gc = ((self.n, self.m), (self.m, self.p))[part]
+        return ops.bilinear_rect_encode(x, self.tokens, self.rank, gr, gc, part, self.shift)
+
+    def _decode(self, m, out):
+        return ops.bilinear_rect_decode(m, self.tokens, self.rank, self.n, self.p, self.shift, out=out)

@@ -1922,6 +1922,22 @@ def _bilinear_list(tokens: torch.Tensor, R: int, n: int, dev, fn: str) -> torch.
     return tokens if tokens.is_contiguous() else tokens.contiguous()
 
 
+def _bilinear_decode_out(M: torch.Tensor, R: int, gr: int, gc: int, out, fn: str) -> torch.Tensor:
+    """The checks of a decode's M (contiguous (batch,R,h,w)) and of its ``out`` (batch,gr*h,gc*w), which is made where
+    none is given."""
+    _need_gpu(M, "M")
+    if M.dtype not in _BILINEAR_DTYPES or M.dim() != 4 or M.shape[1] != R or not M.is_contiguous():
+        raise TensorGameError(fn, -1, f"M must be contiguous float32 or float64 (batch,R={R},h,w), got {M.dtype} "
+                                      f"{tuple(M.shape)}")
+    shape = (M.shape[0], gr * M.shape[2], gc * M.shape[3])
+    if out is None:
+        return torch.empty(shape, dtype=M.dtype, device=M.device)
+    if out.dtype != M.dtype or tuple(out.shape) != shape or out.device != M.device:
+        raise TensorGameError(fn, -1, f"out must be {M.dtype} {shape} on {M.device}, got {out.dtype} {tuple(out.shape)} "
+                                      f"on {out.device}")
+    return out
+
+
 def bilinear_encode(X, tokens, R: int, n: int, mode: int, shift: int = 1, out=None) -> torch.Tensor:
     """The R block combinations of ``batch`` matrices in one launch (include/tensor_game_bilinear.h): X float32 or
     float64 (batch,rows,cols), any row and batch stride (a view is not copied), cut into n x n blocks of (h,w);
@@ -1946,16 +1962,7 @@ def bilinear_decode(M, tokens, R: int, n: int, shift: int = 1, out=None) -> torc
     may be a strided view when given (column stride 1): block c of out[b] = sum_r (tokens[r][2S+c] - shift) * M[b][r].
     Every element is written.  No host sync."""
     fn = "bilinear_decode"
-    _need_gpu(M, "M")
-    if M.dtype not in _BILINEAR_DTYPES or M.dim() != 4 or M.shape[1] != R or not M.is_contiguous():
-        raise TensorGameError(fn, -1, f"M must be contiguous float32 or float64 (batch,R={R},h,w), got {M.dtype} "
-                                      f"{tuple(M.shape)}")
-    shape = (M.shape[0], n * M.shape[2], n * M.shape[3])
-    if out is None:
-        out = torch.empty(shape, dtype=M.dtype, device=M.device)
-    elif out.dtype != M.dtype or tuple(out.shape) != shape or out.device != M.device:
-        raise TensorGameError(fn, -1, f"out must be {M.dtype} {shape} on {M.device}, got {out.dtype} {tuple(out.shape)} "
-                                      f"on {out.device}")
+    out = _bilinear_decode_out(M, R, n, n, out, fn)
     batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(out, "out", fn)
     bilinear_check(batch, rows, cols, ld, stride, R, n, 0, shift, eb)
     tokens = _bilinear_list(tokens, R, n, M.device, fn)
@@ -2018,16 +2025,7 @@ def bilinear_rect_decode(M, tokens, R: int, gr: int, gc: int, shift: int = 1, ou
     (batch,gr*h,gc*w), which may be a strided view when given (column stride 1): block e of out[b] = sum_r
     (tokens[r][2S+e] - shift) * M[b][r].  Every element is written.  No host sync."""
     fn = "bilinear_rect_decode"
-    _need_gpu(M, "M")
-    if M.dtype not in _BILINEAR_DTYPES or M.dim() != 4 or M.shape[1] != R or not M.is_contiguous():
-        raise TensorGameError(fn, -1, f"M must be contiguous float32 or float64 (batch,R={R},h,w), got {M.dtype} "
-                                      f"{tuple(M.shape)}")
-    shape = (M.shape[0], gr * M.shape[2], gc * M.shape[3])
-    if out is None:
-        out = torch.empty(shape, dtype=M.dtype, device=M.device)
-    elif out.dtype != M.dtype or tuple(out.shape) != shape or out.device != M.device:
-        raise TensorGameError(fn, -1, f"out must be {M.dtype} {shape} on {M.device}, got {out.dtype} {tuple(out.shape)} "
-                                      f"on {out.device}")
+    out = _bilinear_decode_out(M, R, gr, gc, out, fn)
     batch, rows, cols, ld, stride, suffix, eb = _bilinear_matrices(out, "out", fn)
     tokens, S = _bilinear_rect_list(tokens, R, M.device, fn)
     bilinear_rect_check(batch, rows, cols, ld, stride, R, S, gr, gc, 2, shift, eb)
