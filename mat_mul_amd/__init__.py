@@ -18,7 +18,7 @@ __all__ = ["TensorGameEnv", "SyntheticDemos", "TranspositionTable", "TensorGameE
            "FusedAlphaTensor", "FusedAlphaTensor25", "net", "FusedTrainer", "SlicedTrainer", "SlicedTrainer25", "train", "rollout", "sample_rollouts", "RolloutResult",
            "solve_states", "solve_stream", "replay_io", "PackedGames", "save_run", "load_run", "Augment", "augment",
            "SolutionArchive", "solutions", "BasisSet", "solve_in_bases", "bases", "SymmetryGroup", "orbits",
-           "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "RectBilinearMatmul", "standard_rect", "bilinear",
+           "FlipWalks", "reduce_archive", "flips", "BilinearMatmul", "RectBilinearMatmul", "FusedBilinearMatmul", "standard_rect", "bilinear",
            "Mod2Walks", "Mod2Result", "reduce_mod2", "reduce_archive_mod2", "flips_mod2",
            "lift_signs", "LiftResult", "reduce_archive_lifted", "lift"]
 
@@ -53,6 +53,7 @@ _ATTRS = {
     "reduce_archive": "flips",
     "BilinearMatmul": "bilinear",
     "RectBilinearMatmul": "bilinear",
+    "FusedBilinearMatmul": "bilinear",
     "standard_rect": "bilinear",
     "Mod2Walks": "flips_mod2",
     "Mod2Result": "flips_mod2",

@@ -261,6 +261,12 @@ RECT_SIGNATURES = {
 }
 RECT_SIGNATURES["tg_bilinear_rect_encode_f64"] = RECT_SIGNATURES["tg_bilinear_rect_encode_f32"]
 RECT_SIGNATURES["tg_bilinear_rect_decode_f64"] = RECT_SIGNATURES["tg_bilinear_rect_decode_f32"]
+# name -> argtypes; every symbol include/tensor_game_products.h declares (limits: TG_MAX_S, TG_SOL_MAX_K, TG_SOL_MAX_SHIFT)
+PRODUCTS_SIGNATURES = {
+    "tg_bilinear_products_check": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i],
+    "tg_bilinear_products_bf16": [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _p, _p],
+}
+PRODUCTS_SIGNATURES["tg_bilinear_products_f16"] = PRODUCTS_SIGNATURES["tg_bilinear_products_bf16"]
 # limits and status bits of include/tensor_game_flips.h
 TG_FLIP_MAX_K, TG_FLIP_MAX_BOUND, TG_FLIP_MAX_STEPS = 128, 63, 65536
 TG_FLIP_BAD_LENGTH, TG_FLIP_BAD_RANGE, TG_FLIP_BAD_SRC = 1, 2, 4
@@ -325,7 +331,7 @@ def _load() -> C.CDLL:
                            **ROLLOUT_SIGNATURES, **ROLLOUT_MASKED_SIGNATURES, **ROLLOUT_SLOTS_SIGNATURES,
                            **SYMMETRY_SIGNATURES, **SOLUTION_SIGNATURES, **BASES_SIGNATURES,
                            **ORBIT_SIGNATURES, **FLIP_SIGNATURES, **FLIP_PLUS_SIGNATURES, **FLIP2_SIGNATURES,
-                           **LIFT2_SIGNATURES, **BILINEAR_SIGNATURES, **RECT_SIGNATURES}.items():
+                           **LIFT2_SIGNATURES, **BILINEAR_SIGNATURES, **RECT_SIGNATURES, **PRODUCTS_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover

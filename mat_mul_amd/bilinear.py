@@ -24,6 +24,9 @@ Not done here: a leaf GEMM of our own, half-precision operands, choosing ``level
 
 ``RectBilinearMatmul`` is the same for a rectangular <n,m,p> (include/tensor_game_rect.h: A in n x m blocks, B in m x p,
 C in n x p, a list of any cube size S >= max(n*m, m*p, n*p)), and ``standard_rect`` its schoolbook list.
+
+``FusedBilinearMatmul`` runs a proven list for <n,m,p> on bfloat16 or float16 operands: one ``ops.bilinear_products`` (the
+block combinations formed while the products load their tiles, include/tensor_game_products.h) and one float32 decode.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ import torch
 from . import functional, ops
 from ._lib import TG_BILINEAR_MAX_N, TG_BILINEAR_MIN_N, TG_MAX_S, TG_SOL_MAX_SHIFT, TensorGameError
 
-__all__ = ["BilinearMatmul", "RectBilinearMatmul", "standard_rect"]
+__all__ = ["BilinearMatmul", "RectBilinearMatmul", "FusedBilinearMatmul", "standard_rect"]
 
 
 def _byte_range(t: torch.Tensor):
@@ -281,3 +284,115 @@ class RectBilinearMatmul(_Bilinear):
 
     def _decode(self, m, out):
         return ops.bilinear_rect_decode(m, self.tokens, self.rank, self.n, self.p, self.shift, out=out)
+
+
+class FusedBilinearMatmul(_Bilinear):
+    """A proven factorisation of <n,m,p> in a cube of size S, run on bfloat16 or float16 operands in two launches: the R
+    block products with the block combinations formed on load (``ops.bilinear_products``: include/tensor_game_products.h
+    states the arithmetic; the combinations are rounded to the operands' type, the products accumulated in float32 on the
+    matrix cores), and ``ops.bilinear_rect_decode`` in float32 on the grid n x p.
+
+        alg = FusedBilinearMatmul(tokens, rank, n, m=None, p=None, S=None, shift=1)      # tokens int8 (K,3S), device
+        alg = FusedBilinearMatmul.from_archive(arch, n, m=None, p=None, index=None)
+        C = alg(A, B, out=None, pad=False)                        # A (...,P,Q) @ B (...,Q,T), bfloat16 or float16
+        alg.n, alg.m, alg.p, alg.S, alg.rank, alg.products        # products = rank
+
+    m and p default to n, S to the width of ``tokens``.  Construction proves the list (``ops.solution_canon`` against
+    ``functional.matmul_target(1, n, m, p, S)``) and runs the canonical form; there is no way round the proof.  The result is
+    float32.  There is no ``levels``: nothing is written between levels here that a second level could read, and a larger
+    grid does that job in one (the 49-term list for <4,4,4> is two levels of Strassen)."""
+    _fn = "FusedBilinearMatmul"
+
+    def __init__(self, tokens: torch.Tensor, rank: int, n: int, m: Optional[int] = None, p: Optional[int] = None,
+                 S: Optional[int] = None, shift: int = 1):
+        """``tokens`` int8 (K,3S) on a ROCm device, of which the first ``rank`` rows are the list.  Raises TensorGameError
+        unless the list is proven against <n,m,p> in that cube.  One host sync (the proof's verdict)."""
+        fn = self._fn
+        _need_device(fn, tokens, "tokens")
+        self.n, self.shift = int(n), int(shift)
+        self.m, self.p = self.n if m is None else int(m), self.n if p is None else int(p)
+        if min(self.n, self.m, self.p) < 1:
+            raise TensorGameError(fn, -1, f"n={self.n}, m={self.m}, p={self.p}: every dimension must be at least 1")
+        need = max(self.n * self.m, self.m * self.p, self.n * self.p)
+        if tokens.dtype != torch.int8 or tokens.dim() != 2 or tokens.shape[1] % 3:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,3S), got {tokens.dtype} {tuple(tokens.shape)}")
+        self.S = tokens.shape[1] // 3 if S is None else int(S)
+        if not need <= self.S <= TG_MAX_S:
+            raise TensorGameError(fn, -1, f"S={self.S} outside [max(n*m, m*p, n*p)={need},{TG_MAX_S}] for "
+                                          f"<{self.n},{self.m},{self.p}>")
+        if tokens.shape[1] != 3 * self.S:
+            raise TensorGameError(fn, -1, f"tokens must be int8 (K,{3 * self.S}) for S={self.S}, got "
+                                          f"{tuple(tokens.shape)}")
+        target = functional.matmul_target(1, self.n, self.m, self.p, self.S, device=tokens.device)
+        self._prove(tokens, rank, target, f"<{self.n},{self.m},{self.p}> at S={self.S}")
+
+    @classmethod
+    def from_archive(cls, arch, n: int, m: Optional[int] = None, p: Optional[int] = None,
+                     index: Optional[int] = None) -> "FusedBilinearMatmul":
+        """The algorithm of entry ``index`` of a ``SolutionArchive`` of cube size arch.S (None: the entry of lowest rank,
+        the first of equals).  The entry is proven again, against <n,m,p>.  Synchronises (``entries``)."""
+        tokens, rank = cls._entry("FusedBilinearMatmul.from_archive", arch, index)
+        return cls(tokens, rank, n, m, p, S=arch.S, shift=arch.shift)
+
+    @property
+    def products(self) -> int:
+        """Block products of one call: the rank, where the schoolbook method takes n*m*p."""
+        return self.rank
+
+    def __call__(self, A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 pad: bool = False) -> torch.Tensor:
+        """A (...,P,Q) times B (...,Q,T), both bfloat16 or both float16 on the list's device, equal leading dimensions;
+        returns float32 (...,P,T).  P must be a multiple of n, Q of m and T of p, or ``pad`` zero-pads them up (with
+        torch) and slices the result.  ``out`` (...,P,T) may be float32 (the decode writes into it where it can) or of
+        the operands' dtype (filled by ``copy_``, one more rounding); it may not overlap A or B.  No host sync;
+        capturable on one stream."""
+        fn = self._fn
+        for t, name in ((A, "A"), (B, "B")):
+            _need_device(fn, t, name)
+            if t.device != self.device:
+                raise TensorGameError(fn, -1, f"{name} is on {t.device}, the list on {self.device}")
+            if t.dim() < 2:
+                raise TensorGameError(fn, -1, f"{name} must have at least two dimensions, got {tuple(t.shape)}")
+        if A.dtype != B.dtype:
+            raise TensorGameError(fn, -1, f"mixed dtypes: A is {A.dtype}, B is {B.dtype}")
+        if A.dtype not in (torch.bfloat16, torch.float16):
+            raise TensorGameError(fn, -1, f"A and B must be bfloat16 or float16, got {A.dtype}")
+        lead, (P, Q), (Q2, T) = tuple(A.shape[:-2]), A.shape[-2:], B.shape[-2:]
+        if tuple(B.shape[:-2]) != lead or Q2 != Q:
+            raise TensorGameError(fn, -1, f"A {tuple(A.shape)} and B {tuple(B.shape)} do not multiply: equal leading "
+                                          "dimensions and Q are required")
+        if out is not None:
+            if out.dtype not in (torch.float32, A.dtype) or tuple(out.shape) != (*lead, P, T) or out.device != A.device:
+                raise TensorGameError(fn, -1, f"out must be torch.float32 or {A.dtype} {(*lead, P, T)} on {A.device}, got "
+                                              f"{out.dtype} {tuple(out.shape)} on {out.device}")
+            for t, name in ((A, "A"), (B, "B")):
+                if _overlap(out, t):
+                    raise TensorGameError(fn, -1, f"out overlaps {name}: in-place operation is not supported")
+        sizes = {"P": (P, self.n, "n"), "Q": (Q, self.m, "m"), "T": (T, self.p, "p")}
+        up = {name: -size % d for name, (size, d, _) in sizes.items()}
+        if any(up.values()) and not pad:
+            name = next(k for k, v in up.items() if v)
+            size, d, letter = sizes[name]
+            raise TensorGameError(fn, -1, f"{name}={size} is no multiple of {letter}={d} (pad=True pads with zeros)")
+        batch = math.prod(lead)
+        a, b = A.reshape(batch, P, Q), B.reshape(batch, Q, T)
+        if any(up.values()):
+            a = torch.nn.functional.pad(a, (0, up["Q"], 0, up["P"]))
+            b = torch.nn.functional.pad(b, (0, up["T"], 0, up["Q"]))
+        a = a if a.stride(2) == 1 else a.contiguous()
+        b = b if b.stride(2) == 1 else b.contiguous()
+        m = ops.bilinear_products(a, b, self.tokens, self.rank, self.n, self.m, self.p, self.shift)
+        direct = None                                   # the decode writes into a float32 `out` itself where it can
+        if out is not None and out.dtype == torch.float32 and not any(up.values()) and out.stride(-1) == 1:
+            try:
+                direct = out.view(batch, P, T)
+            except RuntimeError:
+                pass
+        c = ops.bilinear_rect_decode(m, self.tokens, self.rank, self.n, self.p, self.shift, out=direct)
+        if direct is not None:
+            return out
+        c = c[:, :P, :T].reshape(*lead, P, T)
+        if out is None:
+            return c
+        out.copy_(c)
+        return out

@@ -55,7 +55,8 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "tensor_game.h", 
                                             PKG.parent / "include" / "tensor_game_flips_mod2.h",
                                             PKG.parent / "include" / "tensor_game_lift.h",
                                             PKG.parent / "include" / "tensor_game_bilinear.h",
-                                            PKG.parent / "include" / "tensor_game_rect.h"]
+                                            PKG.parent / "include" / "tensor_game_rect.h",
+                                            PKG.parent / "include" / "tensor_game_products.h"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
          "-mllvm", "-amdgpu-mfma-vgpr-form",  # MFMA results in VGPRs (tg_mfma.h): no v_accvgpr moves
          "-Wall", "-Wno-unused-function"]

@@ -39,6 +39,7 @@ __all__ = [
     "lift2_check", "lift2_workspace_bytes", "lift2_signs",
     "bilinear_check", "bilinear_encode", "bilinear_decode",
     "reset_matmul_rect", "bilinear_rect_check", "bilinear_rect_encode", "bilinear_rect_decode",
+    "bilinear_products_check", "bilinear_products",
 ]
 
 
@@ -2031,4 +2032,57 @@ def bilinear_rect_decode(M, tokens, R: int, gr: int, gc: int, shift: int = 1, ou
     bilinear_rect_check(batch, rows, cols, ld, stride, R, S, gr, gc, 2, shift, eb)
     _launch(M.device, f"tg_bilinear_rect_decode_{suffix}", _ptr(M), batch, rows, cols, ld, stride, _ptr(tokens), int(R), S,
             int(gr), int(gc), int(shift), _ptr(out))
+    return out
+
+
+_PRODUCTS_DTYPES = {torch.bfloat16: "bf16", torch.float16: "f16"}
+
+
+def bilinear_products_check(batch: int, P: int, Q: int, T: int, lda: Optional[int] = None, stride_a: Optional[int] = None,
+                            ldb: Optional[int] = None, stride_b: Optional[int] = None, R: int = 1, S: int = 4, n: int = 2,
+                            m: int = 2, p: int = 2, shift: int = 1) -> None:
+    """Raise TensorGameError (naming the argument) unless tg_bilinear_products_* take these sizes (``lda`` defaults to Q,
+    ``ldb`` to T, the batch strides to rows * ld).  Host only."""
+    lda, ldb = Q if lda is None else lda, T if ldb is None else ldb
+    call("tg_bilinear_products_check", int(batch), int(P), int(Q), int(T), int(lda),
+         int(P * lda if stride_a is None else stride_a), int(ldb), int(Q * ldb if stride_b is None else stride_b), int(R),
+         int(S), int(n), int(m), int(p), int(shift))
+
+
+def _products_matrices(t: torch.Tensor, name: str, fn: str):
+    """(batch, rows, cols, ld, batch_stride) of a strided bfloat16 or float16 (batch,rows,cols) view, which is taken as it
+    is (no copy): only the column stride is held to 1."""
+    _need_gpu(t, name)
+    if t.dtype not in _PRODUCTS_DTYPES or t.dim() != 3:
+        raise TensorGameError(fn, -1, f"{name} must be bfloat16 or float16 (batch,rows,cols), got {t.dtype} "
+                                      f"{tuple(t.shape)}")
+    if t.stride(2) != 1:
+        raise TensorGameError(fn, -1, f"{name}: the column stride must be 1, got {t.stride(2)}")
+    batch, rows, cols = t.shape
+    ld = t.stride(1) if rows > 1 else max(t.stride(1), cols)
+    return batch, rows, cols, ld, t.stride(0) if batch > 1 else rows * ld
+
+
+def bilinear_products(A, B, tokens, R: int, n: int, m: int, p: int, shift: int = 1, out=None) -> torch.Tensor:
+    """The R block products of a bilinear algorithm for <n,m,p> in one launch (include/tensor_game_products.h): A (batch,P,Q)
+    and B (batch,Q,T), both bfloat16 or both float16, any row and batch stride (a view is not copied), A cut into n x m
+    blocks and B into m x p; tokens int8 (K,3S), of which rows 0 .. R-1 and the first n*m entries of part 0 and m*p of part 1
+    are used.  Returns ``out`` float32 (batch,R,P/n,T/p), contiguous: out[b][r] = rn(sum_e u_r[e] * block e of A[b]) times
+    rn(sum_e v_r[e] * block e of B[b]), the combinations rounded to the operands' type and never written to memory, the
+    products accumulated in float32 on the matrix cores.  No host sync."""
+    fn = "bilinear_products"
+    batch, P, Q, lda, stride_a = _products_matrices(A, "A", fn)
+    batch_b, Q2, T, ldb, stride_b = _products_matrices(B, "B", fn)
+    if A.dtype != B.dtype:
+        raise TensorGameError(fn, -1, f"mixed dtypes: A is {A.dtype}, B is {B.dtype}")
+    if batch_b != batch or Q2 != Q or B.device != A.device:
+        raise TensorGameError(fn, -1, f"A {tuple(A.shape)} on {A.device} and B {tuple(B.shape)} on {B.device} do not "
+                                      "multiply: equal batch, Q and device are required")
+    tokens, S = _bilinear_rect_list(tokens, R, A.device, fn)
+    bilinear_products_check(batch, P, Q, T, lda, stride_a, ldb, stride_b, R, S, n, m, p, shift)
+    if out is not None:
+        _need_gpu(out, "out")
+    out = _out(out, (batch, int(R), P // int(n), T // int(p)), torch.float32, A.device, "out")
+    _launch(A.device, f"tg_bilinear_products_{_PRODUCTS_DTYPES[A.dtype]}", _ptr(A), _ptr(B), batch, P, Q, T, lda, stride_a,
+            ldb, stride_b, _ptr(tokens), int(R), S, int(n), int(m), int(p), int(shift), _ptr(out))
     return out

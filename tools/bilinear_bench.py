@@ -27,6 +27,17 @@ of the rectangular entry's medians lies inside it.  Rows "footprint": the grids 
 the width rounded down to a multiple of 4; R = 2 gr gc terms with a third of the coefficients +-1), encode and decode,
 next to ``copy_`` of the same byte count.  Every row gives its bytes (each read or written once) and the share of the
 8 TB/s HBM peak they reach.
+
+    python tools/bilinear_bench.py OUT_DIR --fused [--sizes ...] [--reps 7] [--warmup 2]
+
+``FusedBilinearMatmul`` (include/tensor_game_products.h) on bfloat16 square matrices, with the same method; writes
+OUT_DIR/bilinear_fused_bench.json.  Lists: Strassen's (7 products), the standard <2,2,2> (8), the 49-term Kronecker square
+of Strassen's at n = 4, the standard <4,4,4> (64) and the standard <3,3,3> (27, at N rounded down to a multiple of 24 so
+that its blocks take 16-byte loads too).  Per size one loop alternates every list's ``alg(A, B, out=C)``, every list's
+products kernel alone (``ops.bilinear_products``) and ``torch.matmul`` on the same operands.  Rows "fused": the three
+times, the products' share of the call, the ratio to torch.matmul and the deviation from it over the largest entry.
+Rows "ratio": time(7) / time(8) and time(49) / time(64), of the whole call and of the products alone, next to 7/8 and
+49/64: what encode-on-load lets the saved products show.
 """
 from __future__ import annotations
 
@@ -42,7 +53,7 @@ import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-from mat_mul_amd import BilinearMatmul, ops, standard_rect  # noqa: E402
+from mat_mul_amd import BilinearMatmul, FusedBilinearMatmul, ops, standard_rect  # noqa: E402
 
 DEV = "cuda:0"
 HBM_PEAK_TB_PER_S = 8.0
@@ -166,6 +177,73 @@ def rect_rows(args):
             torch.cuda.empty_cache()
 
 
+def kron_square(f, n):
+    """The Kronecker square of the coefficients f (R,3n^2) of an algorithm for <n,n,n>: one for <n^2,n^2,n^2>, term
+    r1*R + r2 with u[(i1*n+i2)*n^2 + (j1*n+j2)] = u1[i1*n+j1] * u2[i2*n+j2], likewise v and w."""
+    S, N = n * n, n * n
+    out = np.zeros((len(f) ** 2, 3 * N * N), dtype=np.int64)
+    for r1 in range(len(f)):
+        for r2 in range(len(f)):
+            for d in range(3):
+                x1, x2 = (g[d * S:(d + 1) * S].reshape(n, n) for g in (f[r1], f[r2]))
+                out[r1 * len(f) + r2, d * N * N:(d + 1) * N * N] = np.einsum("ij,kl->ikjl", x1, x2).reshape(N * N)
+    return out
+
+
+def fused_rows(args):
+    """The --fused rows (the module's text says what they are)."""
+    out = Path(args.out) / "bilinear_fused_bench.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    res = {"torch": torch.__version__, "device": torch.cuda.get_device_name(0), "dtype": "bfloat16", "rows": []}
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    strassen = np.load(ROOT / "tests" / "golden" / "strassen.npz")["tokens"].astype(np.int64)[:7] - 1
+    lists = [("strassen", torch.from_numpy((strassen + 1).astype(np.int8)), 2), ("standard2", standard_rect(2, 2, 2), 2),
+             ("kron49", torch.from_numpy((kron_square(strassen, 2) + 1).astype(np.int8)), 4), ("standard4", standard_rect(4, 4, 4), 4),
+             ("standard3", standard_rect(3, 3, 3), 3)]
+    algs = [(name, FusedBilinearMatmul(tok.to(DEV), tok.shape[0], n), n) for name, tok, n in lists]
+
+    def emit(row):
+        res["rows"].append(row)
+        print(json.dumps(row), flush=True)
+        out.write_text(json.dumps(res, indent=1) + "\n")
+
+    for N in args.sizes:
+        A = torch.randn((N, N), device=DEV, generator=gen).bfloat16()
+        B = torch.randn((N, N), device=DEV, generator=gen).bfloat16()
+        C, D = torch.empty((N, N), device=DEV), torch.empty_like(A)
+        fns, side = [], {}
+        for name, alg, n in algs:
+            side[name] = M = N if n != 3 else N // 24 * 24
+            a, b, c = A[:M, :M], B[:M, :M], C[:M, :M]
+            prod = torch.empty((1, alg.rank, M // n, M // n), device=DEV)
+            fns.append(lambda alg=alg, a=a, b=b, c=c: alg(a, b, out=c))
+            fns.append(lambda alg=alg, a=a, b=b, n=n, prod=prod: ops.bilinear_products(a[None], b[None], alg.tokens, alg.rank, n, n, n,
+                                                                                       alg.shift, out=prod))
+        fns.append(lambda: torch.matmul(A, B, out=D))
+        times = alternate(fns, args.warmup, args.reps)
+        theirs = times[-1]
+        whole, alone = {}, {}
+        for i, (name, alg, n) in enumerate(algs):
+            whole[name], alone[name] = times[2 * i], times[2 * i + 1]
+            M = side[name]
+            alg(A[:M, :M], B[:M, :M], out=C[:M, :M])
+            ref = torch.matmul(A[:M, :M].float(), B[:M, :M].float())
+            emit({"kind": "fused", "list": name, "n": n, "N": M, "products": alg.products, "schoolbook_products": n ** 3,
+                  "fused": whole[name], "products_alone": alone[name], "torch_matmul_bf16_at_N": N, "torch_matmul": theirs,
+                  "products_share_of_call": alone[name]["median_us"] / whole[name]["median_us"],
+                  "ratio_to_torch_matmul": whole[name]["median_us"] / theirs["median_us"],
+                  "TFLOP_per_s_of_the_product": 2.0 * M ** 3 / whole[name]["median_us"] * 1e-6,
+                  "max_deviation_from_float32_matmul": float((C[:M, :M] - ref).abs().max() / ref.abs().max())})
+            del ref
+        for few, many, ideal in (("strassen", "standard2", 7 / 8), ("kron49", "standard4", 49 / 64)):
+            spread = lambda t: [t[few]["p10_us"] / t[many]["p90_us"], t[few]["p90_us"] / t[many]["p10_us"]]  # noqa: E731
+            emit({"kind": "ratio", "of": [few, many], "N": N, "ideal": ideal,
+                  "fused": whole[few]["median_us"] / whole[many]["median_us"], "fused_p10_p90": spread(whole),
+                  "products_alone": alone[few]["median_us"] / alone[many]["median_us"], "products_alone_p10_p90": spread(alone)})
+        del A, B, C, D, fns
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
@@ -173,9 +251,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rect", action="store_true", help="the rectangular entries instead (bilinear_rect_bench.json)")
+    ap.add_argument("--fused", action="store_true", help="FusedBilinearMatmul in bfloat16 instead (bilinear_fused_bench.json)")
     args = ap.parse_args()
     if args.rect:
         return rect_rows(args)
+    if args.fused:
+        return fused_rows(args)
     out = Path(args.out) / "bilinear_bench.json"
     out.parent.mkdir(parents=True, exist_ok=True)
     strassen = np.load(ROOT / "tests" / "golden" / "strassen.npz")["tokens"].astype(np.int8)
